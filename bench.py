@@ -1,8 +1,14 @@
 """Benchmark: DDSP harmonic-plus-noise synthesis on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's audio if
+--dump-outputs is given and prints the headline line (metric, value, unit, ms_per_step, ...).
+Everything else — the in-region kernel events and rooflines, the per-kernel breakdown, the
+uncached-IR / pipelined / gathered / scatter-gather / op-boundary / training / loss / decoder /
+realtime legs and the CPU baseline — runs only with --full (each leg still has its --no-* switch).
 
 A step = one pass of the synthesis path (decoder.py:106-125: frame-rate controls ->
 harmonic + filtered noise -> 1 s reverb -> audio) over one batch of configuration 2
@@ -97,6 +103,11 @@ def parse():
     p.add_argument("--sample-rate", type=int, default=48000)
     p.add_argument("--reverb-length", type=int, default=None)
     p.add_argument("--noise", choices=("device", "inject"), default="device")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: in-region kernel events and rooflines, "
+                        "per-kernel breakdown, the other legs (each with its --no-* switch) and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's audio as DIR/signal.npy (float32)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-op-leg", action="store_true")
     p.add_argument("--chunks", type=int, default=4,
@@ -175,6 +186,23 @@ def load_traffic(path):
             return json.load(f)
     except (OSError, ValueError):
         return {}
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out, directory, name="signal"):
+    """Write what the timed step returned (the audio [B, F*bs, 1] of its last call) as
+    directory/<name>.npy in float32.  An output above DUMP_MAX_BYTES is written as a fixed sample:
+    the elements at the sorted flat indices numpy.random.default_rng(0).integers(0, numel, n)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    a = out.detach().to("cpu", torch.float32).numpy()
+    n = DUMP_MAX_BYTES // 4
+    if a.size > n:
+        idx = np.sort(np.random.default_rng(0).integers(0, a.size, n))
+        a = a.reshape(-1)[idx]
+    np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def cpu_baseline(args, rank_inputs_seed=0):
@@ -638,10 +666,10 @@ def main():
                            args.sample_rate)
     inp = make_inputs(B, F, H, NB, bs, seed=rank, device=dev, with_noise=(args.noise == "inject"))
     syn = SynthPath(bs, sr, reverb_length=args.reverb_length, noise_mode=args.noise).to(dev)
-    # timed region: events only around the dominant kernel (the roofline's launch duration);
-    # the per-kernel breakdown is measured in a separate loop afterwards
+    # timed region (--full only): events around the dominant kernel alone (the roofline's launch
+    # duration); the per-kernel breakdown is measured in a separate loop afterwards
     timer = EventTimer(["synth_frames"])
-    syn.timer = timer
+    syn.timer = timer if args.full else None
     core.set_noise_seed(1234 + rank)
 
     def step():
@@ -658,6 +686,9 @@ def main():
             torch.cuda.synchronize()
     torch.cuda.synchronize()
     warm_s = time.perf_counter() - tw
+    # the settling loop's step count varies with the clock: rewind the device-noise stream so that timed
+    # step k draws Philox offset k on every run (the outputs of --dump-outputs repeat from run to run)
+    core.set_noise_seed(1234 + rank)
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -676,6 +707,29 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+
+    samples_per_step = B * F * bs * world
+    value = samples_per_step * args.steps / elapsed
+    result = {
+        "metric": "audio samples/sec (48 kHz, 100 harm, blk=512) at 1/2/4/8 GPU; % HBM roofline",
+        "value": round(value, 1), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "warmup_steps_run": warm_steps, "warmup_s": round(warm_s, 3),
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp32",
+        "data": f"synthetic (SURVEY 8(d) seeded controls; noise {'on-device Philox' if args.noise == 'device' else 'injected'})",
+        "config": {"workload": f"config {args.config} synth path: batch {B}/GPU, frames {F}, block_size {bs}, "
+                               f"n_harmonic {H}, n_bands {NB}, sr {sr}, reverb {args.reverb_length} taps",
+                   "global_batch": B * world, "seq_len": F * bs, "parallelism": f"batch-shard x{world}"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # per-kernel breakdown: one event pair per step, one kernel group per loop (events around
     # every group of a step add their own gaps and read high against rocprofv3)
@@ -693,8 +747,6 @@ def main():
         kern_ms[name] = breakdown.mean_ms(name)
     syn.timer = None
 
-    samples_per_step = B * F * bs * world
-    value = samples_per_step * args.steps / elapsed
     traffic = load_traffic(args.traffic)
 
     # dominant kernel: the fused synthesis kernel (per launch = B*F*bs samples of this rank).  Its
@@ -767,16 +819,7 @@ def main():
                                    "event-timed duration (kernel_ms.reverb); traffic = PMC FETCH_SIZE + WRITE_SIZE "
                                    "per group (profiles/pmc_traffic.json)"}
 
-    result = {
-        "metric": "audio samples/sec (48 kHz, 100 harm, blk=512) at 1/2/4/8 GPU; % HBM roofline",
-        "value": round(value, 1), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "warmup_steps_run": warm_steps, "warmup_s": round(warm_s, 3),
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp32",
-        "data": f"synthetic (SURVEY 8(d) seeded controls; noise {'on-device Philox' if args.noise == 'device' else 'injected'})",
-        "config": {"workload": f"config {args.config} synth path: batch {B}/GPU, frames {F}, block_size {bs}, "
-                               f"n_harmonic {H}, n_bands {NB}, sr {sr}, reverb {args.reverb_length} taps",
-                   "global_batch": B * world, "seq_len": F * bs, "parallelism": f"batch-shard x{world}"},
+    result.update({
         "roofline": roofline,
         "op_boundary_effective": op_boundary_effective,
         "roofline_reverb": roofline_reverb,
@@ -785,7 +828,7 @@ def main():
                           "roofline.avg_launch_ms is from inside it.  The synthesis kernel's time depends "
                           "on what ran before it (the shader clock it gets after the reverb's MAC, "
                           "DESIGN.md 3c)",
-    }
+    })
 
     if syn.reverb is not None and not args.no_uncached_leg:
         # the reference rebuilds the impulse and its transform on every Reverb.forward

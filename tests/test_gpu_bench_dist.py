@@ -28,7 +28,7 @@ def test_bench_under_torch_distributed_run_world1():
         pytest.skip("no HIP device")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "1",
-           "--steps", "3", "--warmup", "2", "--settle", "0", "--noise", "inject", "--no-cpu-baseline",
+           "--full", "--steps", "3", "--warmup", "2", "--settle", "0", "--noise", "inject", "--no-cpu-baseline",
            "--no-train-leg", "--no-loss-leg", "--no-model-train-leg", "--no-decoder-leg", "--no-op-leg",
            "--no-pipelined-leg", "--no-uncached-leg"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 LOG=gpurun_out/ab_step.log
 : > $LOG
-ARGS="--no-train-leg --no-loss-leg --no-model-train-leg --no-decoder-leg --no-op-leg --no-cpu-baseline --no-uncached-leg --no-pipelined-leg"
+ARGS="--full --no-train-leg --no-loss-leg --no-model-train-leg --no-decoder-leg --no-op-leg --no-cpu-baseline --no-uncached-leg --no-pipelined-leg"
 for rep in 1 2; do
   for v in "$@"; do
     if [ "$v" = base ]; then LIB=$PWD/ddsp_pytorch_amd/lib/libddsp_hip.so; else LIB=$PWD/build/ab_$v.so; fi

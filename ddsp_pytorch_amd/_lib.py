@@ -67,6 +67,14 @@ SIGNATURES = {
                                                    _I64, _I64, _I64, _I64, _I64, _F, _P]),
     "ddsp_hip_frame_phase_prefix": (_I, [_P, _I64, _I64, _I64, _F, _P, _P]),
     "ddsp_hip_synth_frames_counter": (_I, [_P, _P, _P, _F, _U64, _P, _P, _I64, _I64, _I64, _I64, _I64, _F, _P]),
+    # seamless realtime streaming
+    "ddsp_hip_stream_state_bytes": (_SZ, [_I64, _I64, _I64]),
+    "ddsp_hip_stream_spectrum_floats": (_SZ, [_I64, _I64]),
+    "ddsp_hip_stream_spectrum": (_I, [_P, _I64, _I64, _P, _SZ, _P]),
+    "ddsp_hip_stream_synth_frames": (_I, [_P, _P, _P, _F, _P, _U64, _P, _P, _SZ, _I, _P, _P, _P, _I64, _I64, _I64,
+                                          _I64, _I64, _F, _P]),
+    "ddsp_hip_stream_reverb": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _I64, _I64, _I64, _P]),
+    "ddsp_hip_stream_advance": (_I, [_P, _P, _P, _SZ, _I, _I64, _I64, _I64, _F, _P]),
     "ddsp_hip_reverb_build_impulse": (_I, [_P, _P, _P, _P, _I64, _F, _P]),
     "ddsp_hip_reverb_spectrum_floats": (_SZ, [_I64, _I64]),
     "ddsp_hip_reverb_workspace_size": (_SZ, [_I64, _I64, _I64]),

@@ -831,6 +831,125 @@ def _reverb_apply_launch(x, spectrum, ir_length):
     return out, ws
 
 
+# ------------------------------------------------------------------------------------
+# seamless realtime streaming (ddsp_hip_stream_*): K calls of N samples render what one call of
+# K N samples renders — the oscillator phase carried between calls, a reverb with its full IR
+# ------------------------------------------------------------------------------------
+class StreamState:
+    """The device state of one realtime stream: ``buf`` (uint8, ddsp_hip_stream_state_bytes: the phase
+    carry per item, then — with ``ir_length`` > 0 — the streamed reverb's input history and its ring of
+    block spectra) and ``counter`` (int64[1], the call index: Philox offset and ring slot).  Zero-filled
+    is a fresh stream."""
+
+    def __init__(self, batch, device, call_samples=0, ir_length=0):
+        self.batch, self.call_samples, self.ir_length = int(batch), int(call_samples), int(ir_length)
+        if self.batch < 1:
+            raise RuntimeError("StreamState: batch must be at least 1")
+        nbytes = int(_lib.query("stream_state_bytes", self.batch, self.call_samples, self.ir_length))
+        if nbytes == 0:
+            raise RuntimeError("StreamState: the streamed reverb takes calls of a power-of-two size in "
+                               f"[64, 2048] samples; got {self.call_samples}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("ddsp_hip: the stream state lives on a HIP device (no CPU fallback)")
+        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=device)
+
+    @property
+    def carry(self):
+        """float64 [batch] view of the running phase prefix (writable: a preset phase)."""
+        return self.buf[:8 * self.batch].view(torch.float64)
+
+    def reset(self):
+        self.buf.zero_()
+        self.counter.zero_()
+
+
+def stream_spectrum(impulse, call_samples):
+    """The streamed reverb's IR partition spectra for calls of ``call_samples``: the impulse
+    (Reverb.build_impulse, any shape, L values) at its full length, never cropped to the call."""
+    _dev(impulse)
+    h = _c(impulse.reshape(-1))
+    floats = int(_lib.query("stream_spectrum_floats", int(call_samples), h.numel()))
+    if floats == 0:
+        raise RuntimeError("stream_spectrum: call_samples must be a power of two in [64, 2048] and the "
+                           f"impulse non-empty; got {int(call_samples)}, {h.numel()} taps")
+    spec = torch.empty(floats, dtype=torch.float32, device=h.device)
+    _lib.call("stream_spectrum", _lib.ptr(h), h.numel(), int(call_samples), _lib.ptr(spec), floats,
+              _lib.stream_of(h))
+    return spec
+
+
+def stream_synth_frames(f0, param, mags, block_size, sample_rate, state, seed=0, bias=-5.0, noise=None,
+                        wrap=True, parts=False):
+    """synth_frames for one call of a stream: frame f starts from the phase ``state.carry[b]`` plus its own
+    prefix within the call (``wrap``: the carry taken modulo 2 pi).  ``noise`` [B,F,bs] injected, else
+    on-device Philox with (seed, offset = state.counter).  Reads the state; ``stream_advance`` ends the
+    call.  -> signal [B, F*bs, 1], with ``parts`` (signal, harmonic, noise).  Inference only."""
+    _dev(f0, param, mags)
+    B, F, H1 = param.shape
+    NB = mags.shape[-1]
+    bs = int(block_size)
+    if f0.shape != (B, F, 1) or mags.shape[:2] != (B, F) or H1 < 2:
+        raise RuntimeError("stream_synth_frames: f0 [B,F,1], param [B,F,H+1], mags [B,F,NB] expected")
+    if state.batch != B or state.buf.device != f0.device:
+        raise RuntimeError("stream_synth_frames: the stream state is for another batch size or device")
+    if not synth_frames_in_envelope(H1 - 1, NB, bs, B):
+        raise RuntimeError("stream_synth_frames: shape outside the fused kernel's envelope")
+    if noise is not None:
+        _dev(noise)
+        if tuple(noise.shape) != (B, F, bs):
+            raise RuntimeError(f"stream_synth_frames: noise must be [B, F, block_size] = {(B, F, bs)}")
+        noise = _c(noise)
+    out = torch.empty(B, F * bs, 1, dtype=torch.float32, device=f0.device)
+    harm = torch.empty_like(out) if parts else None
+    nz = torch.empty_like(out) if parts else None
+    _lib.call("stream_synth_frames", _lib.ptr(_c(f0)), _lib.ptr(_c(param)), _lib.ptr(_c(mags)), float(bias),
+              _lib.ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(state.counter), _lib.ptr(state.buf),
+              state.buf.numel(), int(bool(wrap)), _lib.ptr(out), _lib.ptr(harm), _lib.ptr(nz), B, F, H1 - 1, NB,
+              bs, float(sample_rate), _lib.stream_of(out))
+    return (out, harm, nz) if parts else out
+
+
+def stream_reverb(x, spectrum, state, out=None):
+    """One call of the streamed reverb: x [B, N] or [B, N, 1] -> the same shape, such that the calls laid end
+    to end are the causal convolution of the whole input with the full impulse (``stream_spectrum``).
+    Writes the state's history and ring slot; ``stream_advance`` ends the call.  ``out``: a contiguous buffer of
+    x's shape to write to; it may be x itself (in place)."""
+    _dev(x, spectrum)
+    B, N = x.shape[0], x.shape[1]
+    if x.numel() != B * N:
+        raise RuntimeError("stream_reverb: x [B, N] or [B, N, 1] expected")
+    if state.batch != B or state.call_samples != N or state.ir_length < 1 or state.buf.device != x.device:
+        raise RuntimeError("stream_reverb: the stream state is for another batch, call size or device, or has "
+                           "no reverb section")
+    if out is None:
+        out = torch.empty_like(x, memory_format=torch.contiguous_format)
+    else:
+        _dev(out)
+        if out.shape != x.shape or not out.is_contiguous() or out.device != x.device:
+            raise RuntimeError("stream_reverb: out must be a contiguous tensor of x's shape on its device")
+    _lib.call("stream_reverb", _lib.ptr(_c(x)), _lib.ptr(_c(spectrum)), spectrum.numel(), _lib.ptr(state.counter),
+              _lib.ptr(state.buf), state.buf.numel(), _lib.ptr(out), B, N, state.ir_length, _lib.stream_of(out))
+    return out
+
+
+def stream_advance(state, f0=None, block_size=1, sample_rate=1.0, wrap=True):
+    """The end of a stream call (one launch): the carry moves on by the call's phase, sum_f bs inc(f0[b,f])
+    (``wrap``: modulo 2 pi), and the counter by one.  Without ``f0`` (a stream with no synthesis) the
+    counter alone."""
+    if f0 is None:
+        _lib.call("stream_advance", None, _lib.ptr(state.counter), _lib.ptr(state.buf), state.buf.numel(),
+                  int(bool(wrap)), 0, 0, 1, 1.0, _lib.stream_of(state.buf))
+        return
+    _dev(f0)
+    B, F = f0.shape[0], f0.shape[1]
+    if f0.shape != (B, F, 1) or state.batch != B or state.buf.device != f0.device:
+        raise RuntimeError("stream_advance: f0 [B,F,1] on the state's device and of its batch size expected")
+    _lib.call("stream_advance", _lib.ptr(f0.contiguous()), _lib.ptr(state.counter), _lib.ptr(state.buf),
+              state.buf.numel(), int(bool(wrap)), B, F, int(block_size), float(sample_rate), _lib.stream_of(f0))
+
+
 from . import grad as _grad  # noqa: E402  (autograd Functions over the backward kernels)
 
 

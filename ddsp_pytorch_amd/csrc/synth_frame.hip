@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "noise_dsp.h"
+#include "stream_state.h"
 
 namespace ddsp {
 namespace {
@@ -48,13 +49,16 @@ __device__ __forceinline__ void osc_bank4(const float2* __restrict__ coef, int H
 // (the dicts DDSPDecoder.forward returns) to ctrl_out.  PREFIX: read the frame's phase prefix from
 // prefix[] (long renders) instead of summing the earlier frames; its own instantiations, so the
 // training / serving shapes run the code without the branch (1.9% of the kernel, same-box A/B).
-template <bool RNG, bool SPLIT, bool PAD, bool CTRL, bool PREFIX>
+// CARRY: the item's phase at the start of the call (carry0, the realtime stream's running prefix) is added to
+// the frame's own prefix, so a stream of calls continues the oscillators of the call before.
+template <bool RNG, bool SPLIT, bool PAD, bool CTRL, bool PREFIX, bool CARRY = false>
 __device__ __forceinline__ bool frame_synth(
     const float* __restrict__ f0, const float* __restrict__ param, const float* __restrict__ mags,
     float bias, const float* __restrict__ noise, uint32_t k0, uint32_t k1, uint32_t off0, uint32_t off1,
     const uint64_t* __restrict__ counter, float* __restrict__ ctrl_out, int B, int F, int H, int NB, int bs,
     float sr, int lo_end, int tail_start, int pad, int f, int b, int tid, int NT, float4* smem4, double* red,
-    int w0, float (&acc)[4], float (&nz)[4], int& j0_out, int ldp, int ldm, const double* __restrict__ prefix) {
+    int w0, float (&acc)[4], float (&nz)[4], int& j0_out, int ldp, int ldm, const double* __restrict__ prefix,
+    double carry0 = 0.0) {
   const int n = 2 * (NB - 1), half = n >> 1, n4 = (n + 3) & ~3;
   const int H4 = (H + 3) & ~3;
   float2* coef = reinterpret_cast<float2*>(smem4);       // [H4] (k+1, amplitude)
@@ -79,6 +83,7 @@ __device__ __forceinline__ bool frame_synth(
   } else {       // O(f) per frame: fine for the few hundred frames of a training / serving batch
     for (int g = tid; g < f; g += NT) part_s += (double)bs * (double)phase_inc(f0b[g], sr);
   }
+  if (CARRY && tid == 0) part_s += carry0;
   // the frame's H + NB + 1 scale_function values as one work list (item i at thread i mod NT, in
   // ascending i, so the distribution's partial sums keep their order): harmonic distribution
   // (modules.py:53-60 before normalisation), noise magnitudes (modules.py:113), then the amplitude
@@ -361,6 +366,49 @@ __global__ void __launch_bounds__(256) frame_prefix_kernel(const float* __restri
   }
 }
 
+// The realtime stream's frame kernel (ddsp_hip_stream_synth_frames): synth_frame_kernel with the item's phase
+// carried over from the calls before, S = carry[b] + sum_{g<f} bs inc_g in fp64 (wrap: the carry reduced modulo
+// 2 pi first, so a preset or long-running carry never costs omega its fp32 resolution).  The kernel only reads
+// the carry and the call counter; stream_advance_kernel moves both after it.
+template <bool RNG, bool SPLIT>
+__global__ void __launch_bounds__(256) synth_stream_kernel(
+    const float* __restrict__ f0, const float* __restrict__ param, const float* __restrict__ mags, float bias,
+    const float* __restrict__ noise, uint32_t k0, uint32_t k1, const uint64_t* __restrict__ counter,
+    const double* __restrict__ carry, int wrap, float* __restrict__ out, float* __restrict__ harm_out,
+    float* __restrict__ noise_out, int F, int H, int NB, int bs, float sr, int lo_end, int tail_start, int pad) {
+  extern __shared__ float4 smem4[];
+  __shared__ double red[32];
+  float acc[4], nz[4];
+  int j0;
+  const double c = carry[blockIdx.y];
+  const double c0 = wrap ? wrap_2pi(c) : c;
+  if (!frame_synth<RNG, SPLIT, false, false, false, true>(f0, param, mags, bias, noise, k0, k1, 0u, 0u, counter, nullptr,
+                                                          (int)gridDim.y, F, H, NB, bs, sr, lo_end, tail_start, pad,
+                                                          blockIdx.x, blockIdx.y, threadIdx.x, blockDim.x, smem4, red, 0,
+                                                          acc, nz, j0, H + 1, NB, nullptr, c0))
+    return;
+  const int64_t o = ((int64_t)blockIdx.y * F + blockIdx.x) * bs + j0;
+  if (harm_out) *reinterpret_cast<float4*>(harm_out + o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  if (noise_out) *reinterpret_cast<float4*>(noise_out + o) = make_float4(nz[0], nz[1], nz[2], nz[3]);
+  *reinterpret_cast<float4*>(out + o) =
+      make_float4(acc[0] + nz[0], acc[1] + nz[1], acc[2] + nz[2], acc[3] + nz[3]);
+}
+
+// The end of a stream call, one workgroup: carry[b] += sum_g bs inc_g over the call's frames (exact fp64 terms, as
+// the frame kernels sum them; wrap: reduced modulo 2 pi before and after) and *counter += 1.
+__global__ void __launch_bounds__(256) stream_advance_kernel(const float* __restrict__ f0, uint64_t* counter,
+                                                            double* __restrict__ carry, int wrap, int B, int F, int bs,
+                                                            float sr) {
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const float* f0b = f0 + (int64_t)b * F;
+    double c = carry[b];
+    if (wrap) c = wrap_2pi(c);
+    for (int g = 0; g < F; ++g) c += (double)bs * (double)phase_inc(f0b[g], sr);
+    carry[b] = wrap ? wrap_2pi(c) : c;
+  }
+  if (threadIdx.x == 0) *counter += 1;
+}
+
 }  // namespace
 }  // namespace ddsp
 
@@ -502,6 +550,58 @@ int ddsp_hip_synth_frames_counter(const float* f0, const float* param, const flo
   if (!counter) return DDSP_HIP_EINVAL;
   return synth_frames_launch(f0, param, raw_magnitudes, bias, nullptr, seed, 0, counter, out, nullptr, nullptr,
                              nullptr, batch, frames, n_harmonic, n_bands, block_size, sample_rate, stream);
+}
+
+int ddsp_hip_stream_synth_frames(const float* f0, const float* param, const float* raw_magnitudes, float bias,
+                                 const float* noise, uint64_t seed, const uint64_t* counter, const void* state,
+                                 size_t state_bytes, int wrap, float* out, float* harmonic_out, float* noise_out,
+                                 int64_t batch, int64_t frames, int64_t n_harmonic, int64_t n_bands,
+                                 int64_t block_size, float sample_rate, void* stream) {
+  if (batch < 0 || frames < 0 || n_harmonic < 1 || n_bands < 2 || block_size < 4 || !(sample_rate > 0))
+    return DDSP_HIP_EINVAL;
+  if (batch == 0 || frames == 0) return DDSP_HIP_OK;
+  if (!f0 || !param || !raw_magnitudes || !out || !state || (!noise && !counter)) return DDSP_HIP_EINVAL;
+  if (block_size % 4 || block_size > 1024 || n_harmonic > 1024 || n_bands > 1025 || batch > 65535 ||
+      frames > INT32_MAX)
+    return DDSP_HIP_ERANGE;
+  const int bs = (int)block_size;
+  const FrameShape fs = frame_shape(n_harmonic, n_bands, bs);
+  if (sizeof(float) * fs.floats > 120 * 1024) return DDSP_HIP_ERANGE;
+  if (state_bytes < (size_t)batch * sizeof(double)) return DDSP_HIP_EWORKSPACE;
+  const int nt = std::max(64, ((bs / 4 + 63) / 64) * 64);
+  // few frames per call: each frame's harmonics split over G thread groups, as in ddsp_hip_synth_frames
+  int G = batch * frames < 512 ? std::max(1, std::min(4, 256 / nt)) : 1;
+  if (sizeof(float) * (fs.floats + (size_t)bs) > 120 * 1024) G = 1;
+  const size_t shm = sizeof(float) * (fs.floats + (G > 1 ? (size_t)bs : 0));
+  const dim3 grid((unsigned)frames, (unsigned)batch), block((unsigned)(nt * G));
+  const double* carry = reinterpret_cast<const double*>(state);
+#define DDSP_SYNTH_STREAM_LAUNCH(RNG_, SPLIT_)                                                                     \
+  hipLaunchKernelGGL((synth_stream_kernel<RNG_, SPLIT_>), grid, block, shm, S(stream), f0, param, raw_magnitudes,  \
+                     bias, RNG_ ? nullptr : noise, (uint32_t)seed, (uint32_t)(seed >> 32),                        \
+                     RNG_ ? counter : nullptr, carry, wrap ? 1 : 0, out, harmonic_out, noise_out, (int)frames,     \
+                     (int)n_harmonic, (int)n_bands, bs, sample_rate, fs.lo_end, fs.tail_start, fs.pad)
+  if (noise) {
+    if (G > 1) DDSP_SYNTH_STREAM_LAUNCH(false, true);
+    else DDSP_SYNTH_STREAM_LAUNCH(false, false);
+  } else {
+    if (G > 1) DDSP_SYNTH_STREAM_LAUNCH(true, true);
+    else DDSP_SYNTH_STREAM_LAUNCH(true, false);
+  }
+#undef DDSP_SYNTH_STREAM_LAUNCH
+  return launch_status();
+}
+
+int ddsp_hip_stream_advance(const float* f0, uint64_t* counter, void* state, size_t state_bytes, int wrap,
+                            int64_t batch, int64_t frames, int64_t block_size, float sample_rate, void* stream) {
+  if (!counter || batch < 0 || frames < 0) return DDSP_HIP_EINVAL;
+  const bool phase = batch > 0 && frames > 0;  // else (a stream without synthesis) the counter alone
+  if (phase && (!f0 || !state || block_size < 1 || !(sample_rate > 0))) return DDSP_HIP_EINVAL;
+  if (batch > INT32_MAX || frames > INT32_MAX || block_size > INT32_MAX) return DDSP_HIP_ERANGE;
+  if (phase && state_bytes < (size_t)batch * sizeof(double)) return DDSP_HIP_EWORKSPACE;
+  hipLaunchKernelGGL(stream_advance_kernel, dim3(1), dim3(phase && batch > 64 ? 256 : 64), 0, S(stream), f0, counter,
+                     reinterpret_cast<double*>(state), wrap ? 1 : 0, phase ? (int)batch : 0, (int)frames,
+                     (int)block_size, sample_rate);
+  return launch_status();
 }
 
 }  // extern "C"

@@ -321,6 +321,86 @@ at::Tensor reverb_apply(const at::Tensor& x, const at::Tensor& spectrum, int64_t
   return out;
 }
 
+// ---------------- seamless realtime streaming (ddsp_hip_stream_*) ----------------
+// state: the stream's uint8 device buffer (ddsp_hip_stream_state_bytes), counter: its int64 call counter
+void check_stream(const at::Tensor& counter, const at::Tensor& state, const at::Tensor& like) {
+  TORCH_CHECK(state.is_cuda() && state.scalar_type() == at::kByte && state.is_contiguous() &&
+                  state.device() == like.device(),
+              "ddsp_hip: the stream state must be a contiguous uint8 tensor on the inputs' device");
+  TORCH_CHECK(counter.is_cuda() && counter.scalar_type() == at::kLong && counter.numel() >= 1 &&
+                  counter.device() == like.device(),
+              "ddsp_hip: the stream counter must be an int64 tensor on the inputs' device");
+}
+
+at::Tensor synth_frames_stream(const at::Tensor& f0, const at::Tensor& param, const at::Tensor& mags,
+                               int64_t block_size, double sample_rate, double bias,
+                               const std::optional<at::Tensor>& noise, int64_t seed, const at::Tensor& counter,
+                               at::Tensor& state, bool wrap) {
+  check_dev(f0, "f0");
+  check_dev(param, "param");
+  check_dev(mags, "mags");
+  check_stream(counter, state, f0);
+  TORCH_CHECK(param.dim() == 3 && mags.dim() == 3, "synth_frames_stream: param [B,F,H+1] and mags [B,F,NB] expected");
+  const int64_t B = param.size(0), F = param.size(1), H1 = param.size(2), NB = mags.size(2);
+  TORCH_CHECK(f0.sizes() == at::IntArrayRef({B, F, 1}) && mags.size(0) == B && mags.size(1) == F && H1 >= 2,
+              "synth_frames_stream: f0 [B,F,1], param [B,F,H+1], mags [B,F,NB] expected");
+  at::Tensor f = c16(f0), p = c16(param), m = c16(mags), n;
+  if (noise.has_value()) {
+    check_dev(*noise, "noise");
+    TORCH_CHECK(noise->sizes() == at::IntArrayRef({B, F, block_size}), "synth_frames_stream: noise must be [B,F,bs]");
+    n = c16(*noise);
+  }
+  at::Tensor out = at::empty({B, F * block_size, 1}, f.options());
+  ok(ddsp_hip_stream_synth_frames(f.data_ptr<float>(), p.data_ptr<float>(), m.data_ptr<float>(), (float)bias,
+                                  n.defined() ? n.data_ptr<float>() : nullptr, (uint64_t)seed,
+                                  reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
+                                  (size_t)state.numel(), wrap ? 1 : 0, out.data_ptr<float>(), nullptr, nullptr, B, F,
+                                  H1 - 1, NB, block_size, (float)sample_rate, stream_of(f)),
+     "stream_synth_frames");
+  return out;
+}
+
+at::Tensor stream_spectrum(const at::Tensor& impulse, int64_t call_samples) {
+  check_dev(impulse, "impulse");
+  at::Tensor h = c16(impulse.reshape({-1}));
+  const int64_t L = h.numel();
+  const size_t floats = ddsp_hip_stream_spectrum_floats(call_samples, L);
+  TORCH_CHECK(floats > 0, "stream_spectrum: call_samples must be a power of two in [64, 2048] and the IR non-empty");
+  at::Tensor spec = at::empty({(int64_t)floats}, h.options());
+  ok(ddsp_hip_stream_spectrum(h.data_ptr<float>(), L, call_samples, spec.data_ptr<float>(), floats, stream_of(h)),
+     "stream_spectrum");
+  return spec;
+}
+
+at::Tensor reverb_stream(const at::Tensor& x, const at::Tensor& spectrum, int64_t ir_length,
+                         const at::Tensor& counter, at::Tensor& state) {
+  check_dev(x, "x");
+  check_dev(spectrum, "spectrum");
+  check_stream(counter, state, x);
+  TORCH_CHECK(x.dim() >= 2 && spectrum.is_contiguous(), "reverb_stream: x [B,N] or [B,N,1], a contiguous spectrum");
+  const int64_t B = x.size(0), N = x.size(1);
+  TORCH_CHECK(x.numel() == B * N, "reverb_stream: x [B,N] or [B,N,1] expected");
+  at::Tensor xc = c16(x);
+  at::Tensor out = at::empty_like(xc);
+  ok(ddsp_hip_stream_reverb(xc.data_ptr<float>(), spectrum.data_ptr<float>(), (size_t)spectrum.numel(),
+                            reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
+                            (size_t)state.numel(), out.data_ptr<float>(), B, N, ir_length, stream_of(xc)),
+     "stream_reverb");
+  return out;
+}
+
+void stream_advance(const at::Tensor& f0, int64_t block_size, double sample_rate, at::Tensor& counter,
+                    at::Tensor& state, bool wrap) {
+  check_dev(f0, "f0");
+  check_stream(counter, state, f0);
+  TORCH_CHECK(f0.dim() == 3 && f0.size(2) == 1, "stream_advance: f0 [B,F,1] expected");
+  at::Tensor f = f0.contiguous();
+  ok(ddsp_hip_stream_advance(f.data_ptr<float>(), reinterpret_cast<uint64_t*>(counter.data_ptr<int64_t>()),
+                             state.data_ptr(), (size_t)state.numel(), wrap ? 1 : 0, f.size(0), f.size(1), block_size,
+                             (float)sample_rate, stream_of(f)),
+     "stream_advance");
+}
+
 }  // namespace
 
 // ---------------- decoder.py:33-68: the GRU recurrence ----------------
@@ -369,6 +449,12 @@ TORCH_LIBRARY(ddsp_hip, m) {
   m.def("reverb_build_impulse(Tensor noise, Tensor decay, Tensor wet, float sample_rate) -> Tensor");
   m.def("reverb_spectrum(Tensor impulse, int n_samples) -> Tensor");
   m.def("reverb_apply(Tensor x, Tensor spectrum, int ir_length) -> Tensor");
+  m.def("synth_frames_stream(Tensor f0, Tensor param, Tensor mags, int block_size, float sample_rate, float bias,"
+        " Tensor? noise, int seed, Tensor counter, Tensor(a!) state, bool wrap=True) -> Tensor");
+  m.def("stream_spectrum(Tensor impulse, int call_samples) -> Tensor");
+  m.def("reverb_stream(Tensor x, Tensor spectrum, int ir_length, Tensor counter, Tensor(a!) state) -> Tensor");
+  m.def("stream_advance(Tensor f0, int block_size, float sample_rate, Tensor(a!) counter, Tensor(b!) state,"
+        " bool wrap=True) -> ()");
   m.def("gru(Tensor x, Tensor w_ih, Tensor w_hh, Tensor b_ih, Tensor b_hh, Tensor? h0=None) -> (Tensor, Tensor)");
 }
 
@@ -388,5 +474,9 @@ TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA 
   m.impl("reverb_build_impulse", &reverb_build_impulse);
   m.impl("reverb_spectrum", &reverb_spectrum);
   m.impl("reverb_apply", &reverb_apply);
+  m.impl("synth_frames_stream", &synth_frames_stream);
+  m.impl("stream_spectrum", &stream_spectrum);
+  m.impl("reverb_stream", &reverb_stream);
+  m.impl("stream_advance", &stream_advance);
   m.impl("gru", &gru);
 }

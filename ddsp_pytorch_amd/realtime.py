@@ -17,6 +17,15 @@ the concatenations folded into its input — 7 launches + the GRU steps + the sy
 of ~30 torch kernels.  The on-device noise takes its
 Philox offset from a device counter the graph advances (`ddsp_hip_synth_frames_counter`), so
 every replay draws fresh noise; call k equals the eager model run with noise offset k.
+
+By default the synthesis is stateless across calls, as the reference's: every oscillator restarts at
+phase zero at each call boundary and there is no reverb.  ``continuous=True`` makes the stream
+seamless: the graph holds the streamed synthesis (`ddsp_hip_stream_synth_frames`), whose phase prefix
+continues from a per-stream carry in device memory, and the advance launch that replaces the counter
+advance also moves the carry (``wrap``: modulo 2 pi, so omega keeps its fp32 resolution for ever) —
+the same number of launches.  ``reverb=True`` adds the streamed reverb (`ddsp_hip_stream_reverb`, one
+more launch) with the model's reverb parameters and the impulse response at its full length, so K
+calls of N samples are the K N samples the offline model renders.
 """
 from collections import namedtuple
 
@@ -35,10 +44,17 @@ class RealtimeGraph:
     The model's `decoder.cache_gru` is the stream state (updated in place by every call, as in
     decoder.py:56-60); `reset()` zeroes it and rewinds the noise counter.  The returned tensor
     is a static buffer overwritten by the next call (the host copies it out, as `ddsp~` does
-    with memcpy)."""
+    with memcpy).
+
+    ``continuous=True``: the oscillator phase carries over from call to call (``wrap``, default True
+    then: the carry is kept modulo 2 pi).  ``reverb=True`` (needs ``continuous`` and a power-of-two
+    ``call_samples`` in [64, 2048]): the model's reverb runs in the stream with its full impulse
+    response, built at construction (`refresh()` rebuilds it after the parameters change).  The
+    stream's device state is `self.stream` (core.StreamState); `reset()` zeroes it too."""
 
     def __init__(self, model, call_samples=1024, mean_loudness=0.0, std_loudness=1.0,
-                 seed=0x5EEDDD5B, device=None, warmup=3, fused=True, gru_route="steps"):
+                 seed=0x5EEDDD5B, device=None, warmup=3, fused=True, gru_route="steps",
+                 continuous=False, reverb=False, wrap=None):
         device = torch.device(device) if device is not None else next(model.parameters()).device
         if device.type != "cuda":
             raise RuntimeError("RealtimeGraph: the model must be on a HIP device")
@@ -62,6 +78,21 @@ class RealtimeGraph:
         self._inp = torch.zeros(2, N, 1, device=device)
         self.pitch, self.loudness = self._inp[0:1], self._inp[1:2]
         self.counter = torch.zeros(1, dtype=torch.int64, device=device)
+        self.continuous = bool(continuous)
+        self.reverb = bool(reverb)
+        self.wrap = self.continuous if wrap is None else bool(wrap)
+        self.stream = None
+        if self.reverb and not self.continuous:
+            raise RuntimeError("RealtimeGraph: reverb=True needs continuous=True (the streamed reverb)")
+        if self.wrap and not self.continuous:
+            raise RuntimeError("RealtimeGraph: wrap applies to the phase carry of continuous=True")
+        if self.continuous:
+            L = int(model.reverb.length) if self.reverb else 0
+            self.stream = core.StreamState(1, device, N, L)  # raises on a call size the reverb cannot take
+            self.counter = self.stream.counter
+            if self.reverb:
+                self._spec = torch.empty(int(core._lib.query("stream_spectrum_floats", N, L)), device=device)
+                self.refresh()
         self._inp_h = torch.zeros(2, N, 1).pin_memory()
         self._out_h = torch.zeros(1, N, 1).pin_memory()
         self.fused = bool(fused)
@@ -84,6 +115,31 @@ class RealtimeGraph:
         torch.cuda.synchronize(device)
         model.decoder.cache_gru.copy_(cache0)
         self.counter.zero_()
+        if self.stream is not None:
+            self.stream.reset()
+
+    def refresh(self):
+        """Rebuild the streamed reverb's IR spectra from the model's reverb parameters (in place: the
+        captured graph reads the same buffer)."""
+        if not self.reverb:
+            raise RuntimeError("RealtimeGraph.refresh: the stream has no reverb")
+        rv = self.model.reverb
+        with torch.no_grad():
+            imp = core.reverb_build_impulse(rv.noise.detach(), rv.decay.detach(), rv.wet.detach(), rv.sample_rate)
+            self._spec.copy_(core.stream_spectrum(imp, self.call_samples))
+
+    def _synthesis(self, f0, param, mags):
+        """The call's synthesis: stateless (the counter-keyed fused kernel), or the stream's."""
+        bs = self.block_size
+        if not self.continuous:
+            return core.synth_frames_counter(f0, param, mags, bs, self.sample_rate, self.counter, self.seed,
+                                             bias=self.bias)
+        out = core.stream_synth_frames(f0, param, mags, bs, self.sample_rate, self.stream, self.seed,
+                                       bias=self.bias, wrap=self.wrap)
+        if self.reverb:
+            out = core.stream_reverb(out, self._spec, self.stream)
+        core.stream_advance(self.stream, f0, bs, self.sample_rate, wrap=self.wrap)
+        return out
 
     def _setup_fused(self):
         m, dev = self.model, self.device
@@ -144,9 +200,7 @@ class RealtimeGraph:
         core.dense_rows([([di(b["y5"], norm=om[4])], om[6], b["y6"])], R, dev)
         core.dense_rows([([di(b["y6"], norm=om[7])], m.harmonic_proj, b["param"]),
                          ([di(b["y6"], norm=om[7])], m.noise_proj, b["mags"])], R, dev)
-        return core.synth_frames_counter(b["f0"].view(1, R, 1), b["param"].view(1, R, -1),
-                                         b["mags"].view(1, R, -1), bs, self.sample_rate, self.counter,
-                                         self.seed, bias=self.bias)
+        return self._synthesis(b["f0"].view(1, R, 1), b["param"].view(1, R, -1), b["mags"].view(1, R, -1))
 
     def _forward(self):
         """export.py:33-40 realtime ScriptDDSP.forward with the model's synthesis fused."""
@@ -158,12 +212,13 @@ class RealtimeGraph:
         hidden = gru_decoder_forward(m.decoder, pitch, loudness, None, realtime=True)
         param = m.harmonic_proj(hidden)
         mags = m.noise_proj(hidden)
-        return core.synth_frames_counter(pitch, param, mags, bs, self.sample_rate, self.counter,
-                                         self.seed, bias=self.bias)
+        return self._synthesis(pitch.contiguous(), param, mags)
 
     def reset(self):
         self.model.decoder.cache_gru.zero_()
         self.counter.zero_()
+        if self.stream is not None:
+            self.stream.reset()
 
     @torch.no_grad()
     def __call__(self, pitch, loudness):

@@ -522,6 +522,50 @@ int ddsp_hip_reverb_impulse_backward(const float* noise, const float* decay, con
                                      float sample_rate, float* grad_noise, float* grad_decay, float* grad_wet,
                                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------- seamless realtime streaming ----------------
+ * K calls of N samples that render what one call of K N samples renders (no reference counterpart: the
+ * reference's realtime model restarts every oscillator at phase zero on each call and has no reverb,
+ * decoder.py:138-158, export.py:37-40).  The stream's state is ONE caller-allocated device buffer of
+ * ddsp_hip_stream_state_bytes(batch, call_samples, ir_length) bytes, 16-byte aligned, zero-filled for a fresh
+ * stream: double carry[batch] (the running phase prefix per item) at offset 0, then, with ir_length > 0, the
+ * reverb's previous input block and its ring of P = ceil(ir_length / call_samples) block spectra per item
+ * (ir_length 0: the carry alone, any call_samples).  The call counter is a device word of the caller's
+ * (zero for a fresh stream): it is the Philox offset of the on-device noise and, modulo P, the reverb's ring
+ * slot, so a captured HIP graph replays with no by-value state.  One call of the stream is
+ *   ddsp_hip_stream_synth_frames -> [ddsp_hip_stream_reverb] -> ddsp_hip_stream_advance
+ * on one HIP stream: the first two only read the counter and the carry, the advance moves both. */
+size_t ddsp_hip_stream_state_bytes(int64_t batch, int64_t call_samples, int64_t ir_length);
+/* floats of the stream reverb's IR partition spectra (P x (call_samples + 1) complex bins); 0 outside the
+ * reverb's range (call_samples a power of two in [64, 2048], ir_length >= 1) */
+size_t ddsp_hip_stream_spectrum_floats(int64_t call_samples, int64_t ir_length);
+/* The IR partition spectra of impulse[ir_length] (Reverb.build_impulse at full length, modules.py:21-26) for
+ * calls of call_samples: shared by all items, built once per IR.  DDSP_HIP_ERANGE outside the range above,
+ * DDSP_HIP_EWORKSPACE when spectrum_floats is short. */
+int ddsp_hip_stream_spectrum(const float* impulse, int64_t ir_length, int64_t call_samples, float* spectrum,
+                             size_t spectrum_floats, void* stream);
+/* ddsp_hip_synth_frames for one call of a stream: frame f uses the phase prefix carry[b] + sum_{g<f} bs inc_g in
+ * fp64 (wrap != 0: the carry reduced modulo 2 pi first).  noise [B,F,bs] injected, or NULL: on-device Philox
+ * with (seed, offset = *counter).  Envelope and DDSP_HIP_ERANGE as ddsp_hip_synth_frames; DDSP_HIP_EWORKSPACE
+ * when state_bytes is short.  Reads state and counter only. */
+int ddsp_hip_stream_synth_frames(const float* f0, const float* param, const float* raw_magnitudes, float bias,
+                                 const float* noise, uint64_t seed, const uint64_t* counter, const void* state,
+                                 size_t state_bytes, int wrap, float* out, float* harmonic_out, float* noise_out,
+                                 int64_t batch, int64_t frames, int64_t n_harmonic, int64_t n_bands,
+                                 int64_t block_size, float sample_rate, void* stream);
+/* One call of the stream's reverb: y[B, N] such that the calls' outputs laid end to end are the causal
+ * convolution (x_all * impulse)[0 : K N] with the impulse at its full length (modules.py:28-35 without the
+ * crop to the input's length).  One launch, one workgroup per item; y may be x.  call_samples a power of two
+ * in [64, 2048] (else DDSP_HIP_ERANGE); DDSP_HIP_EWORKSPACE when state_bytes or spectrum_floats is short.
+ * Writes the item's history and ring slot *counter mod P; reads the counter. */
+int ddsp_hip_stream_reverb(const float* x, const float* spectrum, size_t spectrum_floats, const uint64_t* counter,
+                           void* state, size_t state_bytes, float* y, int64_t batch, int64_t call_samples,
+                           int64_t ir_length, void* stream);
+/* The end of a call, one one-workgroup launch: carry[b] += sum_g bs inc_g over the call's frames f0[B, F]
+ * (wrap != 0: then reduced modulo 2 pi in fp64 — sin(k omega) is unchanged for the integer harmonic numbers k
+ * and omega keeps its fp32 resolution for ever) and *counter += 1.  batch or frames 0: the counter alone. */
+int ddsp_hip_stream_advance(const float* f0, uint64_t* counter, void* state, size_t state_bytes, int wrap,
+                            int64_t batch, int64_t frames, int64_t block_size, float sample_rate, void* stream);
+
 /* Two-stage serving pipeline (ddsp_pytorch_amd.synth.PipelinedSynthPath; no reference counterpart:
  * the reference synthesises one batch at a time, decoder.py:101-136).  A HIP stream restricted to
  * the CUs whose bits are set in cu_mask (mask_words 32-bit words, bit c = CU index c; HIP deals

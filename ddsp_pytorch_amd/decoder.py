@@ -200,16 +200,21 @@ def decoder_projections(self, hidden):
     the fused synthesis kernel reads with its row stride.  Under autograd the concatenated weights keep the call
     differentiable, so the parameters receive their gradients as the reference's do: at 512 inputs
     grad.ProjectionsFn (the forward on ddsp_hip_projections, the weight gradient on ddsp_hip_linear_weight_grad),
-    elsewhere grad.LinearFn over the concatenated parameters."""
+    elsewhere grad.LinearFn over the concatenated parameters.  Both are fp32 kernels: for any other dtype of
+    the input or the parameters, and inside an autocast region, the two module calls run (_fp32_inference_ok),
+    with or without autograd."""
     hp, npj = self.harmonic_proj, self.noise_proj
     if not hidden.is_cuda or hp.bias is None or npj.bias is None or _hooked(hp) or _hooked(npj):
         return hp(hidden), npj(hidden)  # (module hooks see the calls the reference makes)
     ps = (hp.weight, hp.bias, npj.weight, npj.bias)
     h1, n = hp.out_features, hp.out_features + npj.out_features
     if torch.is_grad_enabled() and (hidden.requires_grad or any(p.requires_grad for p in ps)):
+        if not _fp32_inference_ok(hidden, (hp, npj)):
+            # other dtypes and autocast regions: torch's Linears, in their dtype, with their autograd
+            return hp(hidden), npj(hidden)
         from .grad import LinearFn, ProjectionsFn
-        if hidden.shape[-1] == 512 and all(p.dtype == torch.float32 and p.dim() and p.stride(-1) == 1 for p in ps) \
-                and hidden.dtype == torch.float32 and hp.in_features == npj.in_features == 512:
+        if hidden.shape[-1] == 512 and all(p.dim() and p.stride(-1) == 1 for p in ps) \
+                and hp.in_features == npj.in_features == 512:
             out = ProjectionsFn.apply(hidden, hp.weight, hp.bias, npj.weight, npj.bias)
         else:
             w, b = torch.cat([hp.weight, npj.weight]), torch.cat([hp.bias, npj.bias])  # differentiable

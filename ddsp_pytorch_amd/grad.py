@@ -10,8 +10,15 @@ Pitch (f0) is an input feature in the reference's training loop (``batch['pitch'
 train.py:84-99): no gradient flows to it.  ``remove_above_nyquist`` gives f0 the zero
 gradient the reference's comparison gives; the oscillator ops refuse an f0 that
 requires grad rather than silently returning a wrong (zero) gradient.
+
+First order only: every ``backward`` is ``once_differentiable`` (the vector-Jacobian kernels write
+into fresh buffers that autograd cannot see through), so a double backward (``create_graph=True``,
+e.g. a gradient penalty) raises instead of returning a silently truncated second-order gradient.
+Whatever a backward needs from its forward is a saved tensor, which lives as long as the graph:
+``backward(retain_graph=True)`` may run any number of times.
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import core
@@ -46,6 +53,7 @@ class ScaleFn(_F):
         return core.scale_with_bias(x, bias)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         (x,) = ctx.saved_tensors
         x, g = core._c(x), _g(g)
@@ -66,6 +74,7 @@ class NyquistFn(_F):
         return core.remove_above_nyquist(amplitudes, f0, sample_rate)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         (f0,) = ctx.saved_tensors
         d = core.remove_above_nyquist(g, f0.detach(), ctx.sr)
@@ -84,6 +93,7 @@ class UpsampleFn(_F):
         return core.upsample(signal, factor)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         B, F, C = ctx.shape
         g = _g(g)
@@ -103,6 +113,7 @@ class HarmonicSynthFn(_F):
         return core.harmonic_synth(f0, amplitudes, sample_rate)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         (f0,) = ctx.saved_tensors
         B, T = f0.shape[0], f0.shape[1]
@@ -124,6 +135,7 @@ class ImpulseResponseFn(_F):
         return core.amp_to_impulse_response(amp, target_size)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         NB = ctx.shape[-1]
         g = _g(g)
@@ -144,6 +156,7 @@ class FFTConvolveFn(_F):
         return core.fft_convolve(signal, kernel)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         s, k = ctx.saved_tensors
         gr = torch.flip(g, (-1,))
@@ -166,6 +179,7 @@ class ControlsFn(_F):
         return core.harmonic_controls(amplitudes, distribution, f0, sample_rate)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_amp, g_dist):
         a, d, f0 = ctx.saved_tensors
         B, F, H = d.shape
@@ -196,6 +210,7 @@ class SynthFramesHarmonicFn(_F):
                                           write_back=False)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         B, F, H = ctx.dist.shape
         g = _g(g)
@@ -235,6 +250,7 @@ class HarmonicParamsFn(_F):
         return core.harmonic_synth_params(f0, param, block_size, sample_rate)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         f0, param = ctx.saved_tensors
         return None, params_backward(f0.detach(), param.detach(), _g(g), ctx.bs, ctx.sr), None, None
@@ -258,6 +274,7 @@ class FilteredNoiseFn(_F):
         return outs
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_out, g_nout=None):
         g = g_out if (g_nout is None) else (g_nout if g_out is None else g_out + g_nout)
         g_f = _g(g)
@@ -280,6 +297,7 @@ class SynthFramesFn(_F):
         return outs
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_out, g_harm=None, g_nz=None):
         f0, param, mags = ctx.saved_tensors
         gh = _g(g_out if g_harm is None else g_out + g_harm)
@@ -348,6 +366,7 @@ class ReverbApplyFn(_F):
         return core.reverb_apply(x, spectrum, ir_length)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         dx, _ = reverb_backward(None, None, ctx.spectrum, _g(g), ctx.L, True, False)
         return dx, None, None
@@ -361,8 +380,9 @@ class ReverbFn(_F):
     @staticmethod
     def forward(ctx, x, noise, decay, wet, run, ir_length, sample_rate):
         out, ws, spectrum = run(x)  # modules.Reverb._forward_cached: (out, workspace, spectrum of the cache)
-        ctx.save_for_backward(noise, decay, wet)
-        ctx.ws = ws if any(ctx.needs_input_grad[1:4]) else None
+        # the workspace holds x's partition spectra, a saved activation: kept (when a parameter needs its
+        # gradient) with the saved tensors, so it lives exactly as long as the graph does
+        ctx.save_for_backward(noise, decay, wet, ws if any(ctx.needs_input_grad[1:4]) else None)
         # a view of the module's cache, rebuilt in place by a later forward only if noise / decay / wet
         # have changed by then.  In-place changes through autograd-visible ops are refused at backward
         # (they are saved tensors, version-checked); a write through .data between this forward and its
@@ -375,16 +395,16 @@ class ReverbFn(_F):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
-        noise, decay, wet = ctx.saved_tensors
+        noise, decay, wet, ws = ctx.saved_tensors
         want_p = any(ctx.needs_input_grad[1:4])
         dn = dd = dw = None
         if want_p:  # the impulse gradient never materialised (ddsp_hip_reverb_backward_params)
-            dx, dn, dd, dw = reverb_backward_params(ctx.ws, ctx.spectrum, _g(g), noise.detach(), decay.detach(),
+            dx, dn, dd, dw = reverb_backward_params(ws, ctx.spectrum, _g(g), noise.detach(), decay.detach(),
                                                     wet.detach(), ctx.L, ctx.sr, ctx.needs_input_grad[0])
         else:
             dx, _ = reverb_backward(None, None, ctx.spectrum, _g(g), ctx.L, True, False)
-        ctx.ws = None
         return dx, dn, dd, dw, None, None, None
 
 
@@ -398,6 +418,7 @@ class BuildImpulseFn(_F):
         return core.reverb_build_impulse(noise, decay, wet, sample_rate)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         noise, decay, wet = ctx.saved_tensors
         g = _g(g).reshape(-1)
@@ -417,6 +438,7 @@ class StftMagFn(_F):
         return core.stft_magnitude(signal, n_fft, hop)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         (x,) = ctx.saved_tensors
         B, T = x.shape
@@ -449,6 +471,7 @@ class LinearFn(_F):
         return y.view(*x.shape[:-1], weight.shape[0])
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gy):
         x2, w = ctx.saved_tensors
         g2 = _g(gy).reshape(-1, w.shape[0])
@@ -488,6 +511,7 @@ class ProjectionsFn(_F):
         return y.view(*x.shape[:-1], n4)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gy):
         x2, w1, w2 = ctx.saved_tensors
         n1, n2 = w1.shape[0], w2.shape[0]
@@ -524,6 +548,7 @@ class LNLeakyFn(_F):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gy):
         gc, gamma, beta = ctx.saved_tensors
         cols = gc.shape[-1]
@@ -560,6 +585,7 @@ class GRUFn(_F):
         return out, h_last
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_out, g_hlast):
         x, w_ih, w_hh, out, gates, h0c = ctx.saved_tensors
         B, T, I = x.shape

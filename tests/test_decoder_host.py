@@ -44,6 +44,30 @@ def test_fp32_inference_guard():
         assert not _fp32_inference_ok(x, (lin,))
 
 
+def test_projections_cpu_autocast_with_grad_are_the_modules():
+    """decoder_projections on the CPU (the module route's early return) under autocast with autograd: the
+    outputs and all five gradients are those of harmonic_proj(hidden) and noise_proj(hidden), bit for bit."""
+    torch.manual_seed(1)
+    m = dd.DDSPDecoder(32, 10, 9, 48000, 64, False)
+    ps = [m.harmonic_proj.weight, m.harmonic_proj.bias, m.noise_proj.weight, m.noise_proj.bias]
+    h0 = torch.randn(2, 3, 32)
+
+    def run(fn):
+        h = h0.clone().requires_grad_(True)
+        for p in ps:
+            p.grad = None
+        with torch.autocast("cpu", dtype=torch.bfloat16):
+            a, b = fn(h)
+            (a.float().pow(2).sum() + b.float().sum()).backward()
+        return [a, b, h.grad] + [p.grad.clone() for p in ps]
+
+    ref = run(lambda h: (m.harmonic_proj(h), m.noise_proj(h)))
+    got = run(lambda h: dd.decoder.decoder_projections(m, h))
+    assert got[0].dtype == ref[0].dtype == torch.bfloat16 and got[1].dtype == torch.bfloat16
+    for g, r in zip(got, ref):
+        assert g.dtype == r.dtype and torch.equal(g, r)
+
+
 def test_synth_overridden():
     m = dd.DDSPDecoder(32, 10, 9, 48000, 64, False)
     hs, ns = m.harmonic_synth, m.noise_synth

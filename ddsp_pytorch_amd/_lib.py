@@ -61,8 +61,7 @@ SIGNATURES = {
     "ddsp_hip_filtered_noise_params": (_I, [_P, _F, _P, _U64, _U64, _P, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "ddsp_hip_synth_frames": (_I, [_P, _P, _P, _F, _P, _U64, _U64, _P, _P, _P, _I64, _I64, _I64, _I64,
                                    _I64, _F, _P]),
-    "ddsp_hip_synth_frames_controls": (_I, [_P, _P, _I64, _P, _I64, _F, _P, _U64, _U64, _P, _P, _P, _P, _I64,
-                                            _I64, _I64, _I64, _I64, _F, _P]),
+    "ddsp_hip_synth_frames_supported": (_I, [_I64, _I64, _I64, _I64]),
     "ddsp_hip_synth_frames_controls_prefix": (_I, [_P, _P, _I64, _P, _I64, _F, _P, _U64, _U64, _P, _P, _P, _P, _P,
                                                    _I64, _I64, _I64, _I64, _I64, _F, _P]),
     "ddsp_hip_frame_phase_prefix": (_I, [_P, _I64, _I64, _I64, _F, _P, _P]),
@@ -159,17 +158,21 @@ def load():
 ERANGE = 5  # DDSP_HIP_ERANGE
 
 
+def _entry(name):
+    fn = getattr(load(), "ddsp_hip_" + name, None)
+    if fn is None:
+        raise RuntimeError(f"ddsp_hip: entry point ddsp_hip_{name} is missing from {LIB_PATH}")
+    return fn
+
+
 def call(name, *args, allow=()):
     """Invoke ddsp_hip_<name>; map a non-zero status (other than those in `allow`) to RuntimeError.
     An A/B build of an older revision (DDSP_HIP_LIB) that lacks an entry point whose caller has a
     fallback (ERANGE allowed) answers ERANGE, so that the caller's fallback runs."""
     lib = load()
-    fn = getattr(lib, "ddsp_hip_" + name, None)
-    if fn is None:
-        if ERANGE in allow and "DDSP_HIP_LIB" in os.environ:
-            return ERANGE
-        raise RuntimeError(f"ddsp_hip: entry point ddsp_hip_{name} is missing from {LIB_PATH}")
-    st = fn(*args)
+    if ERANGE in allow and "DDSP_HIP_LIB" in os.environ and not hasattr(lib, "ddsp_hip_" + name):
+        return ERANGE
+    st = _entry(name)(*args)
     if st in allow:
         return st
     if st != 0:
@@ -179,7 +182,8 @@ def call(name, *args, allow=()):
 
 
 def query(name, *args):
-    return getattr(load(), "ddsp_hip_" + name)(*args)
+    """The value of ddsp_hip_<name>, an entry point that returns a size or an answer, not a status."""
+    return _entry(name)(*args)
 
 
 def stream_of(t):

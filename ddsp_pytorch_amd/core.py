@@ -25,7 +25,7 @@ from . import _lib
 __all__ = [
     "scale_function", "remove_above_nyquist", "upsample", "harmonic_synth",
     "amp_to_impulse_response", "fft_convolve", "phase", "harmonic_controls",
-    "harmonic_synth_frames", "harmonic_synth_params", "synth_frames", "filtered_noise", "reverb_build_impulse", "reverb_spectrum_floats",
+    "harmonic_synth_frames", "harmonic_synth_params", "synth_frames", "synth_signal", "filtered_noise", "reverb_build_impulse", "reverb_spectrum_floats",
     "reverb_spectrum", "reverb_impulse_spectrum", "reverb_apply", "reverb_forward", "reverb_cache_bytes", "set_noise_seed", "safe_log", "stft_magnitude", "multiscale_fft",
 ]
 
@@ -192,11 +192,16 @@ def fft_convolve(signal, kernel):
 # ------------------------------------------------------------------------------------
 # fused module-level ops (ddsp/models/modules.py)
 # ------------------------------------------------------------------------------------
-def _rows_view(t, name):
-    """[B, F, C] view with unit stride on C and a single row stride over (B, F)."""
-    if t.dim() != 3 or t.stride(-1) != 1 or t.stride(0) != t.shape[1] * t.stride(1):
-        t = t.contiguous()
-    return t, t.stride(1)
+def _frame_rows(t):
+    """(tensor, row stride) for a [B, F, C] tensor read row by row: unit stride on C and one row stride
+    over (B, F) — a column slice of a wider projection output qualifies as it is — else a contiguous copy
+    (broadcast rows, stride 0, and overlapping rows included).  The kernels read these rows with scalar
+    loads only (no 16-byte vector loads), so a view's row base needs no more than 4-byte alignment."""
+    if (t.dim() == 3 and t.stride(-1) == 1 and t.stride(1) >= max(t.shape[-1], 1)
+            and t.stride(0) == t.shape[1] * t.stride(1)):
+        return t, t.stride(1)
+    t = t.contiguous()
+    return t, t.shape[-1]
 
 
 def harmonic_controls(amplitudes, harmonic_distribution, f0, sample_rate):
@@ -209,8 +214,7 @@ def harmonic_controls(amplitudes, harmonic_distribution, f0, sample_rate):
     if amplitudes.shape != (B, F, 1) or f0.shape != (B, F, 1):
         raise RuntimeError("harmonic_controls: expected amplitudes/f0 [B,F,1] matching "
                            f"distribution {tuple(harmonic_distribution.shape)}")
-    a, a_ld = _rows_view(amplitudes, "amplitudes")
-    d, d_ld = _rows_view(harmonic_distribution, "harmonic_distribution")
+    (a, a_ld), (d, d_ld) = _frame_rows(amplitudes), _frame_rows(harmonic_distribution)
     f0c = _c(f0)
     amp_out = torch.empty(B, F, 1, dtype=torch.float32, device=f0.device)
     dist_out = torch.empty(B, F, H, dtype=torch.float32, device=f0.device)
@@ -342,26 +346,29 @@ EWORKSPACE = 4  # DDSP_HIP_EWORKSPACE
 # the fused synthesis kernel's frames sum their phase prefix themselves up to this many frames per item
 # (O(F) per frame); past it one ddsp_hip_frame_phase_prefix launch precomputes every frame's prefix
 FRAME_PREFIX_MIN_FRAMES = 512
-ERANGE = 5
+ERANGE = _lib.ERANGE
 
 
 def synth_frames_in_envelope(n_harmonic, n_bands, block_size, batch=1):
-    """The fused kernel's shape envelope (mirrors ddsp_hip_synth_frames' DDSP_HIP_ERANGE checks)."""
-    H, NB, bs = int(n_harmonic), int(n_bands), int(block_size)
-    if bs % 4 or bs > 1024 or H > 1024 or NB > 1025 or batch > 65535:
-        return False
-    n = 2 * (NB - 1)
-    half = n // 2
-    if bs >= n:
-        lo_end, tail_start = (half + 3) & ~3, bs - half
-        if tail_start < lo_end:
-            lo_end = bs
-    else:
-        lo_end = bs
-    pad = (lo_end + 4 + 3) & ~3
-    H4, n4 = (H + 3) & ~3, (n + 3) & ~3
-    floats = 8 * H4 + n4 + ((NB + 3) & ~3) + ((half + 4) & ~3) + bs + ((half + 3) & ~3) + pad + bs
-    return 4 * floats <= 120 * 1024
+    """The fused kernel's shape envelope, as the library decides it (ddsp_hip_synth_frames_supported)."""
+    return bool(_lib.query("synth_frames_supported", int(batch), int(n_harmonic), int(n_bands), int(block_size)))
+
+
+def _frame_args(f0, param, mags, noise, block_size, name):
+    """The frame arguments every fused-synthesis entry takes, checked: f0 [B,F,1], param [B,F,H+1], mags
+    [B,F,NB] and, where given, noise [B,F,bs] -> (B, F, H, NB, bs, noise contiguous or None)."""
+    _dev(f0, param, mags)
+    B, F, H1 = param.shape
+    NB = mags.shape[-1]
+    bs = int(block_size)
+    if f0.shape != (B, F, 1) or mags.shape[:2] != (B, F) or H1 < 2:
+        raise RuntimeError(f"{name}: f0 [B,F,1], param [B,F,H+1], mags [B,F,NB] expected")
+    if noise is not None:
+        _dev(noise)
+        if tuple(noise.shape) != (B, F, bs):
+            raise RuntimeError(f"{name}: noise must be [B, F, block_size] = {(B, F, bs)}")
+        noise = _c(noise)
+    return B, F, H1 - 1, NB, bs, noise
 
 
 def synth_frames(f0, param, mags, block_size, sample_rate, bias=-5.0, noise=None, parts=False, controls=False):
@@ -375,14 +382,9 @@ def synth_frames(f0, param, mags, block_size, sample_rate, bias=-5.0, noise=None
     distribution as the reference's caller sees it after ``modules.py:73``'s in-place
     ``*= amplitudes``; written by the same launch (or, under autograd, by the differentiable
     control ops).  Returns None when the shape is outside the fused kernel's envelope
-    (block_size % 4 == 0 and <= 1024, H <= 1024, NB <= 1025)."""
-    _dev(f0, param, mags)
-    B, F, H1 = param.shape
-    NB = mags.shape[-1]
-    bs = int(block_size)
-    if f0.shape != (B, F, 1) or mags.shape[:2] != (B, F) or H1 < 2:
-        raise RuntimeError("synth_frames: f0 [B,F,1], param [B,F,H+1], mags [B,F,NB] expected")
-    if not synth_frames_in_envelope(H1 - 1, NB, bs, B):
+    (``synth_frames_in_envelope``); ``synth_signal`` runs the two module kernels there."""
+    B, F, H, NB, bs, noise = _frame_args(f0, param, mags, noise, block_size, "synth_frames")
+    if not synth_frames_in_envelope(H, NB, bs, B):
         return None
     if _wants_grad(f0, param, mags):
         _grad.refuse_f0_grad(f0, "synth_frames")
@@ -398,35 +400,25 @@ def synth_frames(f0, param, mags, block_size, sample_rate, bias=-5.0, noise=None
     return _synth_frames_launch(f0, param, mags, bs, sample_rate, bias, noise, parts, seed, offset, controls)
 
 
-def _frame_rows(t):
-    """(tensor, row stride) for a [B, F, C] tensor read row by row: unit stride on C and one row stride
-    over (B, F) — a column slice of a wider projection output qualifies as it is — else a contiguous copy
-    (broadcast rows, stride 0, and overlapping rows included).  The kernels read these rows with scalar
-    loads only (no 16-byte vector loads), so a view's row base needs no more than 4-byte alignment."""
-    if (t.dim() == 3 and t.stride(-1) == 1 and t.stride(1) >= max(t.shape[-1], 1)
-            and t.stride(0) == t.shape[1] * t.stride(1)):
-        return t, t.stride(1)
-    t = t.contiguous()
-    return t, t.shape[-1]
+def synth_signal(f0, param, mags, block_size, sample_rate, bias=-5.0, noise=None):
+    """The signal of ``synth_frames`` for any shape: on the fused kernel, or outside its envelope on the two
+    module kernels (the harmonic signal, then the filtered noise adding it)."""
+    signal = synth_frames(f0, param, mags, block_size, sample_rate, bias=bias, noise=noise)
+    if signal is None:
+        harmonic = harmonic_synth_params(f0, param, block_size, sample_rate)
+        signal = filtered_noise(mags, block_size, noise=noise, add=harmonic, raw_bias=bias)
+    return signal
 
 
 def _synth_frames_launch(f0, param, mags, block_size, sample_rate, bias, noise, parts, seed, offset,
                          controls=False):
-    B, F, H1 = param.shape
-    NB = mags.shape[-1]
-    bs = int(block_size)
+    B, F, H, NB, bs, noise = _frame_args(f0, param, mags, noise, block_size, "synth_frames")
     f0c = _c(f0)
     (pc, ldp), (mc, ldm) = _frame_rows(param), _frame_rows(mags)
-    if noise is not None:
-        _dev(noise)
-        if tuple(noise.shape) != (B, F, bs):
-            raise RuntimeError(f"synth_frames: noise must be [B, F, block_size] = {(B, F, bs)}")
-        noise = _c(noise)
     out = torch.empty(B, F * bs, 1, dtype=torch.float32, device=f0.device)
     harm = torch.empty_like(out) if parts else None
     nz = torch.empty_like(out) if parts else None
-    ctrl = (torch.empty(B * F * (1 + (H1 - 1) + NB), dtype=torch.float32, device=f0.device)
-            if controls else None)
+    ctrl = torch.empty(B * F * (1 + H + NB), dtype=torch.float32, device=f0.device) if controls else None
     prefix = None
     if F > FRAME_PREFIX_MIN_FRAMES:  # long renders: each frame reads its phase prefix instead of summing
         prefix = torch.empty(B * F, dtype=torch.float64, device=f0.device)
@@ -434,11 +426,11 @@ def _synth_frames_launch(f0, param, mags, block_size, sample_rate, bias, noise, 
                   _lib.stream_of(out))
     _lib.call("synth_frames_controls_prefix", _lib.ptr(f0c), _lib.ptr(pc), ldp, _lib.ptr(mc), ldm, float(bias),
               _lib.ptr(noise), seed, offset, _lib.ptr(out), _lib.ptr(harm), _lib.ptr(nz), _lib.ptr(ctrl),
-              _lib.ptr(prefix), B, F, H1 - 1, NB, bs, float(sample_rate), _lib.stream_of(out))
+              _lib.ptr(prefix), B, F, H, NB, bs, float(sample_rate), _lib.stream_of(out))
     res = (out, harm, nz) if parts else out
     if not controls:
         return res
-    BF, H = B * F, H1 - 1
+    BF = B * F
     cd = {"amplitudes": ctrl[:BF].view(B, F, 1), "harmonic_distribution": ctrl[BF:BF * (1 + H)].view(B, F, H),
           "magnitudes": ctrl[BF * (1 + H):].view(B, F, NB)}
     return (*res, cd) if parts else (res, cd)
@@ -449,19 +441,14 @@ def synth_frames_counter(f0, param, mags, block_size, sample_rate, counter, seed
     (int64, advanced by one on the stream after the launch): for calls replayed from a captured
     HIP graph, where by-value offsets would freeze.  Call k equals
     synth_frames(..., noise=None) drawn with (seed, offset=k).  Inference only."""
-    _dev(f0, param, mags)
-    B, F, H1 = param.shape
-    NB = mags.shape[-1]
-    bs = int(block_size)
-    if f0.shape != (B, F, 1) or mags.shape[:2] != (B, F) or H1 < 2:
-        raise RuntimeError("synth_frames_counter: f0 [B,F,1], param [B,F,H+1], mags [B,F,NB] expected")
+    B, F, H, NB, bs, _ = _frame_args(f0, param, mags, None, block_size, "synth_frames_counter")
     if counter.dtype != torch.int64 or counter.numel() < 1 or counter.device != f0.device:
         raise RuntimeError("synth_frames_counter: counter must be a device int64 tensor")
-    if not synth_frames_in_envelope(H1 - 1, NB, bs, B):
+    if not synth_frames_in_envelope(H, NB, bs, B):
         raise RuntimeError("synth_frames_counter: shape outside the fused kernel's envelope")
     out = torch.empty(B, F * bs, 1, dtype=torch.float32, device=f0.device)
     _lib.call("synth_frames_counter", _lib.ptr(_c(f0)), _lib.ptr(_c(param)), _lib.ptr(_c(mags)), float(bias),
-              int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(counter), _lib.ptr(out), B, F, H1 - 1, NB, bs,
+              int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(counter), _lib.ptr(out), B, F, H, NB, bs,
               float(sample_rate), _lib.stream_of(out))
     return out
 
@@ -658,6 +645,13 @@ def linear_weight_grad(grad_y, x):
 MLP_EXACT_F32 = 1  # include/ddsp_hip.h DDSP_HIP_MLP_EXACT_F32
 
 
+def _row_strided(out, shape):
+    """``out`` has ``shape`` [..., cols] with unit stride on cols and one row stride over the leading
+    dims (row r at r * out.stride(-2)): a column slice of a wider contiguous buffer qualifies."""
+    return (tuple(out.shape) == tuple(shape) and out.stride(-1) == 1 and
+            all(out.stride(i) == out.stride(i + 1) * out.shape[i + 1] for i in range(out.dim() - 2)))
+
+
 def mlp_block(x, linear, norm, act, out=None, extras=(), flags=0):
     """ddsp/core.py:122-129, one whole block: LeakyReLU(LayerNorm(linear(x))) in one launch
     (ddsp_hip_mlp_block: the Linear on the matrix cores — at 512 inputs fp32-accurate bf16x3 products,
@@ -677,8 +671,7 @@ def mlp_block(x, linear, norm, act, out=None, extras=(), flags=0):
     rows = xc.numel() // K if K else 0
     if out is None:
         out = torch.empty(*lead, n_out, dtype=torch.float32, device=x.device)
-    elif (tuple(out.shape) != lead + (n_out,) or out.stride(-1) != 1 or
-          any(out.stride(i) != out.stride(i + 1) * out.shape[i + 1] for i in range(out.dim() - 2))):
+    elif not _row_strided(out, lead + (n_out,)):
         return None
     y_ld = out.stride(-2) if out.dim() >= 2 else n_out
     ec = [_c(e) for e in extras]
@@ -732,8 +725,7 @@ def layer_norm_leaky_relu(h, norm, act, out=None, w1=None, b1=None):
     rows = h.numel() // h.shape[-1] if h.shape[-1] else 0
     if out is None:
         out = torch.empty(*lead, cols, dtype=torch.float32, device=h.device)
-    elif (tuple(out.shape) != lead + (cols,) or out.stride(-1) != 1 or
-          any(out.stride(i) != out.stride(i + 1) * out.shape[i + 1] for i in range(out.dim() - 2))):
+    elif not _row_strided(out, lead + (cols,)):
         return None
     y_ld = out.stride(-2) if out.dim() >= 2 else cols
     g, b = _c(norm.weight), _c(norm.bias)
@@ -886,27 +878,17 @@ def stream_synth_frames(f0, param, mags, block_size, sample_rate, state, seed=0,
     prefix within the call (``wrap``: the carry taken modulo 2 pi).  ``noise`` [B,F,bs] injected, else
     on-device Philox with (seed, offset = state.counter).  Reads the state; ``stream_advance`` ends the
     call.  -> signal [B, F*bs, 1], with ``parts`` (signal, harmonic, noise).  Inference only."""
-    _dev(f0, param, mags)
-    B, F, H1 = param.shape
-    NB = mags.shape[-1]
-    bs = int(block_size)
-    if f0.shape != (B, F, 1) or mags.shape[:2] != (B, F) or H1 < 2:
-        raise RuntimeError("stream_synth_frames: f0 [B,F,1], param [B,F,H+1], mags [B,F,NB] expected")
+    B, F, H, NB, bs, noise = _frame_args(f0, param, mags, noise, block_size, "stream_synth_frames")
     if state.batch != B or state.buf.device != f0.device:
         raise RuntimeError("stream_synth_frames: the stream state is for another batch size or device")
-    if not synth_frames_in_envelope(H1 - 1, NB, bs, B):
+    if not synth_frames_in_envelope(H, NB, bs, B):
         raise RuntimeError("stream_synth_frames: shape outside the fused kernel's envelope")
-    if noise is not None:
-        _dev(noise)
-        if tuple(noise.shape) != (B, F, bs):
-            raise RuntimeError(f"stream_synth_frames: noise must be [B, F, block_size] = {(B, F, bs)}")
-        noise = _c(noise)
     out = torch.empty(B, F * bs, 1, dtype=torch.float32, device=f0.device)
     harm = torch.empty_like(out) if parts else None
     nz = torch.empty_like(out) if parts else None
     _lib.call("stream_synth_frames", _lib.ptr(_c(f0)), _lib.ptr(_c(param)), _lib.ptr(_c(mags)), float(bias),
               _lib.ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(state.counter), _lib.ptr(state.buf),
-              state.buf.numel(), int(bool(wrap)), _lib.ptr(out), _lib.ptr(harm), _lib.ptr(nz), B, F, H1 - 1, NB,
+              state.buf.numel(), int(bool(wrap)), _lib.ptr(out), _lib.ptr(harm), _lib.ptr(nz), B, F, H, NB,
               bs, float(sample_rate), _lib.stream_of(out))
     return (out, harm, nz) if parts else out
 

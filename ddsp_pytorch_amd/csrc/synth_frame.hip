@@ -423,16 +423,10 @@ struct FrameShape {
 static FrameShape frame_shape(int64_t n_harmonic, int64_t n_bands, int bs) {
   const int n = 2 * (int)(n_bands - 1), half = n / 2;
   FrameShape fs;
-  if (bs >= n) {
+  fs.lo_end = fs.tail_start = bs;  // one run over the whole frame, unless the FIR's two halves fit it apart
+  if (bs >= n && bs - half >= ((half + 3) & ~3)) {
     fs.lo_end = (half + 3) & ~3;
     fs.tail_start = bs - half;
-    if (fs.tail_start < fs.lo_end) {
-      fs.lo_end = bs;
-      fs.tail_start = bs;
-    }
-  } else {
-    fs.lo_end = bs;
-    fs.tail_start = bs;
   }
   fs.pad = (fs.lo_end + 4 + 3) & ~3;
   const int H4 = ((int)n_harmonic + 3) & ~3, n4 = (n + 3) & ~3;
@@ -441,62 +435,85 @@ static FrameShape frame_shape(int64_t n_harmonic, int64_t n_bands, int bs) {
   return fs;
 }
 
+// The fused kernels' launch plan: the one place that decides which shapes they take (the envelope that
+// ddsp_hip_synth_frames_supported reports) and how a shape is launched.
+struct FramePlan {
+  FrameShape fs;
+  int nt;      // threads per frame and thread group
+  int G;       // thread groups that share a frame's harmonics (the SPLIT kernels when > 1)
+  size_t shm;  // LDS bytes, the split buffer included
+  dim3 grid, block;
+  int status;  // DDSP_HIP_OK, or DDSP_HIP_ERANGE outside the envelope
+};
+static FramePlan frame_plan(int64_t batch, int64_t frames, int64_t n_harmonic, int64_t n_bands, int64_t block_size,
+                            bool split_allowed) {
+  FramePlan p{};
+  p.status = DDSP_HIP_ERANGE;
+  if (block_size % 4 || block_size > 1024 || n_harmonic > 1024 || n_bands > 1025 || batch > 65535 ||
+      frames > INT32_MAX)
+    return p;
+  const int bs = (int)block_size;
+  p.fs = frame_shape(n_harmonic, n_bands, bs);
+  const size_t lds_max = 120 * 1024;
+  // Cannot bind under the caps above: over every n_bands and block size at n_harmonic = 1024 a frame takes at
+  // most 45,104 bytes, the split buffer included.  It guards a raised cap.
+  if (sizeof(float) * p.fs.floats > lds_max) return p;
+  p.nt = std::max(64, ((bs / 4 + 63) / 64) * 64);
+  // few frames (far fewer workgroups than CUs): split each frame's harmonics over G thread groups
+  p.G = split_allowed && batch * frames < 512 ? std::max(1, std::min(4, 256 / p.nt)) : 1;
+  if (sizeof(float) * (p.fs.floats + (size_t)bs) > lds_max) p.G = 1;
+  p.shm = sizeof(float) * (p.fs.floats + (p.G > 1 ? (size_t)bs : 0));
+  p.grid = dim3((unsigned)frames, (unsigned)batch);
+  p.block = dim3((unsigned)(p.nt * p.G));
+  p.status = DDSP_HIP_OK;
+  return p;
+}
+
+// sizes no frame entry point takes (DDSP_HIP_EINVAL)
+static bool frame_sizes_invalid(int64_t batch, int64_t frames, int64_t n_harmonic, int64_t n_bands,
+                                int64_t block_size) {
+  return batch < 0 || frames < 0 || n_harmonic < 1 || n_bands < 2 || block_size < 4;
+}
+
 extern "C" {
+
+int ddsp_hip_synth_frames_supported(int64_t batch, int64_t n_harmonic, int64_t n_bands, int64_t block_size) {
+  if (frame_sizes_invalid(batch, 1, n_harmonic, n_bands, block_size)) return 0;
+  return frame_plan(batch, 1, n_harmonic, n_bands, block_size, true).status == DDSP_HIP_OK;
+}
 
 static int synth_frames_launch(const float* f0, const float* param, const float* raw_magnitudes, float bias,
                                const float* noise, uint64_t seed, uint64_t offset, uint64_t* counter, float* out,
                                float* harmonic_out, float* noise_out, float* controls_out, int64_t batch, int64_t frames,
                                int64_t n_harmonic, int64_t n_bands, int64_t block_size, float sample_rate,
-                               void* stream, int64_t param_ld = -1, int64_t mags_ld = -1,
-                               const double* prefix = nullptr) {
-  if (param_ld < 0) param_ld = n_harmonic + 1;
-  if (mags_ld < 0) mags_ld = n_bands;
-  if (batch < 0 || frames < 0 || n_harmonic < 1 || n_bands < 2 || block_size < 4) return DDSP_HIP_EINVAL;
+                               void* stream, int64_t param_ld, int64_t mags_ld, const double* prefix) {
+  if (frame_sizes_invalid(batch, frames, n_harmonic, n_bands, block_size)) return DDSP_HIP_EINVAL;
   if (param_ld < n_harmonic + 1 || mags_ld < n_bands || param_ld > INT32_MAX || mags_ld > INT32_MAX) return DDSP_HIP_EINVAL;
   if (batch == 0 || frames == 0) return DDSP_HIP_OK;
   if (!f0 || !param || !raw_magnitudes || !out) return DDSP_HIP_EINVAL;
-  // the fused kernel's shape envelope; callers fall back to the separate kernels outside it
-  if (block_size % 4 || block_size > 1024 || n_harmonic > 1024 || n_bands > 1025 || batch > 65535 ||
-      frames > INT32_MAX)
-    return DDSP_HIP_ERANGE;
-  const int bs = (int)block_size;
-  const FrameShape fs = frame_shape(n_harmonic, n_bands, bs);
-  const int lo_end = fs.lo_end, tail_start = fs.tail_start, pad = fs.pad;
-  const size_t floats = fs.floats;
-  if (sizeof(float) * floats > 120 * 1024) return DDSP_HIP_ERANGE;
-  const int nt = std::max(64, ((bs / 4 + 63) / 64) * 64);
-  // few frames (far fewer workgroups than CUs): split each frame's harmonics over G thread groups
-  int G = batch * frames < 512 && !prefix ? std::max(1, std::min(4, 256 / nt)) : 1;
-  if (sizeof(float) * (floats + (size_t)bs) > 120 * 1024) G = 1;
-  const size_t shm = sizeof(float) * (floats + (G > 1 ? (size_t)bs : 0));
+  // the kernel has a SPLIT form and a PREFIX form, none with both: a launch that reads a prefix is not split
+  const FramePlan p = frame_plan(batch, frames, n_harmonic, n_bands, block_size, !prefix);
+  if (p.status != DDSP_HIP_OK) return p.status;
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
   const uint32_t o0 = (uint32_t)offset, o1 = (uint32_t)(offset >> 32);
-  const dim3 grid((unsigned)frames, (unsigned)batch), block((unsigned)(nt * G));
-#define DDSP_SYNTH_FRAME_LAUNCH(RNG_, SPLIT_)                                                             \
-  do {                                                                                                  \
-    if (controls_out) DDSP_SYNTH_FRAME_LAUNCH_(RNG_, SPLIT_, true);                                       \
-    else DDSP_SYNTH_FRAME_LAUNCH_(RNG_, SPLIT_, false);                                                  \
+#define DDSP_SYNTH_FRAME_LAUNCH(RNG_, CTRL_)                                                               \
+  do {                                                                                                   \
+    if (p.G > 1) DDSP_SYNTH_FRAME_LAUNCH_(RNG_, true, CTRL_, false);                                       \
+    else if (prefix) DDSP_SYNTH_FRAME_LAUNCH_(RNG_, false, CTRL_, true);                                   \
+    else DDSP_SYNTH_FRAME_LAUNCH_(RNG_, false, CTRL_, false);                                              \
   } while (0)
-#define DDSP_SYNTH_FRAME_LAUNCH_(RNG_, SPLIT_, CTRL_)                                                      \
-  do {                                                                                                  \
-    if (!SPLIT_ && prefix) DDSP_SYNTH_FRAME_LAUNCH_P(RNG_, false, CTRL_, true);                            \
-    else DDSP_SYNTH_FRAME_LAUNCH_P(RNG_, SPLIT_, CTRL_, false);                                            \
-  } while (0)
-#define DDSP_SYNTH_FRAME_LAUNCH_P(RNG_, SPLIT_, CTRL_, PREFIX_)                                            \
-  hipLaunchKernelGGL((synth_frame_kernel<RNG_, SPLIT_, CTRL_, PREFIX_>), grid, block, shm, S(stream), f0, param, raw_magnitudes, \
-                     bias, RNG_ ? nullptr : noise, k0, k1, o0, o1, RNG_ ? counter : nullptr, out, harmonic_out,  \
-                     noise_out, controls_out, (int)frames, (int)n_harmonic, (int)n_bands, bs, sample_rate, lo_end, \
-                     tail_start, pad, (int)param_ld, (int)mags_ld, prefix)
-  if (noise) {
-    if (G > 1) DDSP_SYNTH_FRAME_LAUNCH(false, true);
-    else DDSP_SYNTH_FRAME_LAUNCH(false, false);
-  } else {
-    if (G > 1) DDSP_SYNTH_FRAME_LAUNCH(true, true);
-    else DDSP_SYNTH_FRAME_LAUNCH(true, false);
-  }
+#define DDSP_SYNTH_FRAME_LAUNCH_(RNG_, SPLIT_, CTRL_, PREFIX_)                                             \
+  hipLaunchKernelGGL((synth_frame_kernel<RNG_, SPLIT_, CTRL_, PREFIX_>), p.grid, p.block, p.shm, S(stream), f0, param, \
+                     raw_magnitudes, bias, RNG_ ? nullptr : noise, k0, k1, o0, o1, RNG_ ? counter : nullptr, out,  \
+                     harmonic_out, noise_out, controls_out, (int)frames, (int)n_harmonic, (int)n_bands,            \
+                     (int)block_size, sample_rate, p.fs.lo_end, p.fs.tail_start, p.fs.pad, (int)param_ld,          \
+                     (int)mags_ld, prefix)
+  if (noise && controls_out) DDSP_SYNTH_FRAME_LAUNCH(false, true);
+  else if (noise) DDSP_SYNTH_FRAME_LAUNCH(false, false);
+  else if (controls_out) DDSP_SYNTH_FRAME_LAUNCH(true, true);
+  else DDSP_SYNTH_FRAME_LAUNCH(true, false);
 #undef DDSP_SYNTH_FRAME_LAUNCH
 #undef DDSP_SYNTH_FRAME_LAUNCH_
-#undef DDSP_SYNTH_FRAME_LAUNCH_P
   if (!noise && counter) hipLaunchKernelGGL(counter_advance_kernel, dim3(1), dim3(1), 0, S(stream), counter);
   return launch_status();
 }
@@ -507,17 +524,8 @@ int ddsp_hip_synth_frames(const float* f0, const float* param, const float* raw_
                           int64_t n_harmonic, int64_t n_bands, int64_t block_size, float sample_rate,
                           void* stream) {
   return synth_frames_launch(f0, param, raw_magnitudes, bias, noise, seed, offset, nullptr, out, harmonic_out,
-                             noise_out, nullptr, batch, frames, n_harmonic, n_bands, block_size, sample_rate, stream);
-}
-
-int ddsp_hip_synth_frames_controls(const float* f0, const float* param, int64_t param_ld, const float* raw_magnitudes,
-                                   int64_t magnitudes_ld, float bias, const float* noise, uint64_t seed,
-                                   uint64_t offset, float* out, float* harmonic_out, float* noise_out,
-                                   float* controls_out, int64_t batch, int64_t frames, int64_t n_harmonic,
-                                   int64_t n_bands, int64_t block_size, float sample_rate, void* stream) {
-  return synth_frames_launch(f0, param, raw_magnitudes, bias, noise, seed, offset, nullptr, out, harmonic_out,
-                             noise_out, controls_out, batch, frames, n_harmonic, n_bands, block_size, sample_rate,
-                             stream, param_ld, magnitudes_ld);
+                             noise_out, nullptr, batch, frames, n_harmonic, n_bands, block_size, sample_rate, stream,
+                             n_harmonic + 1, n_bands, nullptr);
 }
 
 int ddsp_hip_synth_frames_controls_prefix(const float* f0, const float* param, int64_t param_ld,
@@ -549,7 +557,8 @@ int ddsp_hip_synth_frames_counter(const float* f0, const float* param, const flo
                                   void* stream) {
   if (!counter) return DDSP_HIP_EINVAL;
   return synth_frames_launch(f0, param, raw_magnitudes, bias, nullptr, seed, 0, counter, out, nullptr, nullptr,
-                             nullptr, batch, frames, n_harmonic, n_bands, block_size, sample_rate, stream);
+                             nullptr, batch, frames, n_harmonic, n_bands, block_size, sample_rate, stream,
+                             n_harmonic + 1, n_bands, nullptr);
 }
 
 int ddsp_hip_stream_synth_frames(const float* f0, const float* param, const float* raw_magnitudes, float bias,
@@ -557,36 +566,24 @@ int ddsp_hip_stream_synth_frames(const float* f0, const float* param, const floa
                                  size_t state_bytes, int wrap, float* out, float* harmonic_out, float* noise_out,
                                  int64_t batch, int64_t frames, int64_t n_harmonic, int64_t n_bands,
                                  int64_t block_size, float sample_rate, void* stream) {
-  if (batch < 0 || frames < 0 || n_harmonic < 1 || n_bands < 2 || block_size < 4 || !(sample_rate > 0))
+  if (frame_sizes_invalid(batch, frames, n_harmonic, n_bands, block_size) || !(sample_rate > 0))
     return DDSP_HIP_EINVAL;
   if (batch == 0 || frames == 0) return DDSP_HIP_OK;
   if (!f0 || !param || !raw_magnitudes || !out || !state || (!noise && !counter)) return DDSP_HIP_EINVAL;
-  if (block_size % 4 || block_size > 1024 || n_harmonic > 1024 || n_bands > 1025 || batch > 65535 ||
-      frames > INT32_MAX)
-    return DDSP_HIP_ERANGE;
-  const int bs = (int)block_size;
-  const FrameShape fs = frame_shape(n_harmonic, n_bands, bs);
-  if (sizeof(float) * fs.floats > 120 * 1024) return DDSP_HIP_ERANGE;
+  const FramePlan p = frame_plan(batch, frames, n_harmonic, n_bands, block_size, true);
+  if (p.status != DDSP_HIP_OK) return p.status;
   if (state_bytes < (size_t)batch * sizeof(double)) return DDSP_HIP_EWORKSPACE;
-  const int nt = std::max(64, ((bs / 4 + 63) / 64) * 64);
-  // few frames per call: each frame's harmonics split over G thread groups, as in ddsp_hip_synth_frames
-  int G = batch * frames < 512 ? std::max(1, std::min(4, 256 / nt)) : 1;
-  if (sizeof(float) * (fs.floats + (size_t)bs) > 120 * 1024) G = 1;
-  const size_t shm = sizeof(float) * (fs.floats + (G > 1 ? (size_t)bs : 0));
-  const dim3 grid((unsigned)frames, (unsigned)batch), block((unsigned)(nt * G));
   const double* carry = reinterpret_cast<const double*>(state);
 #define DDSP_SYNTH_STREAM_LAUNCH(RNG_, SPLIT_)                                                                     \
-  hipLaunchKernelGGL((synth_stream_kernel<RNG_, SPLIT_>), grid, block, shm, S(stream), f0, param, raw_magnitudes,  \
-                     bias, RNG_ ? nullptr : noise, (uint32_t)seed, (uint32_t)(seed >> 32),                        \
+  hipLaunchKernelGGL((synth_stream_kernel<RNG_, SPLIT_>), p.grid, p.block, p.shm, S(stream), f0, param,            \
+                     raw_magnitudes, bias, RNG_ ? nullptr : noise, (uint32_t)seed, (uint32_t)(seed >> 32),        \
                      RNG_ ? counter : nullptr, carry, wrap ? 1 : 0, out, harmonic_out, noise_out, (int)frames,     \
-                     (int)n_harmonic, (int)n_bands, bs, sample_rate, fs.lo_end, fs.tail_start, fs.pad)
-  if (noise) {
-    if (G > 1) DDSP_SYNTH_STREAM_LAUNCH(false, true);
-    else DDSP_SYNTH_STREAM_LAUNCH(false, false);
-  } else {
-    if (G > 1) DDSP_SYNTH_STREAM_LAUNCH(true, true);
-    else DDSP_SYNTH_STREAM_LAUNCH(true, false);
-  }
+                     (int)n_harmonic, (int)n_bands, (int)block_size, sample_rate, p.fs.lo_end, p.fs.tail_start,    \
+                     p.fs.pad)
+  if (noise && p.G > 1) DDSP_SYNTH_STREAM_LAUNCH(false, true);
+  else if (noise) DDSP_SYNTH_STREAM_LAUNCH(false, false);
+  else if (p.G > 1) DDSP_SYNTH_STREAM_LAUNCH(true, true);
+  else DDSP_SYNTH_STREAM_LAUNCH(true, false);
 #undef DDSP_SYNTH_STREAM_LAUNCH
   return launch_status();
 }

@@ -145,10 +145,10 @@ std::tuple<at::Tensor, at::Tensor> harmonic_controls(const at::Tensor& amplitude
   const int64_t B = distribution.size(0), F = distribution.size(1), H = distribution.size(2);
   TORCH_CHECK(amplitudes.sizes() == at::IntArrayRef({B, F, 1}) && f0.sizes() == at::IntArrayRef({B, F, 1}),
               "harmonic_controls: amplitudes and f0 must be [B,F,1]");
-  auto rows_view = [](const at::Tensor& t) {
-    at::Tensor v = t;
-    if (v.stride(-1) != 1 || v.stride(0) != v.size(1) * v.stride(1)) v = v.contiguous();
-    return v;
+  auto rows_view = [](const at::Tensor& t) {  // core._frame_rows: overlapping (e.g. broadcast) rows are copied
+    const bool rows = t.stride(-1) == 1 && t.stride(1) >= std::max<int64_t>(t.size(2), 1) &&
+                      t.stride(0) == t.size(1) * t.stride(1);
+    return rows ? t : t.contiguous();
   };
   at::Tensor a = rows_view(amplitudes), d = rows_view(distribution), f = c16(f0);
   at::Tensor amp_out = at::empty({B, F, 1}, f.options()), dist_out = at::empty({B, F, H}, f.options());
@@ -226,6 +226,31 @@ at::Tensor filtered_noise(const at::Tensor& magnitudes, int64_t block_size, cons
   return out;
 }
 
+// The fused synthesis ops' frame arguments, checked and contiguous (`op` names the operator in the messages)
+struct FrameArgs {
+  at::Tensor f, p, m, n;  // f0 [B,F,1], param [B,F,H+1], mags [B,F,NB], noise [B,F,bs] or undefined
+  const float* np;        // the noise's pointer, or null
+  int64_t B, F, H, NB;
+};
+FrameArgs frame_args(const at::Tensor& f0, const at::Tensor& param, const at::Tensor& mags,
+                     const std::optional<at::Tensor>& noise, int64_t block_size, const char* op) {
+  check_dev(f0, "f0");
+  check_dev(param, "param");
+  check_dev(mags, "mags");
+  TORCH_CHECK(param.dim() == 3 && mags.dim() == 3, op, ": param [B,F,H+1] and mags [B,F,NB] expected");
+  const int64_t B = param.size(0), F = param.size(1), H1 = param.size(2), NB = mags.size(2);
+  TORCH_CHECK(f0.sizes() == at::IntArrayRef({B, F, 1}) && mags.size(0) == B && mags.size(1) == F && H1 >= 2, op,
+              ": f0 [B,F,1], param [B,F,H+1], mags [B,F,NB] expected");
+  FrameArgs a{c16(f0), c16(param), c16(mags), at::Tensor(), nullptr, B, F, H1 - 1, NB};
+  if (noise.has_value()) {
+    check_dev(*noise, "noise");
+    TORCH_CHECK(noise->sizes() == at::IntArrayRef({B, F, block_size}), op, ": noise must be [B,F,bs]");
+    a.n = c16(*noise);
+    a.np = a.n.data_ptr<float>();
+  }
+  return a;
+}
+
 // decoder.py:106-121 in one launch (ddsp_hip_synth_frames): harmonic + filtered noise, their controls and
 // the sum; outside the fused kernel's shape envelope the two module kernels (harmonic_synth_params, then
 // filtered_noise adding the harmonic).  parts: the harmonic and noise signals as well.
@@ -234,35 +259,22 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> synth_frames_impl(const at::Tenso
                                                                  double sample_rate, double bias,
                                                                  const std::optional<at::Tensor>& noise,
                                                                  int64_t seed, int64_t offset, bool parts) {
-  check_dev(f0, "f0");
-  check_dev(param, "param");
-  check_dev(mags, "mags");
-  TORCH_CHECK(param.dim() == 3 && mags.dim() == 3, "synth_frames: param [B,F,H+1] and mags [B,F,NB] expected");
-  const int64_t B = param.size(0), F = param.size(1), H1 = param.size(2), NB = mags.size(2);
-  TORCH_CHECK(f0.sizes() == at::IntArrayRef({B, F, 1}) && mags.size(0) == B && mags.size(1) == F && H1 >= 2,
-              "synth_frames: f0 [B,F,1], param [B,F,H+1], mags [B,F,NB] expected");
-  at::Tensor f = c16(f0), p = c16(param), m = c16(mags), n;
-  if (noise.has_value()) {
-    check_dev(*noise, "noise");
-    TORCH_CHECK(noise->sizes() == at::IntArrayRef({B, F, block_size}), "synth_frames: noise must be [B,F,bs]");
-    n = c16(*noise);
-  }
-  const float* np = n.defined() ? n.data_ptr<float>() : nullptr;
-  at::Tensor out = at::empty({B, F * block_size, 1}, f.options());
+  const FrameArgs a = frame_args(f0, param, mags, noise, block_size, "synth_frames");
+  const float *f = a.f.data_ptr<float>(), *p = a.p.data_ptr<float>(), *m = a.m.data_ptr<float>();
+  at::Tensor out = at::empty({a.B, a.F * block_size, 1}, a.f.options());
   at::Tensor harm = parts ? at::empty_like(out) : at::Tensor();
   at::Tensor nz = parts ? at::empty_like(out) : at::Tensor();
-  int st = ddsp_hip_synth_frames(f.data_ptr<float>(), p.data_ptr<float>(), m.data_ptr<float>(), (float)bias, np,
-                                 (uint64_t)seed, (uint64_t)offset, out.data_ptr<float>(),
-                                 parts ? harm.data_ptr<float>() : nullptr, parts ? nz.data_ptr<float>() : nullptr, B,
-                                 F, H1 - 1, NB, block_size, (float)sample_rate, stream_of(f));
+  float* nzp = parts ? nz.data_ptr<float>() : nullptr;
+  int st = ddsp_hip_synth_frames(f, p, m, (float)bias, a.np, (uint64_t)seed, (uint64_t)offset, out.data_ptr<float>(),
+                                 parts ? harm.data_ptr<float>() : nullptr, nzp, a.B, a.F, a.H, a.NB, block_size,
+                                 (float)sample_rate, stream_of(a.f));
   if (st == DDSP_HIP_ERANGE) {  // outside the fused kernel's envelope: the two module kernels
     at::Tensor h = parts ? harm : at::empty_like(out);
-    ok(ddsp_hip_harmonic_synth_params(f.data_ptr<float>(), p.data_ptr<float>(), h.data_ptr<float>(), B, F, H1 - 1,
-                                      block_size, (float)sample_rate, stream_of(f)),
+    ok(ddsp_hip_harmonic_synth_params(f, p, h.data_ptr<float>(), a.B, a.F, a.H, block_size, (float)sample_rate,
+                                      stream_of(a.f)),
        "harmonic_synth_params");
-    st = ddsp_hip_filtered_noise_params(m.data_ptr<float>(), (float)bias, np, (uint64_t)seed, (uint64_t)offset,
-                                        h.data_ptr<float>(), out.data_ptr<float>(),
-                                        parts ? nz.data_ptr<float>() : nullptr, B, F, NB, block_size, stream_of(f));
+    st = ddsp_hip_filtered_noise_params(m, (float)bias, a.np, (uint64_t)seed, (uint64_t)offset, h.data_ptr<float>(),
+                                        out.data_ptr<float>(), nzp, a.B, a.F, a.NB, block_size, stream_of(a.f));
   }
   ok(st, "synth_frames");
   return {out, harm, nz};
@@ -336,26 +348,13 @@ at::Tensor synth_frames_stream(const at::Tensor& f0, const at::Tensor& param, co
                                int64_t block_size, double sample_rate, double bias,
                                const std::optional<at::Tensor>& noise, int64_t seed, const at::Tensor& counter,
                                at::Tensor& state, bool wrap) {
-  check_dev(f0, "f0");
-  check_dev(param, "param");
-  check_dev(mags, "mags");
+  const FrameArgs a = frame_args(f0, param, mags, noise, block_size, "synth_frames_stream");
   check_stream(counter, state, f0);
-  TORCH_CHECK(param.dim() == 3 && mags.dim() == 3, "synth_frames_stream: param [B,F,H+1] and mags [B,F,NB] expected");
-  const int64_t B = param.size(0), F = param.size(1), H1 = param.size(2), NB = mags.size(2);
-  TORCH_CHECK(f0.sizes() == at::IntArrayRef({B, F, 1}) && mags.size(0) == B && mags.size(1) == F && H1 >= 2,
-              "synth_frames_stream: f0 [B,F,1], param [B,F,H+1], mags [B,F,NB] expected");
-  at::Tensor f = c16(f0), p = c16(param), m = c16(mags), n;
-  if (noise.has_value()) {
-    check_dev(*noise, "noise");
-    TORCH_CHECK(noise->sizes() == at::IntArrayRef({B, F, block_size}), "synth_frames_stream: noise must be [B,F,bs]");
-    n = c16(*noise);
-  }
-  at::Tensor out = at::empty({B, F * block_size, 1}, f.options());
-  ok(ddsp_hip_stream_synth_frames(f.data_ptr<float>(), p.data_ptr<float>(), m.data_ptr<float>(), (float)bias,
-                                  n.defined() ? n.data_ptr<float>() : nullptr, (uint64_t)seed,
-                                  reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
-                                  (size_t)state.numel(), wrap ? 1 : 0, out.data_ptr<float>(), nullptr, nullptr, B, F,
-                                  H1 - 1, NB, block_size, (float)sample_rate, stream_of(f)),
+  at::Tensor out = at::empty({a.B, a.F * block_size, 1}, a.f.options());
+  ok(ddsp_hip_stream_synth_frames(a.f.data_ptr<float>(), a.p.data_ptr<float>(), a.m.data_ptr<float>(), (float)bias,
+                                  a.np, (uint64_t)seed, reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()),
+                                  state.data_ptr(), (size_t)state.numel(), wrap ? 1 : 0, out.data_ptr<float>(), nullptr,
+                                  nullptr, a.B, a.F, a.H, a.NB, block_size, (float)sample_rate, stream_of(a.f)),
      "stream_synth_frames");
   return out;
 }

@@ -38,10 +38,6 @@ def refuse_f0_grad(f0, name):
             "training loop, train.py:84-99); pass f0.detach()")
 
 
-def wants_grad(*tensors):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
-
-
 # ------------------------------------------------------------------------------------------
 class ScaleFn(_F):
     """core.py:77-78 (+ the bias of modules.py:113)."""
@@ -183,8 +179,7 @@ class ControlsFn(_F):
     def backward(ctx, g_amp, g_dist):
         a, d, f0 = ctx.saved_tensors
         B, F, H = d.shape
-        a_v, a_ld = core._rows_view(a, "amplitudes")
-        d_v, d_ld = core._rows_view(d, "harmonic_distribution")
+        (a_v, a_ld), (d_v, d_ld) = core._frame_rows(a), core._frame_rows(d)
         g_amp = _g(g_amp) if g_amp is not None else torch.zeros(B, F, 1, device=d.device)
         g_dist = _g(g_dist) if g_dist is not None else torch.zeros(B, F, H, device=d.device)
         da = torch.empty(B, F, 1, dtype=torch.float32, device=d.device)

@@ -55,19 +55,13 @@ class SynthPath(nn.Module):
     @torch.no_grad()
     def synthesize(self, f0, param, mags, noise=None):
         """decoder.py:106-121: harmonic + filtered noise (both synths, their controls and the sum)
-        in one kernel — the path before the reverb."""
+        in one kernel (outside its envelope two, core.synth_signal) — the path before the reverb."""
         if self.noise_mode == "inject" and noise is None:
             raise ValueError("noise_mode='inject' needs a noise tensor")
         nz = noise if self.noise_mode == "inject" else None
         with self._t("synth_frames"):
-            signal = core.synth_frames(f0, param, mags, self.block_size, self.sample_rate,
-                                       bias=self.initial_bias, noise=nz)
-        if signal is None:  # outside the fused kernel's envelope: two kernels
-            with self._t("synth_frames"):
-                harmonic = core.harmonic_synth_params(f0, param, self.block_size, self.sample_rate)
-                signal = core.filtered_noise(mags, self.block_size, noise=nz, add=harmonic,
-                                             raw_bias=self.initial_bias)
-        return signal
+            return core.synth_signal(f0, param, mags, self.block_size, self.sample_rate,
+                                     bias=self.initial_bias, noise=nz)
 
     @torch.no_grad()
     def forward(self, f0, param, mags, noise=None):
@@ -198,12 +192,8 @@ class SynthGraph:
             sig = core.synth_frames_counter(self.f0, self.param, self.mags, p.block_size, p.sample_rate,
                                             self.counter, self.seed, bias=p.initial_bias)
         else:
-            sig = core.synth_frames(self.f0, self.param, self.mags, p.block_size, p.sample_rate,
+            sig = core.synth_signal(self.f0, self.param, self.mags, p.block_size, p.sample_rate,
                                     bias=p.initial_bias, noise=self.noise)
-            if sig is None:
-                harmonic = core.harmonic_synth_params(self.f0, self.param, p.block_size, p.sample_rate)
-                sig = core.filtered_noise(self.mags, p.block_size, noise=self.noise, add=harmonic,
-                                          raw_bias=p.initial_bias)
         rv = p.reverb
         if rv is None:
             return sig

@@ -132,13 +132,20 @@ int ddsp_hip_filtered_noise_params(const float* raw_magnitudes, float bias, cons
  * projection param[B,F,H+1], FilteredNoise.get_controls + forward from the raw noise projection
  * raw_magnitudes[B,F,NB] (scale_function(x + bias)), and signal = harmonic + noise -> out[B,F*bs].
  * noise / seed / offset as ddsp_hip_filtered_noise; harmonic_out and noise_out (nullable)
- * receive the two parts.  Shape envelope: block_size % 4 == 0 and <= 1024, H <= 1024,
- * NB <= 1025; outside it DDSP_HIP_ERANGE is returned and callers use the separate kernels. */
+ * receive the two parts.  Outside the fused kernel's envelope (ddsp_hip_synth_frames_supported)
+ * DDSP_HIP_ERANGE is returned and callers use the separate kernels. */
 int ddsp_hip_synth_frames(const float* f0, const float* param, const float* raw_magnitudes, float bias,
                           const float* noise, uint64_t seed, uint64_t offset, float* out,
                           float* harmonic_out, float* noise_out, int64_t batch, int64_t frames,
                           int64_t n_harmonic, int64_t n_bands, int64_t block_size, float sample_rate,
                           void* stream);
+
+/* The fused frame kernel's shape envelope, the one shared by ddsp_hip_synth_frames, _controls_prefix,
+ * _counter and ddsp_hip_stream_synth_frames: 1 when they take (batch, n_harmonic, n_bands, block_size) for
+ * some frames >= 1, 0 when they answer DDSP_HIP_ERANGE or DDSP_HIP_EINVAL.  Today: block_size % 4 == 0 and
+ * <= 1024, n_harmonic <= 1024, n_bands <= 1025, batch <= 65535 (a frame's LDS, which also bounds it, cannot
+ * bind under these caps).  Host only: no device is needed or touched. */
+int ddsp_hip_synth_frames_supported(int64_t batch, int64_t n_harmonic, int64_t n_bands, int64_t block_size);
 
 /* ddsp_hip_synth_frames that also writes the controls DDSPDecoder.forward returns
  * (decoder.py:127-135: output['harmonic_ctrls'], output['noise_ctrls']) into controls_out (nullable),
@@ -147,13 +154,8 @@ int ddsp_hip_synth_frames(const float* f0, const float* param, const float* raw_
  * HarmonicSynth.forward's in-place `*= amplitudes` (modules.py:61,73), magnitudes =
  * scale_function(raw_magnitudes + bias) (modules.py:111-114).  param_ld / magnitudes_ld: elements between
  * consecutive frames' rows (>= H + 1 / >= NB), so both may be column slices of one projection output
- * (decoder.py:106-117 computed as a single GEMM). */
-int ddsp_hip_synth_frames_controls(const float* f0, const float* param, int64_t param_ld, const float* raw_magnitudes,
-                                   int64_t magnitudes_ld, float bias, const float* noise, uint64_t seed,
-                                   uint64_t offset, float* out, float* harmonic_out, float* noise_out,
-                                   float* controls_out, int64_t batch, int64_t frames, int64_t n_harmonic,
-                                   int64_t n_bands, int64_t block_size, float sample_rate, void* stream);
-/* The same with frame_prefix (nullable): the exact fp64 phase prefix of every frame,
+ * (decoder.py:106-117 computed as a single GEMM).
+ * frame_prefix (nullable): the exact fp64 phase prefix of every frame,
  * frame_prefix[b * frames + f] = sum_{g < f} block_size * fl32(fl32(fl32(2 pi) f0[b, g]) / sr) (the
  * reference's cumsum, core.py:138, at each frame's start), as ddsp_hip_frame_phase_prefix writes it.
  * Without it every frame's workgroup sums its earlier frames itself: O(frames) per frame, O(frames^2)

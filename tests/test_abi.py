@@ -56,6 +56,61 @@ def test_abi_rejects_bad_arguments_without_launching():
     # empty inputs are a no-op success
     assert lib.ddsp_hip_scale_function(null, null, 0, 0.0, null) == 0
     assert lib.ddsp_hip_harmonic_synth_frames(null, null, null, 0, null, 0, 5, 4, 512, 48000.0, null) == 0
+    # the removed duplicate of ddsp_hip_synth_frames_controls_prefix is gone from header, library and ctypes table
+    assert "ddsp_hip_synth_frames_controls" not in declared_symbols()
+    assert "ddsp_hip_synth_frames_controls" not in _lib.SIGNATURES
+    assert not hasattr(lib, "ddsp_hip_synth_frames_controls")
+    assert lib.ddsp_hip_version() >= 103
+    # a missing entry point is the same error from query as from call
+    for use in (_lib.query, _lib.call):
+        with pytest.raises(RuntimeError, match="entry point ddsp_hip_no_such_thing is missing"):
+            use("no_such_thing")
+    _synth_frames_envelope_cases(lib)
+
+
+# (batch, H, NB, block) -> inside the fused frame kernel's envelope; one row on each side of every cap.  The
+# expected column is the rule itself (block % 4 == 0 and 4 <= block <= 1024, 1 <= H <= 1024, 2 <= NB <= 1025,
+# batch <= 65535), written out, not computed by the library
+ENVELOPE = [
+    ((32, 100, 65, 1024), True), ((32, 100, 65, 1028), False), ((32, 100, 65, 510), False),
+    ((32, 100, 65, 0), False),
+    ((32, 1024, 65, 512), True), ((32, 1025, 65, 512), False), ((32, 0, 65, 512), False),
+    ((32, 100, 1025, 512), True), ((32, 100, 1026, 512), False), ((32, 100, 1, 512), False),
+    ((65535, 100, 65, 512), True), ((65536, 100, 65, 512), False),
+    ((32, 100, 65, 512), True),  # config 2
+]
+ENVELOPE_INVALID_SIZES = {(32, 100, 65, 0), (32, 0, 65, 512), (32, 100, 1, 512)}  # DDSP_HIP_EINVAL, not ERANGE
+
+
+def _synth_frames_envelope_cases(lib):
+    """ddsp_hip_synth_frames_supported against the literal table, and outside the envelope (sizes otherwise
+    valid) the plain and the stream launch answer ERANGE before any HIP call; nothing here may launch, so
+    neither is called on a supported row."""
+    import ctypes
+    from ddsp_pytorch_amd import core
+    null, dummy = ctypes.c_void_p(0), ctypes.c_void_p(256)  # dummy: never dereferenced
+    EINVAL, ERANGE = 1, 5
+    for (B, H, NB, bs), inside in ENVELOPE:
+        assert lib.ddsp_hip_synth_frames_supported(B, H, NB, bs) == int(inside), (B, H, NB, bs)
+        assert core.synth_frames_in_envelope(H, NB, bs, B) is inside
+        if inside:
+            continue
+        want = EINVAL if (B, H, NB, bs) in ENVELOPE_INVALID_SIZES else ERANGE
+        assert lib.ddsp_hip_synth_frames(dummy, dummy, dummy, -5.0, dummy, 0, 0, dummy, null, null, B, 2, H, NB, bs,
+                                         48000.0, null) == want, (B, H, NB, bs)
+        assert lib.ddsp_hip_stream_synth_frames(dummy, dummy, dummy, -5.0, dummy, 0, null, dummy, 8 * B, 1, dummy, null,
+                                                null, B, 2, H, NB, bs, 48000.0, null) == want, (B, H, NB, bs)
+    # the checks only one of the two makes keep their place: a short stream state is seen after the envelope
+    assert lib.ddsp_hip_stream_synth_frames(dummy, dummy, dummy, -5.0, dummy, 0, null, dummy, 8, 1, dummy, null, null,
+                                            32, 2, 100, 65, 1028, 48000.0, null) == ERANGE
+    assert lib.ddsp_hip_stream_synth_frames(dummy, dummy, dummy, -5.0, null, 0, null, dummy, 8 * 32, 1, dummy, null,
+                                            null, 32, 2, 100, 65, 1028, 48000.0, null) == EINVAL  # noise || counter
+    assert lib.ddsp_hip_stream_synth_frames(dummy, dummy, dummy, -5.0, dummy, 0, null, dummy, 8 * 32, 1, dummy, null,
+                                            null, 32, 2, 100, 65, 1028, 0.0, null) == EINVAL  # sample_rate
+    assert lib.ddsp_hip_synth_frames(dummy, dummy, dummy, -5.0, dummy, 0, 0, null, null, null, 32, 2, 100, 65, 1028,
+                                     48000.0, null) == EINVAL  # null out before the envelope
+    assert lib.ddsp_hip_synth_frames_controls_prefix(dummy, dummy, 100, dummy, 65, -5.0, dummy, 0, 0, dummy, null, null,
+                                                     null, null, 32, 2, 100, 65, 1028, 48000.0, null) == EINVAL  # ld
 
 
 def test_no_cpu_fallback():

@@ -142,6 +142,36 @@ def test_harmonic_module_grad(dd, B, F, bs, H):
     assert relerr(pg2.grad, pc.grad) < GRAD_REL, relerr(pg2.grad, pc.grad)
 
 
+def test_harmonic_controls_broadcast_rows(dd):
+    """Amplitudes and distribution expanded over the frames from one row (row stride 0: the rows overlap).
+    core.harmonic_controls and its backward (grad.ControlsFn) read a contiguous copy of such rows, so they equal
+    the results for .contiguous() copies of the same inputs bit for bit.  (A row stride below the row's width
+    used to be handed to the kernels, which refuse it as an invalid argument.)"""
+    B, F, H = 1, 3, 4
+    g = torch.Generator().manual_seed(5)
+    a_row, d_row = torch.randn(1, generator=g).cuda(), torch.randn(H, generator=g).cuda()
+    f0 = f0_frames(B, F, 5).cuda()
+    ups = torch.randn(B, F, 1, generator=g).cuda(), torch.randn(B, F, H, generator=g).cuda()
+    a, d = a_row.expand(B, F, 1), d_row.expand(B, F, H)
+    assert a.stride() == (0, 0, 1) and d.stride() == (0, 0, 1)
+    with torch.no_grad():
+        want = dd.core.harmonic_controls(a.contiguous(), d.contiguous(), f0, 48000)
+        got = dd.core.harmonic_controls(a, d, f0, 48000)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    from ddsp_pytorch_amd import script
+    script.load_ops()  # the TorchScript operator copies such rows too
+    got = torch.ops.ddsp_hip.harmonic_controls(a, d, f0, 48000.0)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    grads = []
+    for ins in ((a.contiguous().requires_grad_(True), d.contiguous().requires_grad_(True)),
+                (a_row.clone().requires_grad_(True).expand(B, F, 1), d_row.clone().requires_grad_(True).expand(B, F, H))):
+        outs = dd.core.harmonic_controls(*ins, f0, 48000)
+        assert outs[0].grad_fn is not None and torch.equal(outs[0], want[0]) and torch.equal(outs[1], want[1])
+        grads.append(torch.autograd.grad(outs, ins, ups))  # what ControlsFn.backward returns, [B,F,1] and [B,F,H]
+    assert torch.equal(grads[0][0], grads[1][0]) and torch.equal(grads[0][1], grads[1][1])
+    assert grads[0][1].abs().sum() > 0
+
+
 @pytest.mark.parametrize("B,F,bs,NB", [(2, 16, 512, 65), (1, 8, 256, 65), (2, 4, 64, 17),
                                        # the wave-per-frame noise VJP's lag-segment tails (bs/8 = 80, 96, 112, 128
                                        # lags: 64 + 16, 64 + 32, 64 + 32 + 16, 2 x 64) and a frame count that

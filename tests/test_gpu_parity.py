@@ -575,9 +575,10 @@ def test_config5_synth_path_items(dd):
 
 # ------------------------------------------------------------------ fused synthesis frame
 @pytest.mark.parametrize("B,F,H,NB,bs", [(2, 16, 100, 65, 512), (1, 6, 64, 65, 256), (2, 5, 17, 9, 64),
-                                         (1, 3, 128, 129, 1024), (1, 4, 100, 65, 441)])
+                                         (1, 3, 128, 129, 1024), (1, 4, 100, 65, 441), (1, 2, 4, 5, 6)])
 def test_synth_frames_vs_oracle(dd, B, F, H, NB, bs):
-    """decoder.py:106-121 in one kernel (or the two-kernel fallback outside its envelope)."""
+    """decoder.py:106-121 in one kernel (or the two-kernel fallback outside its envelope, core.synth_signal,
+    which SynthPath and a captured SynthGraph both take: there bit for bit the two module kernels)."""
     rng = np.random.default_rng(B * 100 + H + bs)
     f0 = (50.0 * 20.0 ** rng.random((B, F, 1))).astype(np.float32)
     param = rng.standard_normal((B, F, H + 1)).astype(np.float32)
@@ -590,10 +591,16 @@ def test_synth_frames_vs_oracle(dd, B, F, H, NB, bs):
         r = dd.core.synth_frames(G(f0), G(param), G(mags), bs, 48000, noise=G(noise), parts=True)
         syn = dd.synth.SynthPath(bs, 48000, reverb_length=None, noise_mode="inject")
         path = C(syn(G(f0), G(param), G(mags), G(noise)))
+        graphed = C(dd.synth.SynthGraph(syn, G(f0), G(param), G(mags), noise=G(noise)).replay())
     if bs % 4:
         assert r is None  # outside the fused envelope
+        with torch.no_grad():
+            two = dd.core.harmonic_synth_params(G(f0), G(param), bs, 48000)
+            two = C(dd.core.filtered_noise(G(mags), bs, noise=G(noise), add=two, raw_bias=syn.initial_bias))
+        assert np.array_equal(path, two) and np.array_equal(graphed, two)
     else:
         out, harm, nz = (C(t) for t in r)
         assert rms(harm, harm_ref) < 1e-6 and rms(nz, noise_ref) < 1e-7, (rms(harm, harm_ref), rms(nz, noise_ref))
         assert rms(out, harm_ref + noise_ref) < 1e-6
     assert rms(path, harm_ref + noise_ref) < 1e-6
+    assert rms(graphed, harm_ref + noise_ref) < 1e-6

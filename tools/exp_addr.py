@@ -25,8 +25,9 @@ def main():
     ptrs = set()
 
     def synth_into(out):
-        _lib.call("synth_frames_controls", _lib.ptr(f0), _lib.ptr(param), H + 1, _lib.ptr(mags), NB, -5.0,
-                  _lib.ptr(None), 0, 0, _lib.ptr(out), _lib.ptr(None), _lib.ptr(None), _lib.ptr(None), B, F, H, NB, bs, float(sr), _lib.stream_of(out))
+        _lib.call("synth_frames_controls_prefix", _lib.ptr(f0), _lib.ptr(param), H + 1, _lib.ptr(mags), NB, -5.0,
+                  _lib.ptr(None), 0, 0, _lib.ptr(out), _lib.ptr(None), _lib.ptr(None), _lib.ptr(None), _lib.ptr(None),
+                  B, F, H, NB, bs, float(sr), _lib.stream_of(out))
 
     def synth_alloc():
         o = core.synth_frames(f0, param, mags, bs, sr)

@@ -7,6 +7,8 @@ Drop-in for hugofloresgarcia/ddsp_pytorch's synthesis hot path:
 * module level — ``ddsp_pytorch_amd.modules``: HarmonicSynth, FilteredNoise, Reverb
   (ddsp/models/modules.py), fused kernels;
 * ``install(ddsp)`` rebinds both inside an imported reference package;
+* analysis — ``core.extract_loudness``, ``core.mfcc`` and ``features.analyze``: the loudness and MFCC
+  features the models consume, from raw audio on the device (ddsp/core.py:81-97, ddsp/preprocess.py:28-32);
 * ``DDSPDecoder`` and ``DDSPAutoencoder`` — the reference's two models (same state_dicts) running
   on these kernels.
 
@@ -18,6 +20,8 @@ from .core import (amp_to_impulse_response, fft_convolve, harmonic_synth, remove
                    scale_function, upsample)
 from .decoder import DDSPDecoder
 from .encoder import DDSPAutoencoder
+from . import features
+from .features import analyze
 from .install import install
 from .modules import FilteredNoise, HarmonicSynth, Reverb
 from . import synth  # noqa: E402  (SynthPath, make_inputs: the bench's and the tests' synthesis-path driver)

@@ -107,6 +107,10 @@ SIGNATURES = {
     "ddsp_hip_stft_magnitude_backward": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _P, _SZ, _P]),
     "ddsp_hip_spectral_loss_workspace_size": (_SZ, [_I64, _I64, _P, _P, _I]),
     "ddsp_hip_spectral_loss": (_I, [_P, _P, _I64, _I64, _P, _P, _I, _P, _P, _P, _SZ, _P]),
+    # audio analysis (loudness, MFCC)
+    "ddsp_hip_loudness": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _P]),
+    "ddsp_hip_mfcc_workspace_size": (_SZ, [_I64, _I64, _I64, _I64, _I64]),
+    "ddsp_hip_mfcc": (_I, [_P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _F, _P, _SZ, _P]),
     # backward
     "ddsp_hip_scale_function_backward": (_I, [_P, _P, _P, _I64, _F, _P]),
     "ddsp_hip_upsample_backward": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P]),

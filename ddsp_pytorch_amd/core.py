@@ -18,6 +18,7 @@ import ctypes
 import itertools
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -27,6 +28,7 @@ __all__ = [
     "amp_to_impulse_response", "fft_convolve", "phase", "harmonic_controls",
     "harmonic_synth_frames", "harmonic_synth_params", "synth_frames", "synth_signal", "filtered_noise", "reverb_build_impulse", "reverb_spectrum_floats",
     "reverb_spectrum", "reverb_impulse_spectrum", "reverb_apply", "reverb_forward", "reverb_cache_bytes", "set_noise_seed", "safe_log", "stft_magnitude", "multiscale_fft",
+    "extract_loudness", "mfcc",
 ]
 
 
@@ -807,6 +809,149 @@ def stft_magnitude(signal, n_fft, hop):
 def multiscale_fft(signal, scales, overlap):
     """ddsp/core.py:27-41: one magnitude spectrogram per scale, hop int(s * (1 - overlap))."""
     return [stft_magnitude(signal, s, int(s * (1 - overlap))) for s in scales]
+
+
+# ------------------------------------------------------------------------------------
+# audio analysis: the features the models consume (ddsp/core.py:81-97, ddsp/preprocess.py:28-32)
+# ------------------------------------------------------------------------------------
+def a_weighting_table(sample_rate, n_fft):
+    """core.py:90-91: librosa.A_weighting(librosa.fft_frequencies(sample_rate, n_fft)) in dB, float64
+    [n_fft/2+1], clipped below at -80 (so the 0 Hz bin is -80)."""
+    f_sq = np.linspace(0.0, float(sample_rate) / 2, 1 + int(n_fft) // 2) ** 2
+    c = np.array([12200.0, 20.6, 107.7, 737.9]) ** 2
+    with np.errstate(divide="ignore"):
+        w = 2.0 + 20.0 * (np.log10(c[0]) + 2 * np.log10(f_sq) - np.log10(f_sq + c[0]) - np.log10(f_sq + c[1])
+                          - 0.5 * np.log10(f_sq + c[2]) - 0.5 * np.log10(f_sq + c[3]))
+    return np.maximum(w, -80.0)
+
+
+def _hz_to_mel(f):
+    """Slaney's scale (librosa's default, htk=False): linear below 1 kHz, logarithmic above."""
+    f = np.asarray(f, dtype=np.float64)
+    f_sp, min_log_hz, logstep = 200.0 / 3, 1000.0, math.log(6.4) / 27.0
+    min_log_mel = min_log_hz / f_sp
+    return np.where(f >= min_log_hz, min_log_mel + np.log(np.maximum(f, min_log_hz) / min_log_hz) / logstep, f / f_sp)
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    f_sp, min_log_hz, logstep = 200.0 / 3, 1000.0, math.log(6.4) / 27.0
+    min_log_mel = min_log_hz / f_sp
+    return np.where(m >= min_log_mel, min_log_hz * np.exp(logstep * (m - min_log_mel)), f_sp * m)
+
+
+def mel_filterbank_table(sample_rate, n_fft, n_mels, fmin, fmax):
+    """librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax, htk=False, norm='slaney'), float64
+    [n_mels, n_fft/2+1]: triangles between n_mels + 2 mel-spaced edges, each row scaled by 2 / its width."""
+    freqs = np.linspace(0.0, float(sample_rate) / 2, 1 + int(n_fft) // 2)
+    edges = _mel_to_hz(np.linspace(_hz_to_mel(float(fmin)), _hz_to_mel(float(fmax)), int(n_mels) + 2))
+    fdiff = np.diff(edges)
+    ramps = edges[:, None] - freqs[None, :]
+    lower = -ramps[:-2] / fdiff[:-1, None]
+    upper = ramps[2:] / fdiff[1:, None]
+    fb = np.maximum(0.0, np.minimum(lower, upper))
+    return fb * (2.0 / (edges[2:] - edges[:-2]))[:, None]
+
+
+def mel_bands(filterbank):
+    """A dense filterbank [n_mels, bins] as ddsp_hip_mfcc takes it: (first bin, count, packed weights) per
+    row — the row's span from its first to its last non-zero bin; an empty row has count 0."""
+    starts, counts, weights = [], [], []
+    for row in np.asarray(filterbank):
+        nz = np.flatnonzero(row)
+        s, c = (int(nz[0]), int(nz[-1] - nz[0] + 1)) if nz.size else (0, 0)
+        starts.append(s)
+        counts.append(c)
+        weights.append(row[s:s + c])
+    packed = np.concatenate(weights) if weights else np.zeros(0)
+    return np.asarray(starts, dtype=np.int32), np.asarray(counts, dtype=np.int32), packed
+
+
+def dct_table(n_mfcc, n_mels):
+    """The first n_mfcc rows of the orthonormal DCT-II of n_mels points (scipy.fftpack.dct(type=2,
+    norm='ortho'), librosa.feature.mfcc's), float64 [n_mfcc, n_mels]."""
+    i = np.arange(int(n_mfcc))[:, None]
+    m = np.arange(int(n_mels))[None, :]
+    t = math.sqrt(2.0 / n_mels) * np.cos(math.pi * i * (2 * m + 1) / (2.0 * n_mels))
+    t[0] = math.sqrt(1.0 / n_mels)
+    return t
+
+
+_FEATURE_TABLES = {}  # (kind, parameters, device) -> device tensors, built on the host once
+
+
+def _feature_tables(kind, params, device, make):
+    key = (kind, params, device.type, device.index if device.index is not None else torch.cuda.current_device())
+    tabs = _FEATURE_TABLES.get(key)
+    if tabs is None:
+        tabs = tuple(torch.from_numpy(np.ascontiguousarray(a if a.dtype == np.int32 else a.astype(np.float32)))
+                     .to(device) for a in make())
+        _FEATURE_TABLES[key] = tabs
+    return tabs
+
+
+def _signal_rows(signal, block_size, name):
+    """signal [T] or [B, T] on a HIP device -> (contiguous detached [B, T], whether it was 1-D)."""
+    _dev(signal)
+    if signal.dim() not in (1, 2):
+        raise RuntimeError(f"{name}: expected audio [time] or [batch, time], got {tuple(signal.shape)}")
+    if int(block_size) < 1:
+        raise RuntimeError(f"{name}: block_size must be positive, got {block_size}")
+    x = signal.detach()
+    return _c(x.unsqueeze(0) if x.dim() == 1 else x), signal.dim() == 1
+
+
+def extract_loudness(signal, sample_rate, block_size, n_fft=2048):
+    """ddsp/core.py:81-97 on the device: signal [T] or [B, T] (HIP, fp32; made contiguous if it is not) ->
+    A-weighted log-magnitude loudness [T // block_size] or [B, T // block_size], one launch, no spectrogram
+    in memory.  The reference's quirk is kept: the natural log of the magnitude plus a weighting in dB.
+    The A-weighting table is built on the host at the first call per (sample_rate, n_fft, device) and cached;
+    later calls do not synchronise with the host (capturable in a HIP graph).  No autograd: an input that
+    requires grad is analysed detached."""
+    x, one_d = _signal_rows(signal, block_size, "extract_loudness")
+    n_fft = int(n_fft)
+    (w,) = _feature_tables("a_weighting", (float(sample_rate), n_fft), x.device,
+                           lambda: (a_weighting_table(sample_rate, n_fft),))
+    B, T = x.shape
+    out = torch.empty(B, T // int(block_size), dtype=torch.float32, device=x.device)
+    _lib.call("loudness", _lib.ptr(x), _lib.ptr(w), _lib.ptr(out), B, T, n_fft, int(block_size), _lib.stream_of(x))
+    return out[0] if one_d else out
+
+
+def mfcc_tables(sample_rate, n_mfcc, n_fft, n_mels, fmin, fmax, device):
+    """(band_start, band_count, band_weights, dct) of ``mfcc`` on ``device``, cached per parameters."""
+    params = (float(sample_rate), int(n_mfcc), int(n_fft), int(n_mels), float(fmin), float(fmax))
+
+    def make():
+        s, c, w = mel_bands(mel_filterbank_table(sample_rate, n_fft, n_mels, fmin, fmax))
+        return s, c, w, dct_table(n_mfcc, n_mels)
+    return _feature_tables("mfcc", params, torch.device(device), make)
+
+
+def mfcc(signal, sample_rate, block_size, n_mfcc=30, n_fft=1024, n_mels=128, fmin=20.0, fmax=8000.0, top_db=80.0,
+         return_db=False):
+    """ddsp/preprocess.py:30-32 on the device: ``librosa.feature.mfcc(x, sr, n_mfcc, n_fft, hop_length=
+    block_size, fmin, fmax, n_mels).T`` with librosa's defaults behind it (Slaney mel filterbank, power
+    spectrogram, 10 log10 with amin 1e-10 and ref 1, top_db per item, orthonormal DCT-II).  signal [T] or
+    [B, T] (HIP, fp32) -> [1 + T // block_size, n_mfcc] or [B, 1 + T // block_size, n_mfcc]; two launches,
+    no spectrogram in memory.  ``return_db``: also the mel spectrogram in dB before the clamp,
+    [B, frames, n_mels].  Tables: built on the host at the first call per (parameters, device) and cached;
+    later calls do not synchronise with the host.  No autograd: an input that requires grad is analysed
+    detached."""
+    x, one_d = _signal_rows(signal, block_size, "mfcc")
+    band_start, band_count, band_weights, dct = mfcc_tables(sample_rate, n_mfcc, n_fft, n_mels, fmin, fmax, x.device)
+    B, T = x.shape
+    n_fft, hop, n_mels, n_mfcc = int(n_fft), int(block_size), int(n_mels), int(n_mfcc)
+    frames = T // hop + 1
+    out = torch.empty(B, frames, n_mfcc, dtype=torch.float32, device=x.device)
+    ws = _workspace(_lib.query("mfcc_workspace_size", B, T, n_fft, hop, n_mels), x.device)
+    _lib.call("mfcc", _lib.ptr(x), _lib.ptr(band_start), _lib.ptr(band_count), _lib.ptr(band_weights),
+              band_weights.numel(), _lib.ptr(dct), _lib.ptr(out), B, T, n_fft, hop, n_mels, n_mfcc, float(top_db),
+              _lib.ptr(ws), ws.numel(), _lib.stream_of(x))
+    db = ws[:4 * B * frames * n_mels].view(torch.float32).view(B, frames, n_mels)  # D before the clamp
+    if one_d:
+        out, db = out[0], db[0]
+    return (out, db) if return_db else out
 
 
 def _reverb_apply_launch(x, spectrum, ir_length):

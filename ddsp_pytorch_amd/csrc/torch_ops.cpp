@@ -400,6 +400,54 @@ void stream_advance(const at::Tensor& f0, int64_t block_size, double sample_rate
      "stream_advance");
 }
 
+// ---------------- audio analysis (ddsp/core.py:81-97, ddsp/preprocess.py:30-32) ----------------
+// x [T] or [B, T] -> the rows [B, T] contiguous (an exported host feeds audio as it has it)
+at::Tensor audio_rows(const at::Tensor& x, const char* op) {
+  check_dev(x, "x");
+  TORCH_CHECK(x.dim() == 1 || x.dim() == 2, op, ": x [time] or [batch, time] expected");
+  return c16(x.dim() == 1 ? x.unsqueeze(0) : x);
+}
+
+at::Tensor loudness(const at::Tensor& x, const std::optional<at::Tensor>& weights, int64_t n_fft, int64_t hop) {
+  at::Tensor xc = audio_rows(x, "loudness");  // core.py:81-97 extract_loudness
+  TORCH_CHECK(hop >= 1, "loudness: hop must be positive");
+  const int64_t B = xc.size(0), T = xc.size(1);
+  at::Tensor w;
+  if (weights.has_value() && weights->defined()) {
+    check_dev(*weights, "weights");
+    TORCH_CHECK(weights->numel() == n_fft / 2 + 1, "loudness: weights must hold n_fft/2+1 values");
+    w = weights->contiguous();
+  }
+  at::Tensor out = at::empty({B, T / hop}, xc.options());
+  ok(ddsp_hip_loudness(xc.data_ptr<float>(), w.defined() ? w.data_ptr<float>() : nullptr, out.data_ptr<float>(), B, T,
+                       n_fft, hop, stream_of(xc)),
+     "loudness");
+  return x.dim() == 1 ? out.select(0, 0) : out;
+}
+
+at::Tensor mfcc(const at::Tensor& x, const at::Tensor& band_start, const at::Tensor& band_count,
+                const at::Tensor& band_weights, const at::Tensor& dct, int64_t n_fft, int64_t hop, double top_db) {
+  at::Tensor xc = audio_rows(x, "mfcc");  // preprocess.py:30-32 librosa.feature.mfcc(...).T
+  check_dev(band_weights, "band_weights");
+  check_dev(dct, "dct");
+  TORCH_CHECK(hop >= 1, "mfcc: hop must be positive");
+  TORCH_CHECK(dct.dim() == 2, "mfcc: dct [n_mfcc, n_mels] expected");
+  const int64_t B = xc.size(0), T = xc.size(1), n_mfcc = dct.size(0), n_mels = dct.size(1);
+  for (const at::Tensor* t : {&band_start, &band_count})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->numel() == n_mels,
+                "mfcc: band_start and band_count must be int32 HIP tensors of n_mels values");
+  at::Tensor bs = band_start.contiguous(), bc = band_count.contiguous(), bw = band_weights.contiguous(),
+             d = dct.contiguous();
+  const int64_t frames = T / hop + 1;
+  at::Tensor out = at::empty({B, frames, n_mfcc}, xc.options());
+  at::Tensor ws = workspace(ddsp_hip_mfcc_workspace_size(B, T, n_fft, hop, n_mels), xc);
+  ok(ddsp_hip_mfcc(xc.data_ptr<float>(), bs.data_ptr<int32_t>(), bc.data_ptr<int32_t>(), bw.data_ptr<float>(),
+                   bw.numel(), d.data_ptr<float>(), out.data_ptr<float>(), B, T, n_fft, hop, n_mels, n_mfcc,
+                   (float)top_db, ws.data_ptr(), (size_t)ws.numel(), stream_of(xc)),
+     "mfcc");
+  return x.dim() == 1 ? out.select(0, 0) : out;
+}
+
 }  // namespace
 
 // ---------------- decoder.py:33-68: the GRU recurrence ----------------
@@ -455,6 +503,9 @@ TORCH_LIBRARY(ddsp_hip, m) {
   m.def("stream_advance(Tensor f0, int block_size, float sample_rate, Tensor(a!) counter, Tensor(b!) state,"
         " bool wrap=True) -> ()");
   m.def("gru(Tensor x, Tensor w_ih, Tensor w_hh, Tensor b_ih, Tensor b_hh, Tensor? h0=None) -> (Tensor, Tensor)");
+  m.def("loudness(Tensor x, Tensor? weights, int n_fft, int hop) -> Tensor");
+  m.def("mfcc(Tensor x, Tensor band_start, Tensor band_count, Tensor band_weights, Tensor dct, int n_fft, int hop,"
+        " float top_db) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA key on ROCm
@@ -478,4 +529,6 @@ TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA 
   m.impl("reverb_stream", &reverb_stream);
   m.impl("stream_advance", &stream_advance);
   m.impl("gru", &gru);
+  m.impl("loudness", &loudness);
+  m.impl("mfcc", &mfcc);
 }

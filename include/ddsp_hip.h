@@ -422,6 +422,43 @@ int ddsp_hip_spectral_loss(const float* target, const float* recon, int64_t batc
                            const int64_t* n_ffts, const int64_t* hops, int n_scales, float* loss, float* grad_recon,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------- audio analysis: the features the models consume, from raw audio ----------------
+ * Both take x[batch, n_samples] and librosa.stft's frames: centred (reflect padding by n_fft/2, frame f
+ * centred at f * hop), periodic Hann(n_fft), an UNNORMALISED FFT (ddsp_hip_stft_magnitude scales by
+ * n_fft^-1/2; these do not), computed in fp64 from the fp32 input (the features take logs of single bins; inputs,
+ * tables, logs and outputs are fp32).  No spectrogram is written; every reduction has a fixed order (no atomics), so
+ * the results are bit-reproducible and independent of the batch around an item.
+ * Envelope, checked before any HIP call: n_fft a power of two in [16, 4096] (else DDSP_HIP_ERANGE),
+ * n_samples > n_fft/2 (else DDSP_HIP_EINVAL), hop >= 1 (any value: not a power of two, n_samples % hop != 0),
+ * batch <= 65535 (else DDSP_HIP_ERANGE), and for the MFCC 1 <= n_mfcc <= n_mels (else DDSP_HIP_EINVAL),
+ * n_mels <= 256 (else DDSP_HIP_ERANGE), top_db >= 0.  Null pointers and negative sizes: DDSP_HIP_EINVAL;
+ * batch == 0: a no-op success; a short workspace: DDSP_HIP_EWORKSPACE. */
+
+/* ddsp/core.py:81-97  extract_loudness(signal, sample_rate, block_size = hop, n_fft):
+ * out[b, f] = mean over k = 0..n_fft/2 of (ln(|X[b,f,k]| + 1e-7) + weights[k]), f = 0 .. n_samples/hop - 1
+ * (core.py:95 drops the last of librosa's 1 + n_samples/hop frames; it is not computed).  weights: the
+ * caller's additive table of n_fft/2+1 floats (core.py:90-93: librosa.A_weighting of the bin frequencies, in
+ * dB, added to the NATURAL log as the reference does); NULL = zeros.  out [batch, n_samples/hop]. */
+int ddsp_hip_loudness(const float* x, const float* weights, float* out, int64_t batch, int64_t n_samples,
+                      int64_t n_fft, int64_t hop, void* stream);
+
+/* ddsp/preprocess.py:30-32  librosa.feature.mfcc(x, sr, n_mfcc, n_fft, hop_length, fmin, fmax, n_mels).T:
+ * per frame the power |X_k|^2, the mel energies M[m] = sum_k fb[m,k] |X_k|^2, D[m] = 10 log10(max(1e-10, M[m]));
+ * per item D <- max(D, max(D) - top_db) (librosa.power_to_db, ref = 1); then the DCT
+ * out[b, f, i] = sum_m dct[i, m] D[b, f, m], i < n_mfcc — out [batch, frames, n_mfcc] with all
+ * frames = n_samples/hop + 1 (ddsp/data.py:25 drops the last one later).
+ * The filterbank comes as one band of bins per mel row: row m weighs bins band_start[m] ..
+ * band_start[m] + band_count[m] - 1 with band_weights[o_m ..], o_m = band_count[0] + .. + band_count[m-1]
+ * (n_band_weights floats in all; a band that would leave the spectrum or the array is cut there).  dct: the
+ * caller's table [n_mfcc, n_mels] (librosa: orthonormal DCT-II).  Two launches (the clamp needs the item's
+ * maximum).  Workspace: ddsp_hip_mfcc_workspace_size bytes (0 for sizes outside the envelope); after the call
+ * its first batch * frames * n_mels floats hold D before the clamp, [batch, frames, n_mels]. */
+size_t ddsp_hip_mfcc_workspace_size(int64_t batch, int64_t n_samples, int64_t n_fft, int64_t hop, int64_t n_mels);
+int ddsp_hip_mfcc(const float* x, const int32_t* band_start, const int32_t* band_count, const float* band_weights,
+                  int64_t n_band_weights, const float* dct, float* out, int64_t batch, int64_t n_samples,
+                  int64_t n_fft, int64_t hop, int64_t n_mels, int64_t n_mfcc, float top_db, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 /* ---------------- backward (training): train.py:84-130 back-propagates through the path ----------------
  * Vector-Jacobian products of the entry points above.  `grad*` inputs are the upstream
  * gradients (same shapes as the forward outputs), `grad_*` outputs are caller-allocated and

@@ -1,0 +1,102 @@
+"""Times the analysis front end (core.extract_loudness, core.mfcc, features.analyze: csrc/features.hip) on the
+GPU, beside what a user would write today on the same GPU: torch.stft plus the same tables as dense ATen ops.
+
+Shapes: the training shape of the reference's config.yaml (16 items x 192,000 samples, block 512, 48 kHz) and
+config 2's (64 x 102,400).  Each figure is the median over `--windows` event-timed windows of `--reps` calls,
+after a warm-up of every timed callable.  Beside each time: the bytes the algorithm needs (x read once, the
+features written, and for the MFCC the D workspace written and read back) and the rate they make.  Prints one
+JSON line per (shape, leg); DESIGN.md 3f records a run.  Needs a HIP device: there is no CPU path.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ddsp_pytorch_amd as dd  # noqa: E402
+from ddsp_pytorch_amd import core  # noqa: E402
+
+SHAPES = [("train 16x192000", 16, 192000, 512, 48000), ("config2 64x102400", 64, 102400, 512, 48000)]
+
+
+def torch_loudness(x, w, n_fft, hop):
+    """core.py:81-97 as torch ops: a full complex spectrogram and its log go through memory."""
+    S = torch.stft(x, n_fft, hop, n_fft, torch.hann_window(n_fft, device=x.device), center=True, pad_mode="reflect",
+                   return_complex=True).abs()
+    return (torch.log(S + 1e-7) + w[None, :, None]).mean(1)[..., :-1]
+
+
+def torch_mfcc(x, fb, dct, n_fft, hop, top_db=80.0):
+    """preprocess.py:30-32 as torch ops with the dense filterbank and DCT as matmuls."""
+    P = torch.stft(x, n_fft, hop, n_fft, torch.hann_window(n_fft, device=x.device), center=True, pad_mode="reflect",
+                   return_complex=True).abs() ** 2
+    D = 10.0 * torch.log10(torch.clamp(fb @ P, min=1e-10))
+    D = torch.maximum(D, D.amax(dim=(1, 2), keepdim=True) - top_db)
+    return (dct @ D).transpose(1, 2)
+
+
+def timed(fn, reps, windows):
+    """Median milliseconds per call over `windows` event-timed windows of `reps` calls."""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(windows):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b) / reps)
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--reps", type=int, default=1000)
+    ap.add_argument("--windows", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_features: needs a HIP device (there is no CPU path)")
+    dev = torch.device("cuda", 0)
+    for name, B, T, hop, sr in SHAPES:
+        g = torch.Generator().manual_seed(B + T)
+        t = torch.arange(T) / sr
+        x = (0.3 * torch.sin(2 * torch.pi * 220.0 * t) + 0.1 * torch.sin(2 * torch.pi * 1760.0 * t))[None, :] \
+            * torch.linspace(1.0, 0.05, T)[None, :] + 0.01 * torch.randn(B, T, generator=g)
+        x = x.to(dev)
+        F = T // hop
+        pitch = torch.full((B, F, 1), 220.0, device=dev)
+        w = torch.from_numpy(core.a_weighting_table(sr, 2048)).float().to(dev)
+        fb = torch.from_numpy(core.mel_filterbank_table(sr, 1024, 128, 20.0, 8000.0)).float().to(dev)
+        dct = torch.from_numpy(core.dct_table(30, 128)).float().to(dev)
+        n_w = int(core.mfcc_tables(sr, 30, 1024, 128, 20.0, 8000.0, dev)[2].numel())
+        loud_bytes = 4 * (B * T + B * F + 1025)
+        mfcc_bytes = 4 * (B * T + 2 * B * (F + 1) * 128 + B * (F + 1) * 30 + n_w + 30 * 128)
+        legs = [
+            ("loudness hip", lambda: core.extract_loudness(x, sr, hop), loud_bytes),
+            ("loudness torch.stft", lambda: torch_loudness(x, w, 2048, hop), None),
+            ("mfcc hip", lambda: core.mfcc(x, sr, hop), mfcc_bytes),
+            ("mfcc torch.stft", lambda: torch_mfcc(x, fb, dct, 1024, hop), None),
+            ("analyze hip", lambda: dd.features.analyze(x, pitch, sr, hop), loud_bytes + mfcc_bytes),
+            ("analyze torch.stft", lambda: (torch_loudness(x, w, 2048, hop), torch_mfcc(x, fb, dct, 1024, hop)), None),
+        ]
+        # the two routes compute the same features (fp32 FFTs of different structure)
+        dl = float((core.extract_loudness(x, sr, hop) - torch_loudness(x, w, 2048, hop)).abs().max())
+        dm = float((core.mfcc(x, sr, hop) - torch_mfcc(x, fb, dct, 1024, hop)).abs().max())
+        print(json.dumps({"shape": name, "max_abs_diff_loudness": dl, "max_abs_diff_mfcc": dm}), flush=True)
+        for leg, fn, nbytes in legs:
+            med, lo, hi = timed(fn, args.reps, args.windows)
+            row = {"shape": name, "leg": leg, "ms": round(med, 4), "ms_min": round(lo, 4), "ms_max": round(hi, 4)}
+            if nbytes is not None:
+                row["algorithmic_bytes"] = nbytes
+                row["GB_per_s"] = round(nbytes / (med * 1e-3) / 1e9, 1)
+            print(json.dumps(row), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -555,47 +555,84 @@ def gru(x, gru_module, h0=None, persistent_flags=0):
     params = (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)
     if _wants_grad(x, h0, *params):
         return _grad.GRUFn.apply(x, *params, h0)
-    B, T, _ = x.shape
-    H = g.hidden_size
+    out, h_last, h0c = gru_buffers(x, g.hidden_size, h0)
     w_ih, w_hh, b_ih, b_hh = params
-    out = torch.empty(B, T, H, dtype=torch.float32, device=x.device)
-    h_last = torch.empty(1, B, H, dtype=torch.float32, device=x.device)
-    h0c = _c(h0.reshape(B, H)) if h0 is not None else None
     gru_layer_launch(x, w_ih, b_ih, w_hh, b_hh, h0c, out, h_last, None, persistent_flags)
     return out, h_last
+
+
+def gru_buffers(x, H, h0):
+    """One layer call's outputs and initial state as the kernels take them: out [B, T, H], h_T [1, B, H],
+    h0 as contiguous [B, H] (or None)."""
+    B, T = x.shape[:2]
+    out = torch.empty(B, T, H, dtype=torch.float32, device=x.device)
+    h_last = torch.empty(1, B, H, dtype=torch.float32, device=x.device)
+    return out, h_last, (_c(h0.reshape(B, H)) if h0 is not None else None)
 
 
 # include/ddsp_hip.h: ddsp_hip_gru_forward_persistent's flags (test hooks) and status bits
 GRU_SPREAD, GRU_NO_MASK_CHECK, GRU_FORCE_ABORT = 1, 2, 4
 GRU_STATUS_LOCAL, GRU_STATUS_RESCUED = 1, 2
-_GRU_LAST = {}  # device index -> (route, persistent workspace or None) of the last gru_layer_launch
+_GRU_LAST = {}  # device index -> (route, persistent workspace or None) of the last GRU launch (_gru_ran)
+
+
+def _gru_ran(device, route, ws=None):
+    """Record the route of the launch just made on ``device`` for gru_last_route; returns it."""
+    dev = device.index if device.index is not None else torch.cuda.current_device()
+    _GRU_LAST[dev] = (route, ws)
+    return route
 
 
 def gru_layer_launch(x, w_ih, b_ih, w_hh, b_hh, h0c, out, h_last, gates, persistent_flags=0):
     """The layer's forward on the device: the input projection for every step as one GEMM, then the
-    recurrence as one persistent launch (ddsp_hip_gru_forward_persistent: hidden 512, batch <= 64, a stream
-    that may use every CU) or on ddsp_hip_gru_forward's step kernels (a form with each step's projection
-    inside the step launch measured slower: 13.3 vs 7.4-7.8 us per step).  A persistent launch
-    that cannot get its workgroups resident aborts and its outputs are recomputed, on the same stream, with
-    the step kernels' arithmetic (gru_rescue_kernel): the values are right on every route;
-    ``gru_last_route`` tells which one ran.  Returns the route taken ("persistent" or "steps")."""
+    recurrence (gru_recurrence; a form with each step's projection inside the step launch measured slower:
+    13.3 vs 7.4-7.8 us per step).  Returns the route taken ("persistent" or "steps")."""
     B, T, I = x.shape
-    H = w_hh.shape[1]
-    xp = linear(_c(x).reshape(B * T, I), w_ih, b_ih).view(B, T, 3 * H)
-    args = (_lib.ptr(xp), _lib.ptr(_c(w_hh)), _lib.ptr(_c(b_hh)), _lib.ptr(h0c), _lib.ptr(out), _lib.ptr(h_last),
-            _lib.ptr(gates), B, T, H)
-    # hidden 512, batch <= 64: the whole recurrence as one persistent launch (W_hh resident in registers, h
-    # handed between the workgroups of a group); otherwise (ERANGE) one launch per step
+    xp = linear(_c(x).reshape(B * T, I), w_ih, b_ih).view(B, T, 3 * w_hh.shape[1])
+    return gru_recurrence(xp, w_hh, b_hh, h0c, out, h_last, gates, persistent_flags)
+
+
+def gru_recurrence(xp, w_hh, b_hh, h0, out, h_last, gates=None, persistent_flags=0, ws=None, persistent=True,
+                   h_last_steps=None):
+    """The recurrence over the projected inputs xp [B, T, 3H] into out [B, T, H] and h_T: one persistent launch
+    (ddsp_hip_gru_forward_persistent: hidden 512, batch <= 64, a stream that may use every CU; W_hh resident
+    in registers, h handed between the workgroups of a group), else (ERANGE, or ``persistent=False``: no
+    attempt) ddsp_hip_gru_forward's one launch per step.  A persistent launch that cannot get its workgroups
+    resident aborts and its outputs are recomputed, on the same stream, with the step kernels' arithmetic
+    (gru_rescue_kernel): the values are right on every route; ``gru_last_route`` tells which one ran.
+    ``ws``: the persistent launch's workspace where the caller keeps one alive (a captured graph).
+    ``h_last_steps``: where the step kernels write h_T if not ``h_last`` — they may write over h0, the
+    persistent launch may not (its rescue re-reads h0).  Returns the route taken ("persistent" or "steps")."""
+    B, T, H = out.shape
+    args = (_lib.ptr(xp), _lib.ptr(_c(w_hh)), _lib.ptr(_c(b_hh)), _lib.ptr(h0), _lib.ptr(out))
+    dims = (_lib.ptr(gates), B, T, H)
+    if persistent:
+        if ws is None:
+            ws = _workspace(_lib.query("gru_persistent_workspace_size"), out.device)
+        st = _lib.call("gru_forward_persistent", *args, _lib.ptr(h_last), *dims, int(persistent_flags), _lib.ptr(ws),
+                       ws.numel(), _lib.stream_of(out), allow=(ERANGE,))
+        if st != ERANGE:
+            return _gru_ran(out.device, "persistent", ws)
+    _lib.call("gru_forward", *args, _lib.ptr(h_last if h_last_steps is None else h_last_steps), *dims,
+              _lib.stream_of(out))
+    return _gru_ran(out.device, "steps")
+
+
+def gru_backward_launch(w_hh, gates, out, h0, g_out, g_hlast, dxp, dgn, dh0, persistent_flags=0):
+    """The layer's BPTT from the forward's saved gate planes into dxp [B, T, 3H], dgn [B, T, H] and dh0: one
+    persistent launch (hidden 512, batch <= 64), else (ERANGE) ddsp_hip_gru_backward's one launch per step.
+    ``persistent_flags``: the persistent launch's test hooks.  Returns the route taken."""
+    B, T, H = out.shape
+    args = (_lib.ptr(_c(w_hh)), _lib.ptr(gates), _lib.ptr(out), _lib.ptr(h0), _lib.ptr(g_out), _lib.ptr(g_hlast),
+            _lib.ptr(dxp), _lib.ptr(dgn), _lib.ptr(dh0), B, T, H)
     ws = _workspace(_lib.query("gru_persistent_workspace_size"), out.device)
-    st = _lib.call("gru_forward_persistent", *args, int(persistent_flags), _lib.ptr(ws), ws.numel(),
-                   _lib.stream_of(out), allow=(ERANGE,))
-    dev = out.device.index if out.device.index is not None else torch.cuda.current_device()
-    if st == ERANGE:
-        _lib.call("gru_forward", *args, _lib.stream_of(out))
-        _GRU_LAST[dev] = ("steps", None)
-        return "steps"
-    _GRU_LAST[dev] = ("persistent", ws)
-    return "persistent"
+    st = _lib.call("gru_backward_persistent", *args, int(persistent_flags), _lib.ptr(ws), ws.numel(),
+                   _lib.stream_of(dxp), allow=(ERANGE,))
+    if st != ERANGE:
+        return _gru_ran(out.device, "persistent", ws)
+    ws = _workspace(_lib.query("gru_backward_workspace_size", B, H), out.device)
+    _lib.call("gru_backward", *args, _lib.ptr(ws), ws.numel(), _lib.stream_of(dxp))
+    return _gru_ran(out.device, "steps")
 
 
 def gru_last_route(device=None):
@@ -617,8 +654,8 @@ def gru_last_route(device=None):
 
 def linear(x, weight, bias):
     """x [rows, in] @ weight[out, in]^T + bias -> [rows, out] (no autograd): ddsp_hip_linear — the bf16 matrix
-    cores with the fp32-accurate three-term split — where it applies (in 512 / 1024, out a multiple of 512),
-    else torch.addmm (hipBLASLt)."""
+    cores with the fp32-accurate three-term split — where it applies (in 512 / 1024 / 1536, out a multiple of
+    512: dense.hip:1312), else torch.addmm (hipBLASLt)."""
     _dev(x, weight, bias)
     rows, K = x.shape
     N = weight.shape[0]
@@ -627,6 +664,13 @@ def linear(x, weight, bias):
     st = _lib.call("linear", _lib.ptr(xc), K, K, _lib.ptr(wc), K, _lib.ptr(bc), _lib.ptr(y), N, rows, N,
                    _lib.stream_of(y), allow=(ERANGE,))
     return torch.addmm(bias, x, weight.t()) if st == ERANGE else y
+
+
+def linear_input_grad(grad_y, weight):
+    """grad_y [rows, out] @ weight [out, in] -> [rows, in], a Linear's input gradient (no autograd): ``linear``
+    with W^T as its weight and a zero bias."""
+    wt = weight.t().contiguous()
+    return linear(grad_y, wt, torch.zeros(wt.shape[0], dtype=wt.dtype, device=wt.device))
 
 
 def linear_weight_grad(grad_y, x):
@@ -654,6 +698,23 @@ def _row_strided(out, shape):
             all(out.stride(i) == out.stride(i + 1) * out.shape[i + 1] for i in range(out.dim() - 2)))
 
 
+def _out_rows(out, lead, cols, device):
+    """Where a kernel writes its [*lead, cols] result -> (buffer, row stride): a fresh buffer, or the caller's
+    ``out`` if the kernel can address it (_row_strided), else (None, 0)."""
+    if out is None:
+        out = torch.empty(*lead, cols, dtype=torch.float32, device=device)
+    elif not _row_strided(out, tuple(lead) + (cols,)):
+        return None, 0
+    return out, (out.stride(-2) if out.dim() >= 2 else cols)
+
+
+# Below one K chunk of the matrix-core kernels (16 wide: k = 16 h + ..., dense.hip:363, 552) a block's Linear has no
+# work for them: the decoder keeps the K = 1 Linear in the LayerNorm kernel (or torch's, under autograd) and runs
+# mlp_block / grad.LinearFn from here up.  A policy of the callers, not an envelope: ddsp_hip_mlp_block itself takes
+# any K >= 1 (dense.hip:1270).
+MLP_MATRIX_MIN_IN = 16
+
+
 def mlp_block(x, linear, norm, act, out=None, extras=(), flags=0):
     """ddsp/core.py:122-129, one whole block: LeakyReLU(LayerNorm(linear(x))) in one launch
     (ddsp_hip_mlp_block: the Linear on the matrix cores — at 512 inputs fp32-accurate bf16x3 products,
@@ -669,13 +730,10 @@ def mlp_block(x, linear, norm, act, out=None, extras=(), flags=0):
             or any(e.shape != x.shape[:-1] + (1,) for e in extras)):
         return None
     xc = _c(x)
-    lead = tuple(x.shape[:-1])
     rows = xc.numel() // K if K else 0
+    out, y_ld = _out_rows(out, x.shape[:-1], n_out, x.device)
     if out is None:
-        out = torch.empty(*lead, n_out, dtype=torch.float32, device=x.device)
-    elif not _row_strided(out, lead + (n_out,)):
         return None
-    y_ld = out.stride(-2) if out.dim() >= 2 else n_out
     ec = [_c(e) for e in extras]
     st = _lib.call("mlp_block", _lib.ptr(xc), K, K, _lib.ptr(_c(linear.weight)), n_in, _lib.ptr(_c(linear.bias)),
                    _lib.ptr(ec[0] if ec else None), _lib.ptr(ec[1] if len(ec) > 1 else None), 1,
@@ -693,14 +751,9 @@ def projections(x, lin1, lin2, pad_to=64):
     outputs as column slices of one [..., n] result.  Nothing is cached on the modules."""
     _dev(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias)
     n1, n2, K = lin1.out_features, lin2.out_features, x.shape[-1]
-    xc, w1, w2 = _c(x), _c(lin1.weight), _c(lin2.weight)
-    rows = xc.numel() // K if K else 0
-    n4 = -(-(n1 + n2) // 4) * 4  # row stride of the result: 16-byte aligned rows
-    y = torch.empty(*x.shape[:-1], n4, dtype=torch.float32, device=x.device)
-    st = _lib.call("projections", _lib.ptr(xc), K, K, _lib.ptr(w1), w1.stride(0), _lib.ptr(_c(lin1.bias)), n1,
-                   _lib.ptr(w2), w2.stride(0), _lib.ptr(_c(lin2.bias)), n2, _lib.ptr(y), n4, rows,
-                   _lib.stream_of(y), allow=(ERANGE,))
-    if st != ERANGE:
+    w1, w2 = _c(lin1.weight), _c(lin2.weight)
+    y, launched = projections_launch(_c(x), w1, lin1.bias, w2, lin2.bias)
+    if launched:
         return y[..., :n1], y[..., n1:n1 + n2]
     n_pad = -(-(n1 + n2) // pad_to) * pad_to
     w = torch.empty(n_pad, K, dtype=torch.float32, device=x.device)
@@ -711,6 +764,22 @@ def projections(x, lin1, lin2, pad_to=64):
     return y[..., :n1], y[..., n1:n1 + n2]
 
 
+def projections_launch(x, w1, b1, w2, b2):
+    """ddsp_hip_projections over x [..., K] and the two layers' parameters, all contiguous (_c) -> (y [..., n4],
+    launched): both outputs side by side in rows of n4 floats, n1 + n2 rounded up to 4 (16-byte aligned rows).
+    ``launched`` False: outside the kernel's shapes (dense.hip:1343), y is not written."""
+    n1, n2, K = w1.shape[0], w2.shape[0], x.shape[-1]
+    n4 = -(-(n1 + n2) // 4) * 4
+    y = torch.empty(*x.shape[:-1], n4, dtype=torch.float32, device=x.device)
+    st = _lib.call("projections", _lib.ptr(x), K, K, _lib.ptr(w1), K, _lib.ptr(_c(b1)), n1, _lib.ptr(w2), K,
+                   _lib.ptr(_c(b2)), n2, _lib.ptr(y), n4, x.numel() // K if K else 0, _lib.stream_of(y),
+                   allow=(ERANGE,))
+    return y, st != ERANGE
+
+
+LN_LEAKY_COLS = (512, 1024)  # the widths ddsp_hip_layer_norm_leaky_relu and its backward take (dense.hip:1216, 1248)
+
+
 def layer_norm_leaky_relu(h, norm, act, out=None, w1=None, b1=None):
     """ddsp/core.py:122-129 after one block's Linear: LeakyReLU(LayerNorm(h)) in one pass
     (ddsp_hip_layer_norm_leaky_relu).  h [..., cols] contiguous; or, with w1/b1 (a Linear with one input
@@ -718,24 +787,29 @@ def layer_norm_leaky_relu(h, norm, act, out=None, w1=None, b1=None):
     (optional) may be a column slice of a wider buffer with one row stride.  Returns None where the
     kernel does not apply (the caller runs torch's modules); inference only."""
     _dev(h, norm.weight, norm.bias)
-    cols = int(norm.normalized_shape[-1])
-    if len(norm.normalized_shape) != 1 or (w1 is None and h.shape[-1] != cols) or (w1 is not None and h.shape[-1] != 1):
+    if len(norm.normalized_shape) != 1:
+        return None
+    return ln_leaky_launch(h, norm.weight, norm.bias, norm.eps, act.negative_slope, out, w1, b1)
+
+
+def ln_leaky_launch(h, gamma, beta, eps, slope, out=None, w1=None, b1=None):
+    """layer_norm_leaky_relu on the affine parameters themselves (grad.LNLeakyFn has no modules): None where the
+    kernel does not apply — shapes that do not fit gamma, an ``out`` it cannot address, ERANGE (widths outside
+    LN_LEAKY_COLS, unaligned rows)."""
+    cols = gamma.shape[0]
+    if h.shape[-1] != (cols if w1 is None else 1):
         return None
     if not h.is_contiguous():
         h = h.contiguous()
-    lead = tuple(h.shape[:-1])
     rows = h.numel() // h.shape[-1] if h.shape[-1] else 0
+    out, y_ld = _out_rows(out, h.shape[:-1], cols, h.device)
     if out is None:
-        out = torch.empty(*lead, cols, dtype=torch.float32, device=h.device)
-    elif not _row_strided(out, lead + (cols,)):
         return None
-    y_ld = out.stride(-2) if out.dim() >= 2 else cols
-    g, b = _c(norm.weight), _c(norm.bias)
     w1c = _c(w1) if w1 is not None else None
     b1c = _c(b1) if b1 is not None else None
-    st = _lib.call("layer_norm_leaky_relu", _lib.ptr(h), int(h.shape[-1]), _lib.ptr(w1c), _lib.ptr(b1c), _lib.ptr(g),
-                   _lib.ptr(b), float(norm.eps), float(act.negative_slope), _lib.ptr(out), int(y_ld), int(rows), cols,
-                   _lib.stream_of(out), allow=(ERANGE,))
+    st = _lib.call("layer_norm_leaky_relu", _lib.ptr(h), int(h.shape[-1]), _lib.ptr(w1c), _lib.ptr(b1c),
+                   _lib.ptr(_c(gamma)), _lib.ptr(_c(beta)), float(eps), float(slope), _lib.ptr(out), int(y_ld),
+                   int(rows), cols, _lib.stream_of(out), allow=(ERANGE,))
     return None if st == ERANGE else out
 
 

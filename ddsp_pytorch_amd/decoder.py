@@ -12,11 +12,17 @@ and weight gradient on the matrix-core kernels (grad.LinearFn), their LayerNorm 
 backward on this package's kernels (grad.LNLeakyFn), the projections one grad.ProjectionsFn (forward in one
 matrix-core launch, weight gradient on the matrix cores), and the GRU's BPTT is one persistent
 launch with its weight gradients on the matrix cores.
+
+Which of these a call takes is decided in one place per layer: ``mlp_route`` once per MLP and forward
+("kernels", "autograd" or "modules"), ``_gru`` for the recurrence, ``decoder_projections`` for the two
+projections.  They share two questions: is somebody observing the modules (``_observed``: then the module
+calls stay), and must autograd record the call (``core._wants_grad``).  A kernel's shapes are named beside
+its wrapper in ``core`` (MLP_MATRIX_MIN_IN, LN_LEAKY_COLS) or answered by the launch itself (ERANGE).
 """
 import torch
 import torch.nn as nn
 
-from . import core
+from . import core, grad
 from .modules import NOISE_MODES, FilteredNoise, HarmonicSynth, Reverb
 
 
@@ -56,107 +62,127 @@ def _gru(mod, hidden, h0):
     return mod.gru(hidden, h0) if h0 is not None else mod.gru(hidden)
 
 
-def _mlp_fusable(seq, x):
-    """An unobserved (Linear, LayerNorm, LeakyReLU) x n block chain (ddsp/core.py:122-129) on the GPU at
-    inference (see _mlp_plain); the LayerNorm + LeakyReLU pairs may run as one kernel."""
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in seq.parameters())):
-        return False
-    return _mlp_plain(seq, x)
-
-
-def _mlp_plain(seq, x):
-    """An unobserved (Linear, LayerNorm, LeakyReLU) x n block chain (ddsp/core.py:122-129) in fp32 on the GPU:
-    no module or global hooks, the plain torch classes, affine LayerNorms, Linears with biases."""
+def _observed(*mods):
+    """Somebody watches these module calls: forward (pre-)hooks on one of them or registered globally.  Such a
+    call stays a module call."""
     from torch.nn.modules import module as _m
-    if not x.is_cuda:
-        return False
-    if _m._global_forward_hooks or _m._global_forward_pre_hooks or seq._forward_hooks or seq._forward_pre_hooks:
-        return False
-    if type(seq) is not nn.Sequential or type(seq).forward is not nn.Sequential.forward:
-        return False
-    if not _fp32_inference_ok(x, (seq,)):
-        return False
+    return bool(_m._global_forward_hooks or _m._global_forward_pre_hooks or
+                any(m._forward_hooks or m._forward_pre_hooks for m in mods))
+
+
+def _blocks(seq):
+    """The (Linear, LayerNorm, LeakyReLU) triples of a ddsp/core.py:122-129 chain."""
     mods = list(seq)
-    if len(mods) % 3:
-        return False
-    for i in range(0, len(mods), 3):
-        lin, ln, act = mods[i:i + 3]
+    return [mods[i:i + 3] for i in range(0, len(mods), 3)]
+
+
+def _mlp_params(seq):
+    """The parameters of an unobserved (Linear, LayerNorm, LeakyReLU) x n chain, or None where ``seq`` is not one:
+    the plain torch classes, affine LayerNorms, Linears with biases, no hooks on the chain or in it — nothing
+    can tell its kernels from its module calls.  (Read off the blocks: walking the module tree with
+    ``parameters()`` costs more than every other question mlp_route asks.)"""
+    if (type(seq) is not nn.Sequential or type(seq).forward is not nn.Sequential.forward or len(seq) % 3
+            or _observed(seq, *seq)):
+        return None
+    params = []
+    for lin, ln, act in _blocks(seq):
         if (type(lin) is not nn.Linear or type(ln) is not nn.LayerNorm or type(act) is not nn.LeakyReLU or
-                lin.bias is None or not ln.elementwise_affine or ln.bias is None or
-                any(m._forward_hooks or m._forward_pre_hooks for m in (lin, ln, act))):
-            return False
-    return True
+                lin.bias is None or not ln.elementwise_affine or ln.bias is None):
+            return None
+        params += [lin.weight, lin.bias, ln.weight, ln.bias]
+    return params
 
 
-def mlp_forward(seq, x, out=None, extras=()):
-    """seq(torch.cat([x, *extras], -1)) for a core.py:122-129 MLP.  On the GPU at inference a block with
-    512 outputs is ONE launch (core.mlp_block: the Linear on the matrix cores, LayerNorm + LeakyReLU in
-    its epilogue; ``extras`` — per-row [..., 1] inputs appended to x, the out_mlp's f0 and loudness —
-    enter the first block's epilogue, so the concatenation is never built), a one-feature first Linear
-    folds into the LayerNorm kernel (core.layer_norm_leaky_relu), other blocks run their GEMM then that
-    kernel; the last block may write into ``out`` (e.g. a column slice of the GRU input concatenation)."""
-    if not _mlp_fusable(seq, x):
-        xin = torch.cat([x, *extras], -1) if extras else x
-        if _mlp_plain(seq, xin):
-            # under autograd: each block's Linear on grad.LinearFn (the one-feature first Linear stays torch's) and
-            # its LayerNorm + LeakyReLU on grad.LNLeakyFn (512 / 1024 features; else torch's modules)
-            from .grad import LinearFn, LNLeakyFn
-            y = xin
-            mods = list(seq)
-            for i in range(0, len(mods), 3):
-                lin, ln, act = mods[i:i + 3]
-                g = LinearFn.apply(y, lin.weight, lin.bias) if lin.in_features >= 16 else lin(y)
-                if lin.out_features in (512, 1024) and tuple(ln.normalized_shape) == (lin.out_features,):
-                    y = LNLeakyFn.apply(g, ln.weight, ln.bias, ln.eps, act.negative_slope)
-                else:
-                    y = act(ln(g))
-        else:
-            y = seq(xin)
-        if out is None:
-            return y
-        out.copy_(y)
-        return out
-    mods = list(seq)
-    h = x
-    for i in range(0, len(mods), 3):
-        lin, ln, act = mods[i:i + 3]
-        dst = out if i + 3 == len(mods) else None
-        ext = extras if i == 0 else ()
-        y = None
-        if lin.in_features == 1 and not ext:
-            y = core.layer_norm_leaky_relu(h, ln, act, out=dst, w1=lin.weight[:, 0], b1=lin.bias)
-        elif lin.in_features >= 16:
-            y = core.mlp_block(h, lin, ln, act, out=dst, extras=ext)
+def mlp_route(seq, x, extras=()):
+    """How mlp_forward runs seq(cat([x, *extras])), decided once per MLP and forward: "kernels" (an unobserved
+    block chain in fp32 on the GPU that autograd need not record: the inference kernels), "autograd" (the same
+    chain recorded: grad.LinearFn / grad.LNLeakyFn per block, on the concatenated input) or "modules" (torch's
+    modules, as the reference calls them).  ``extras`` do not change the first answer — at inference a
+    non-fp32 one is core's TypeError — but the autograd route takes the concatenation, in the dtype torch.cat
+    gives it."""
+    params = _mlp_params(seq) if x.is_cuda else None
+    if params is None:
+        return "modules"
+    if _fp32_ok(x.dtype, x.device.type, params) and not core._wants_grad(x, *params):
+        return "kernels"
+    dtype = x.dtype
+    for e in extras:
+        dtype = torch.promote_types(dtype, e.dtype)
+    return "autograd" if _fp32_ok(dtype, x.device.type, params) else "modules"
+
+
+def _block_kernels(lin, ln, act, h, extras, out):
+    """One block at inference: a one-feature Linear folds into the LayerNorm kernel, a block in core.mlp_block's
+    shapes is that one launch, others run their GEMM then the LayerNorm kernel, or torch's modules outside it.
+    ``out`` is written where the kernel can address it (the caller copies otherwise)."""
+    y = None
+    if lin.in_features == 1 and not extras:
+        y = core.layer_norm_leaky_relu(h, ln, act, out=out, w1=lin.weight[:, 0], b1=lin.bias)
+    elif lin.in_features >= core.MLP_MATRIX_MIN_IN:
+        y = core.mlp_block(h, lin, ln, act, out=out, extras=extras)
+    if y is None:
+        hin = torch.cat([h, *extras], -1) if extras else h
+        g = torch.nn.functional.linear(hin, lin.weight, lin.bias)
+        y = core.layer_norm_leaky_relu(g, ln, act, out=out)
         if y is None:
-            hin = torch.cat([h, *ext], -1) if ext else h
-            g = torch.nn.functional.linear(hin, lin.weight, lin.bias)
-            y = core.layer_norm_leaky_relu(g, ln, act, out=dst)
-            if y is None:
-                y = act(ln(g))
-        if dst is not None and y is not dst:
-            dst.copy_(y)
-            y = dst
-        h = y
-    return h
+            y = act(ln(g))
+    return y
+
+
+def _block_autograd(lin, ln, act, y):
+    """One block under autograd: the Linear on grad.LinearFn (the one-feature first Linear stays torch's), its
+    LayerNorm + LeakyReLU on grad.LNLeakyFn at the kernel's widths, else torch's modules."""
+    g = grad.LinearFn.apply(y, lin.weight, lin.bias) if lin.in_features >= core.MLP_MATRIX_MIN_IN else lin(y)
+    if lin.out_features in core.LN_LEAKY_COLS and tuple(ln.normalized_shape) == (lin.out_features,):
+        return grad.LNLeakyFn.apply(g, ln.weight, ln.bias, ln.eps, act.negative_slope)
+    return act(ln(g))
+
+
+def mlp_forward(seq, x, out=None, extras=(), route=None):
+    """seq(torch.cat([x, *extras], -1)) for a core.py:122-129 MLP, on ``route`` (mlp_route; computed if not
+    given).  On the GPU at inference a block with 512 outputs is ONE launch (core.mlp_block: the Linear on the
+    matrix cores, LayerNorm + LeakyReLU in its epilogue; ``extras`` — per-row [..., 1] inputs appended to x,
+    the out_mlp's f0 and loudness — enter the first block's epilogue, so the concatenation is never built), a
+    one-feature first Linear folds into the LayerNorm kernel (core.layer_norm_leaky_relu), other blocks run
+    their GEMM then that kernel; the last block may write into ``out`` (e.g. a column slice of the GRU input
+    concatenation).  On the other routes ``out`` receives a copy."""
+    if route is None:
+        route = mlp_route(seq, x, extras)
+    if route == "kernels":
+        y, blocks = x, _blocks(seq)
+        for i, blk in enumerate(blocks):
+            y = _block_kernels(*blk, y, extras if i == 0 else (), out if i == len(blocks) - 1 else None)
+    else:
+        y = torch.cat([x, *extras], -1) if extras else x
+        if route == "autograd":
+            for blk in _blocks(seq):
+                y = _block_autograd(*blk, y)
+        else:
+            y = seq(y)
+    if out is not None and y is not out:
+        out.copy_(y)
+        y = out
+    return y
 
 
 def gru_decoder_forward(self, f0, loudness, z=None, realtime=False):
     """ddsp/models/decoder.py:43-68 GRUDecoder.forward (incl. the optional z projection), the GRU on
     the step kernel for inference.  install() binds it to the reference's GRUDecoder too.  At inference
     on the GPU the MLP blocks' LayerNorm + LeakyReLU run fused and the input MLPs write straight into
-    the GRU's input concatenation (mlp_forward)."""
+    the GRU's input concatenation (mlp_forward): only when every one of them is on the kernels."""
     mlps = [(self.f0_mlp, f0), (self.loudness_mlp, loudness)]
     if getattr(self, "add_z", False):
         assert z is not None
         mlps.append((self.z_mlp, z))
+    routes = [mlp_route(m, x) for m, x in mlps]
     widths = [m[-3].out_features if len(m) >= 3 else -1 for m, _ in mlps]
-    if all(_mlp_fusable(m, x) for m, x in mlps) and len(set(widths)) == 1:
+    if all(r == "kernels" for r in routes) and len(set(widths)) == 1:
         W = widths[0]
         hidden = torch.empty(*f0.shape[:-1], W * len(mlps), dtype=torch.float32, device=f0.device)
         for i, (m, x) in enumerate(mlps):
-            mlp_forward(m, x, out=hidden[..., i * W:(i + 1) * W])
+            mlp_forward(m, x, out=hidden[..., i * W:(i + 1) * W], route="kernels")
     else:
-        hidden = torch.cat([mlp_forward(m, x) for m, x in mlps], -1)
+        hidden = torch.cat([mlp_forward(m, x, route=r) for (m, x), r in zip(mlps, routes)], -1)
     if realtime:
         gru_out, cache = _gru(self, hidden, self.cache_gru)
         self.cache_gru.copy_(cache)
@@ -166,30 +192,29 @@ def gru_decoder_forward(self, f0, loudness, z=None, realtime=False):
 
 
 def _hooked(m):
-    """A module call that must stay a module call: forward (pre-)hooks registered on it or globally, or
-    a subclass / wrapper whose forward is not nn.Linear's."""
-    from torch.nn.modules import module as _m
-    return bool(m._forward_hooks or m._forward_pre_hooks or _m._global_forward_hooks or
-                _m._global_forward_pre_hooks or type(m).forward is not torch.nn.Linear.forward)
+    """A module call that must stay a module call: observed (_observed), or a subclass / wrapper whose forward
+    is not nn.Linear's."""
+    return _observed(m) or type(m).forward is not torch.nn.Linear.forward
 
 
 def _synth_overridden(m, cls):
-    """The synth module's calls must stay module calls: forward (pre-)hooks on it or globally, or a class
-    whose forward / get_controls is not this package's (``cls``; install() binds the same functions to
-    the reference's classes, so an installed reference module is not overridden)."""
-    from torch.nn.modules import module as _m
-    if m._forward_hooks or m._forward_pre_hooks or _m._global_forward_hooks or _m._global_forward_pre_hooks:
-        return True
+    """The synth module's calls must stay module calls: observed (_observed), or a class whose forward /
+    get_controls is not this package's (``cls``; install() binds the same functions to the reference's
+    classes, so an installed reference module is not overridden)."""
     t = type(m)
-    return any(getattr(t, n, None) is not cls.__dict__[n] for n in ("forward", "get_controls"))
+    return _observed(m) or any(getattr(t, n, None) is not cls.__dict__[n] for n in ("forward", "get_controls"))
+
+
+def _fp32_ok(dtype, device_type, params):
+    """The fp32 network kernels apply: float32 input and parameters, and no autocast region (under
+    torch.autocast torch's modules run in the autocast dtype; these kernels compute in fp32 only)."""
+    return (dtype == torch.float32 and all(p.dtype == torch.float32 for p in params)
+            and not torch.is_autocast_enabled(device_type))
 
 
 def _fp32_inference_ok(x, mods):
-    """The fp32 network kernels apply: float32 input and parameters, and no autocast region (under
-    torch.autocast torch's modules run in the autocast dtype; these kernels compute in fp32 only)."""
-    if x.dtype != torch.float32 or any(p.dtype != torch.float32 for m in mods for p in m.parameters()):
-        return False
-    return not torch.is_autocast_enabled(x.device.type)
+    """_fp32_ok for input x and the parameters of ``mods``."""
+    return _fp32_ok(x.dtype, x.device.type, (p for m in mods for p in m.parameters()))
 
 
 def decoder_projections(self, hidden):
@@ -201,30 +226,25 @@ def decoder_projections(self, hidden):
     differentiable, so the parameters receive their gradients as the reference's do: at 512 inputs
     grad.ProjectionsFn (the forward on ddsp_hip_projections, the weight gradient on ddsp_hip_linear_weight_grad),
     elsewhere grad.LinearFn over the concatenated parameters.  Both are fp32 kernels: for any other dtype of
-    the input or the parameters, and inside an autocast region, the two module calls run (_fp32_inference_ok),
+    the input or the parameters, and inside an autocast region, the two module calls run (_fp32_ok),
     with or without autograd."""
     hp, npj = self.harmonic_proj, self.noise_proj
-    if not hidden.is_cuda or hp.bias is None or npj.bias is None or _hooked(hp) or _hooked(npj):
-        return hp(hidden), npj(hidden)  # (module hooks see the calls the reference makes)
     ps = (hp.weight, hp.bias, npj.weight, npj.bias)
+    if (not hidden.is_cuda or hp.bias is None or npj.bias is None or _hooked(hp) or _hooked(npj)
+            or not _fp32_ok(hidden.dtype, hidden.device.type, ps)):
+        # module hooks see the calls the reference makes; other dtypes and autocast regions run torch's Linears,
+        # in their dtype, with their autograd
+        return hp(hidden), npj(hidden)
     h1, n = hp.out_features, hp.out_features + npj.out_features
-    if torch.is_grad_enabled() and (hidden.requires_grad or any(p.requires_grad for p in ps)):
-        if not _fp32_inference_ok(hidden, (hp, npj)):
-            # other dtypes and autocast regions: torch's Linears, in their dtype, with their autograd
-            return hp(hidden), npj(hidden)
-        from .grad import LinearFn, ProjectionsFn
+    if core._wants_grad(hidden, *ps):
         if hidden.shape[-1] == 512 and all(p.dim() and p.stride(-1) == 1 for p in ps) \
                 and hp.in_features == npj.in_features == 512:
-            out = ProjectionsFn.apply(hidden, hp.weight, hp.bias, npj.weight, npj.bias)
+            out = grad.ProjectionsFn.apply(hidden, hp.weight, hp.bias, npj.weight, npj.bias)
         else:
             w, b = torch.cat([hp.weight, npj.weight]), torch.cat([hp.bias, npj.bias])  # differentiable
-            out = LinearFn.apply(hidden, w, b)
+            out = grad.LinearFn.apply(hidden, w, b)
         return out[..., :h1], out[..., h1:n]
-    if _fp32_inference_ok(hidden, (hp, npj)):
-        r = core.projections(hidden, hp, npj)
-        if r is not None:
-            return r
-    return hp(hidden), npj(hidden)
+    return core.projections(hidden, hp, npj)
 
 
 def decoder_synthesize(self, hidden, f0):

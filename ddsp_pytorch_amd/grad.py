@@ -472,8 +472,7 @@ class LinearFn(_F):
         g2 = _g(gy).reshape(-1, w.shape[0])
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            wt = w.t().contiguous()
-            gx = core.linear(g2, wt, torch.zeros(wt.shape[0], dtype=wt.dtype, device=wt.device)).view(ctx.x_shape)
+            gx = core.linear_input_grad(g2, w).view(ctx.x_shape)
         if ctx.needs_input_grad[1]:
             gw = core.linear_weight_grad(g2, x2)
         if ctx.needs_input_grad[2]:
@@ -492,18 +491,13 @@ class ProjectionsFn(_F):
     def forward(ctx, x, w1, b1, w2, b2):
         K = x.shape[-1]
         x2 = core._c(x).reshape(-1, K)
-        n1, n2 = w1.shape[0], w2.shape[0]
-        n4 = -(-(n1 + n2) // 4) * 4
-        y = torch.empty(x2.shape[0], n4, dtype=torch.float32, device=x.device)
         w1c, w2c = core._c(w1), core._c(w2)
-        st = _lib.call("projections", _lib.ptr(x2), K, K, _lib.ptr(w1c), K, _lib.ptr(core._c(b1)), n1, _lib.ptr(w2c),
-                       K, _lib.ptr(core._c(b2)), n2, _lib.ptr(y), n4, x2.shape[0], _lib.stream_of(y),
-                       allow=(core.ERANGE,))
-        if st == core.ERANGE:  # (unaligned rows) one library GEMM
-            y[:, :n1 + n2] = torch.addmm(torch.cat([b1, b2]), x2, torch.cat([w1c, w2c]).t())
+        y, launched = core.projections_launch(x2, w1c, b1, w2c, b2)
+        if not launched:  # (unaligned rows) one library GEMM
+            y[:, :w1.shape[0] + w2.shape[0]] = torch.addmm(torch.cat([b1, b2]), x2, torch.cat([w1c, w2c]).t())
         ctx.save_for_backward(x2, w1c, w2c)
         ctx.x_shape = x.shape
-        return y.view(*x.shape[:-1], n4)
+        return y.view(*x.shape[:-1], y.shape[-1])
 
     @staticmethod
     @once_differentiable
@@ -528,16 +522,15 @@ class LNLeakyFn(_F):
     """LeakyReLU(LayerNorm(g)) under autograd for the decoder's MLP blocks (ddsp/core.py:122-129): the forward on
     ddsp_hip_layer_norm_leaky_relu, the backward — dg, dgamma, dbeta from the saved g — on
     ddsp_hip_layer_norm_leaky_relu_backward (one pass instead of torch's LeakyReLU and LayerNorm backward kernels
-    and its separate parameter-gradient reductions).  g [..., cols] with cols 512 or 1024 (mlp_forward checks)."""
+    and its separate parameter-gradient reductions).  g [..., cols] with cols in core.LN_LEAKY_COLS (mlp_forward
+    checks)."""
 
     @staticmethod
     def forward(ctx, g, gamma, beta, eps, slope):
         gc = core._c(g)
-        cols = gc.shape[-1]
-        rows = gc.numel() // cols
-        y = torch.empty_like(gc)
-        _lib.call("layer_norm_leaky_relu", _lib.ptr(gc), cols, None, None, _lib.ptr(core._c(gamma)),
-                  _lib.ptr(core._c(beta)), float(eps), float(slope), _lib.ptr(y), cols, rows, cols, _lib.stream_of(y))
+        y = core.ln_leaky_launch(gc, gamma, beta, eps, slope)
+        if y is None:
+            raise RuntimeError(f"LNLeakyFn: input {tuple(g.shape)} is outside the kernel's shapes")
         ctx.save_for_backward(gc, gamma, beta)
         ctx.eps, ctx.slope = float(eps), float(slope)
         return y
@@ -567,12 +560,8 @@ class GRUFn(_F):
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, h0):
-        B, T, I = x.shape
-        H = w_hh.shape[1]
-        out = torch.empty(B, T, H, dtype=torch.float32, device=x.device)
-        h_last = torch.empty(1, B, H, dtype=torch.float32, device=x.device)
-        gates = torch.empty(4, B, T, H, dtype=torch.float32, device=x.device)
-        h0c = core._c(h0.reshape(B, H)) if h0 is not None else None
+        out, h_last, h0c = core.gru_buffers(x, w_hh.shape[1], h0)
+        gates = torch.empty(4, *out.shape, dtype=torch.float32, device=x.device)
         core.gru_layer_launch(x, w_ih, b_ih, w_hh, b_hh, h0c, out, h_last, gates)
         ctx.save_for_backward(x, w_ih, w_hh, out, gates, h0c if h0c is not None else torch.empty(0))
         ctx.has_h0 = h0 is not None
@@ -591,25 +580,13 @@ class GRUFn(_F):
         dh0 = torch.empty(B, H, dtype=torch.float32, device=x.device) if ctx.has_h0 else None
         go = core._c(g_out) if g_out is not None else None
         gh = core._c(g_hlast.reshape(B, H)) if g_hlast is not None else None
-        args = (_lib.ptr(core._c(w_hh)), _lib.ptr(gates), _lib.ptr(out), _lib.ptr(h0p), _lib.ptr(go), _lib.ptr(gh),
-                _lib.ptr(dxp), _lib.ptr(dgn), _lib.ptr(dh0), B, T, H)
-        # hidden 512, batch <= 64: the whole BPTT as one persistent launch; otherwise (ERANGE) one launch per step
-        ws = core._workspace(_lib.query("gru_persistent_workspace_size"), x.device)
-        st = _lib.call("gru_backward_persistent", *args, int(GRU_BPTT_FLAGS), _lib.ptr(ws), ws.numel(),
-                       _lib.stream_of(dxp), allow=(core.ERANGE,))
-        dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
-        core._GRU_LAST[dev] = ("persistent", ws) if st == 0 else ("steps", None)
-        if st == core.ERANGE:
-            ws = core._workspace(_lib.query("gru_backward_workspace_size", B, H), x.device)
-            _lib.call("gru_backward", *args, _lib.ptr(ws), ws.numel(), _lib.stream_of(dxp))
+        core.gru_backward_launch(w_hh, gates, out, h0p, go, gh, dxp, dgn, dh0, GRU_BPTT_FLAGS)
         dxp2 = dxp.view(B * T, 3 * H)
         dG = torch.cat([dxp[..., :2 * H], dgn], -1).view(B * T, 3 * H)
         hprev = torch.cat([(h0p.view(B, 1, H) if h0p is not None else torch.zeros(B, 1, H, device=x.device)),
                            out[:, :-1]], 1).reshape(B * T, H)
-        dx = None
-        if ctx.needs_input_grad[0]:  # dx = dxp W_ih on the matrix-core kernel (W_ih^T as its weight; addmm outside it)
-            wt = w_ih.t().contiguous()
-            dx = core.linear(dxp2, wt, torch.zeros(wt.shape[0], dtype=wt.dtype, device=wt.device)).view(B, T, I)
+        # dx = dxp W_ih on the matrix-core kernel (addmm outside it)
+        dx = core.linear_input_grad(dxp2, w_ih).view(B, T, I) if ctx.needs_input_grad[0] else None
         dw_ih = core.linear_weight_grad(dxp2, x.reshape(B * T, I)) if ctx.needs_input_grad[1] else None
         dw_hh = core.linear_weight_grad(dG, hprev) if ctx.needs_input_grad[2] else None
         db_ih = dxp2.sum(0) if ctx.needs_input_grad[3] else None

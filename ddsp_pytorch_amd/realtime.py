@@ -182,18 +182,14 @@ class RealtimeGraph:
         g = d.gru
         w_ih = _Linear(g.weight_ih_l0, g.bias_ih_l0, g.input_size, 3 * g.hidden_size)
         core.dense_rows([([di(b["y3f"], norm=f0m[7]), di(b["y3l"], norm=lm[7])], w_ih, b["xp"])], R, dev)
+        # the state in place: the step kernels write h_T over h0; the persistent launch, whose rescue re-reads h0,
+        # into a buffer of its own, copied over the state after it.  The workspace is this object's: the graph holds it
         cache = d.cache_gru
-        L = core._lib
-        args = (L.ptr(b["xp"]), L.ptr(g.weight_hh_l0), L.ptr(g.bias_hh_l0), L.ptr(cache), L.ptr(b["gru"]))
-        st = core.ERANGE
-        if self.gru_route == "persistent":  # h_T into its own buffer: the rescue kernel re-reads h0
-            st = L.call("gru_forward_persistent", *args, L.ptr(b["h_last"]), None, 1, R, g.hidden_size, 0,
-                        L.ptr(self._gru_ws), self._gru_ws.numel(), L.stream_of(cache), allow=(core.ERANGE,))
-            if st == 0:
-                cache.view(1, -1).copy_(b["h_last"])
-        if st == core.ERANGE:  # one launch per step, h_T written over h0 (the step kernels allow it)
-            L.call("gru_forward", *args, L.ptr(cache), None, 1, R, g.hidden_size, L.stream_of(cache))
-        self.gru_route_taken = "persistent" if st == 0 else "steps"
+        self.gru_route_taken = core.gru_recurrence(
+            b["xp"].view(1, R, -1), g.weight_hh_l0, g.bias_hh_l0, cache, b["gru"].view(1, R, -1), b["h_last"],
+            ws=self._gru_ws, persistent=self.gru_route == "persistent", h_last_steps=cache)
+        if self.gru_route_taken == "persistent":
+            cache.view(1, -1).copy_(b["h_last"])
         # out_mlp(cat([gru_out, f0, loudness])) (decoder.py:68), then the projections
         core.dense_rows([([di(b["gru"]), di(b["f0"]), di(b["loud"])], om[0], b["y4"])], R, dev)
         core.dense_rows([([di(b["y4"], norm=om[1])], om[3], b["y5"])], R, dev)

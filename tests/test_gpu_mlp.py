@@ -52,12 +52,12 @@ def test_layer_norm_leaky_relu_kernel(dd):
 
 def test_mlp_under_autograd_keeps_torch(dd):
     """Training keeps torch's modules (their autograd): the fused path is inference-only."""
-    from ddsp_pytorch_amd.decoder import _mlp_fusable, mlp
+    from ddsp_pytorch_amd.decoder import mlp, mlp_route
     m = mlp(1, 512, 3).cuda()
     x = torch.randn(2, 5, 1, device="cuda")
-    assert not _mlp_fusable(m, x)
+    assert mlp_route(m, x) != "kernels"
     with torch.no_grad():
-        assert _mlp_fusable(m, x)
+        assert mlp_route(m, x) == "kernels"
 
 
 @pytest.mark.parametrize("rows", [1, 63, 64, 65, 1000])

@@ -146,7 +146,8 @@ __global__ void __launch_bounds__(512) frame_backward_kernel(
   const bool quads = NOISE && (half % 4 == 0) && n <= bs && (bs % 4 == 0);
   // quads: segment rows n + 4 floats apart, so the rows of one wave's segments start on different banks
   // (48.1-48.2 -> 47.2-47.5 us for the noise VJP at config 2, same box)
-  const int npart_len = NSEG * (quads ? n + 4 : qmax);
+  // (at least n: the cosine transform's [2][half] partial sums reuse npart, and NSEG * bs < n when n > bs)
+  const int npart_len = max(NSEG * (quads ? n + 4 : qmax), n);
   float* xl = smem + ((hfl + 3) & ~3);                              // [bs] noise
   float* ct = xl + bs;                                               // [n] cos(2 pi q / n)
   float* e = ct + n;                                                 // [n] windowed tap gradients
@@ -207,7 +208,17 @@ __global__ void __launch_bounds__(512) frame_backward_kernel(
       for (int k = tid; k < H; k += NT) uk[k] = uk[k] / norm;
     if (tid == 0) {
       const float w0 = (float)(S0 + dinc), w1 = (float)(S0 + (double)bs * dinc);
-      fast_s = fmaxf(fabsf(w0), fabsf(w1)) * (float)H < kFastArgLimit;
+      // The hardware sine's error is absolute (3.2e-7: reduce_rev's revolutions carry 3e-8 at |y| ~ 0.5, the odd
+      // multiples of pi), harmless against a gradient of the size of g.  When the frame's arguments k omega_t
+      // spread over few periods, its sines are a smooth function of (t, k) with only about H bs inc / pi
+      // independent directions, and the frame's whole gradient can cancel to a few percent of its terms:
+      // omega_t near a multiple of pi puts every k omega_t near one, or g is nearly orthogonal to the one or two
+      // directions.  That happened twice in 600 frames at bs = 4, H = 8, and the sine's error was 1.1e-5 of those
+      // frames' gradients (tests/test_gpu_vjp_shapes.py, case 8).  Frames whose arguments spread over less than
+      // 16 rad take the general loop below: its polynomial sine on the pi-reduced argument keeps its relative
+      // accuracy at the zero crossings.  (At bs = 512, H = 100 these are pitches below 2.4 Hz.)
+      const bool wide = (float)H * (float)bs * fabsf((float)dinc) >= 16.0f;
+      fast_s = wide && fmaxf(fabsf(w0), fabsf(w1)) * (float)H < kFastArgLimit;
     }
   }
   __syncthreads();
@@ -266,7 +277,7 @@ __global__ void __launch_bounds__(512) frame_backward_kernel(
 #pragma unroll
           for (int c = 0; c < kKPT; ++c) {
             const float x = p.x * kf[c];
-            acc[c] = fmaf(p.y, fabsf(x) < kFastArgLimit ? sin_reduced(x) : sin_slow(x), acc[c]);
+            acc[c] = fmaf(p.y, fabsf(x) < kFastArgLimit ? sin_poly(x) : sin_slow(x), acc[c]);
           }
         }
       }
@@ -700,7 +711,7 @@ size_t frame_backward_lds_floats(bool harm, bool noise, int H, int bs, int NS, i
   const int n = 2 * (NB - 1);
   const int qmax = std::min(n, bs);
   const bool quads = ((n / 2) % 4 == 0) && n <= bs && bs % 4 == 0;
-  const size_t npart_len = (size_t)NSEG * (quads ? n + 4 : qmax);
+  const size_t npart_len = std::max((size_t)NSEG * (quads ? n + 4 : qmax), (size_t)n);
   const size_t off_xl = (hfl + 3) & ~(size_t)3;
   const size_t off_gl = (off_xl + (size_t)bs + 2 * (size_t)n + npart_len + 3) & ~(size_t)3;
   return off_gl + (size_t)bs + 8;

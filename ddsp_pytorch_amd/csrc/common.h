@@ -68,7 +68,9 @@ __device__ __forceinline__ float amp_sin_acc(float rs, float a, float ac3, float
 }
 
 // sin(x) for |x| < kFastArgLimit by the polynomial: abs error < 2e-7 (rms 4e-8 on uniform
-// arguments).  Kept as the second, independent evaluation for kernel probes and tests.
+// arguments), and relative to the sine near its zero crossings (r = x - n pi is formed without rounding
+// there).  The second, independent evaluation for kernel probes and tests, and the sine of the backward's
+// general loop (backward.hip: frames whose sines can all be small).
 __device__ __forceinline__ float sin_poly(float x) {
   const float rs = reduce_signed(x);
   const float r2 = rs * rs;

@@ -655,7 +655,7 @@ def gru_last_route(device=None):
 def linear(x, weight, bias):
     """x [rows, in] @ weight[out, in]^T + bias -> [rows, out] (no autograd): ddsp_hip_linear — the bf16 matrix
     cores with the fp32-accurate three-term split — where it applies (in 512 / 1024 / 1536, out a multiple of
-    512: dense.hip:1312), else torch.addmm (hipBLASLt)."""
+    512: dense.hip's ddsp_hip_linear), else torch.addmm (hipBLASLt)."""
     _dev(x, weight, bias)
     rows, K = x.shape
     N = weight.shape[0]
@@ -708,10 +708,10 @@ def _out_rows(out, lead, cols, device):
     return out, (out.stride(-2) if out.dim() >= 2 else cols)
 
 
-# Below one K chunk of the matrix-core kernels (16 wide: k = 16 h + ..., dense.hip:363, 552) a block's Linear has no
-# work for them: the decoder keeps the K = 1 Linear in the LayerNorm kernel (or torch's, under autograd) and runs
-# mlp_block / grad.LinearFn from here up.  A policy of the callers, not an envelope: ddsp_hip_mlp_block itself takes
-# any K >= 1 (dense.hip:1270).
+# Below one K chunk of the matrix-core kernels (16 wide: k = 16 h + ..., dense.hip's mlp_block_kernel) a block's
+# Linear has no work for them: the decoder keeps the K = 1 Linear in the LayerNorm kernel (or torch's, under
+# autograd) and runs mlp_block / grad.LinearFn from here up.  A policy of the callers, not an envelope:
+# ddsp_hip_mlp_block itself takes any K >= 1.
 MLP_MATRIX_MIN_IN = 16
 
 
@@ -767,7 +767,7 @@ def projections(x, lin1, lin2, pad_to=64):
 def projections_launch(x, w1, b1, w2, b2):
     """ddsp_hip_projections over x [..., K] and the two layers' parameters, all contiguous (_c) -> (y [..., n4],
     launched): both outputs side by side in rows of n4 floats, n1 + n2 rounded up to 4 (16-byte aligned rows).
-    ``launched`` False: outside the kernel's shapes (dense.hip:1343), y is not written."""
+    ``launched`` False: outside the kernel's shapes (dense.hip's ddsp_hip_projections), y is not written."""
     n1, n2, K = w1.shape[0], w2.shape[0], x.shape[-1]
     n4 = -(-(n1 + n2) // 4) * 4
     y = torch.empty(*x.shape[:-1], n4, dtype=torch.float32, device=x.device)
@@ -777,7 +777,7 @@ def projections_launch(x, w1, b1, w2, b2):
     return y, st != ERANGE
 
 
-LN_LEAKY_COLS = (512, 1024)  # the widths ddsp_hip_layer_norm_leaky_relu and its backward take (dense.hip:1216, 1248)
+LN_LEAKY_COLS = (512, 1024)  # the widths ddsp_hip_layer_norm_leaky_relu and its backward take (dense.hip)
 
 
 def layer_norm_leaky_relu(h, norm, act, out=None, w1=None, b1=None):

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 
+#include "bf16x3.h"
 #include "common.h"
 
 namespace ddsp {
@@ -371,7 +372,7 @@ constexpr int kMlpRows = 64;        // rows per workgroup
 constexpr int kMlpKC = 32;          // K per LDS stage
 constexpr int kMlpLd = kMlpKC + 4;  // LDS row stride (floats): 16-B aligned rows, banks spread
 
-// The block's epilogue (both forms below): bias, the out_mlp's two extra input columns, LayerNorm (two-pass
+// The block's epilogue (the f32 and the bf16x3 form below): bias, the out_mlp's two extra input columns, LayerNorm (two-pass
 // mean / biased variance over the row, reduced across the 8 waves in LDS) and LeakyReLU, one store per value.
 __device__ __forceinline__ void mlp_epilogue(f32x4_t (&acc)[4][4], int64_t r0, int K, const float* __restrict__ w,
                                              int64_t w_ld, const float* __restrict__ bias,
@@ -542,96 +543,8 @@ __global__ void __launch_bounds__(512) mlp_block_kernel(
   mlp_epilogue(acc, r0, K, w, w_ld, bias, e0, e1, e_ld, gamma, beta, eps, slope, y, y_ld, R, red, stat);
 }
 
-// The same block with the x tile RESIDENT in LDS and W streamed straight into MFMA operand registers (the
-// decoder's blocks: K = 512).  Why: in the staged form above every K step is a pair of workgroup barriers
-// around one LDS stage that all 8 waves fill and then read, so the matrix pipe idles for the barrier, the
-// LDS writes and the first reads of every step (89 us per config-2 block against ~55 us of MFMA issue).
-// Here the workgroup's 64 x K slice of x is loaded into LDS once (133 KB at K = 512, rows padded to
-// K + 8 floats: the 16-lane groups of a ds_read_b128 then hit 16 distinct bank quads), and W needs no
-// LDS at all — wave wv alone uses output columns [64 wv, 64 wv + 64), so each lane loads its B fragment
-// (column 64 wv + 16 j + l16, k = 16 h + 4 q .. + 3: one float4 per tile and 16-wide K chunk h) from
-// global memory kP chunks ahead of its use into a register ring.  The main loop has no barrier: each wave
-// runs 4 LDS reads + 4 global loads + 64 MFMAs per chunk on its own.  Same operands per MFMA and the same
-// k order as the staged form (k = 16 h + 4 q + s at sub-step s), so the results are identical bit for bit.
-constexpr int kMlpResK = 512;
-constexpr int kMlpResLd = kMlpResK + 8;
-template <int kP>
-__global__ void __launch_bounds__(512) mlp_block_res_kernel(
-    const float* __restrict__ x, int64_t x_ld, const float* __restrict__ w, int64_t w_ld,
-    const float* __restrict__ bias, const float* __restrict__ e0, const float* __restrict__ e1, int64_t e_ld,
-    const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float slope, float* __restrict__ y,
-    int64_t y_ld, int64_t R) {
-  constexpr int K = kMlpResK, NH = K / 16;
-  static_assert(NH % kP == 0, "ring");
-  __shared__ __attribute__((aligned(16))) float xs[kMlpRows * kMlpResLd];
-  __shared__ float red[8][kMlpRows];
-  __shared__ float stat[kMlpRows];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int q = lane >> 4, l16 = lane & 15;
-  const int64_t r0 = (int64_t)blockIdx.x * kMlpRows;
-  // this lane's W fragment rows: column 64 wv + 16 j + l16, k offset 4 q
-  const float* wl = w + (int64_t)(64 * wv + l16) * w_ld + 4 * q;
-  const int64_t wj = 16 * w_ld;
-  float4 wb[kP][4];
-#pragma unroll
-  for (int p = 0; p < kP; ++p)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wb[p][j] = *reinterpret_cast<const float4*>(wl + j * wj + 16 * p);
-  // the x tile into LDS (rows >= R read row R - 1: loaded, never stored)
-  {
-    constexpr int kF4 = kMlpRows * K / 4 / 512;  // float4 per thread
-    float4 v[kF4];
-#pragma unroll
-    for (int i = 0; i < kF4; ++i) {
-      const int f = t + 512 * i, row = f / (K / 4), c4 = f - row * (K / 4);
-      const int64_t rr = r0 + row < R ? r0 + row : R - 1;
-      v[i] = *reinterpret_cast<const float4*>(x + rr * x_ld + 4 * c4);
-    }
-#pragma unroll
-    for (int i = 0; i < kF4; ++i) {
-      const int f = t + 512 * i, row = f / (K / 4), c4 = f - row * (K / 4);
-      *reinterpret_cast<float4*>(&xs[row * kMlpResLd + 4 * c4]) = v[i];
-    }
-  }
-  __syncthreads();
-  f32x4_t acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  const float* xl = xs + l16 * kMlpResLd + 4 * q;
-  for (int h0 = 0; h0 < NH; h0 += kP) {
-#pragma unroll
-    for (int p = 0; p < kP; ++p) {
-      const int h = h0 + p;
-      float4 af[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const float4*>(xl + 16 * i * kMlpResLd + 16 * h);
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float a = s == 0 ? af[i].x : s == 1 ? af[i].y : s == 2 ? af[i].z : af[i].w;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float b = s == 0 ? wb[p][j].x : s == 1 ? wb[p][j].y : s == 2 ? wb[p][j].z : wb[p][j].w;
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[i][j], 0, 0, 0);
-          }
-        }
-      }
-      // refill this ring slot with chunk h + kP (clamped: the last kP reloads re-read the final chunk, so
-      // every iteration issues the same loads and the wait counts stay exact)
-      const int hn = h + kP < NH ? h + kP : NH - 1;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) wb[p][j] = *reinterpret_cast<const float4*>(wl + j * wj + 16 * hn);
-      __builtin_amdgcn_sched_barrier(0);  // keep the refill here (the scheduler would sink it to the slot's use)
-    }
-  }
-  mlp_epilogue(acc, r0, K, w, w_ld, bias, e0, e1, e_ld, gamma, beta, eps, slope, y, y_ld, R, red, stat);
-}
-
 // The decoder's blocks (K = 512) on the bf16 matrix cores with fp32 accuracy.  The f32-input MFMA runs at
-// 1/16 of the bf16 rate, and the kernels above are bound by it (84-90 us per config-2 block: 74 TF on the
+// 1/16 of the bf16 rate, and the kernel above is bound by it (84-90 us per config-2 block: 74 TF on the
 // 200 CUs a 12,800-row batch fills, at the clock MFMA-dense loops hold).  Here both operands are split
 // exactly into three bf16 terms, v = hi + mid + lo (hi = v with its low 16 bits cleared, mid the same of
 // v - hi, lo = v - hi - mid: each term exact, 8 significant bits apiece, together all 24 of the fp32
@@ -647,10 +560,87 @@ __global__ void __launch_bounds__(512) mlp_block_res_kernel(
 //     a register ring kP 32-wide chunks ahead of its use (no LDS).
 // Fragments (v_mfma_f32_16x16x32_bf16): lane (q, l16) holds A[row l16][k = 8 q .. + 7] and
 // B[k = 8 q .. + 7][col l16]; C/D as the f32 form (row 4 q + e, col l16), so the epilogue is shared.
-// (split_bf16x3, u32x4_t and as_bf16x8: common.h)
+// (the split, the fragment types and the six-product mfma_bf3: bf16x3.h)
 
 constexpr int kBf3QK = 128;                     // K per quarter (LDS split stage)
+constexpr int kBf3MlpK = 512;                   // the MLP blocks' K on this kernel (the decoder's hidden size)
 constexpr int kBf3Plane = kMlpRows * kBf3QK;    // bf16 elements per plane (row-major, 256 B rows)
+constexpr int kBf3Buf = 3 * kBf3Plane / 2;      // uint32 words per buffer (three planes)
+
+// The x stage of the bf16x3 x W^T kernels (linear_bf3_kernel, proj_bf3_sk_kernel; 512 threads, 64 rows).  LDS:
+// xs[buffer][plane hi/mid/lo][row][128 k] bf16, the 16-byte quads (8 bf16) of a row at position Q ^ (row & 15).
+// Split role: thread -> row t >> 3, k 16 (t & 7) .. + 15 of a quarter (quads Q = 2 (t & 7), + 1).
+struct Bf3XStage {
+  int srow, sq;
+  const float* src;
+  float4 v[4];
+  __device__ __forceinline__ Bf3XStage(const float* x, int64_t x_ld, int64_t r0, int64_t R)
+      : srow(threadIdx.x >> 3), sq(2 * (threadIdx.x & 7)) {
+    src = x + (r0 + srow < R ? r0 + srow : R - 1) * x_ld + 8 * sq;  // rows >= R: never stored
+  }
+  __device__ __forceinline__ void load(int qt) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const float4*>(src + kBf3QK * qt + 4 * i);
+  }
+  __device__ __forceinline__ void store(uint32_t* xs, int buf) const {
+    u32x4_t hq[2], mq[2], lq[2];
+    split_bf16x3(v[0], v[1], hq[0], mq[0], lq[0]);
+    split_bf16x3(v[2], v[3], hq[1], mq[1], lq[1]);
+    uint32_t* base = xs + buf * kBf3Buf + srow * (kBf3QK / 2);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int pos = 4 * ((sq + e) ^ (srow & 15));  // uint32 offset of the quad
+      *reinterpret_cast<u32x4_t*>(base + pos) = hq[e];
+      *reinterpret_cast<u32x4_t*>(base + kBf3Plane / 2 + pos) = mq[e];
+      *reinterpret_cast<u32x4_t*>(base + kBf3Plane + pos) = lq[e];
+    }
+  }
+  // quarters 0 and 1 resident, quarter 2's loads in flight under quarter 0
+  __device__ __forceinline__ void prologue(uint32_t* xs) {
+    load(0);
+    store(xs, 0);
+    load(1);
+    store(xs, 1);
+    load(2);
+    __syncthreads();
+  }
+  // after quarter qt of NQ: its buffer takes quarter qt + 2, and quarter qt + 3's loads start
+  __device__ __forceinline__ void advance(uint32_t* xs, int qt, int NQ) {
+    if (qt + 1 < NQ) {
+      __syncthreads();  // buffer qt & 1 fully read; the previous quarter's split writes visible
+      if (qt + 2 < NQ) {
+        store(xs, qt & 1);
+        if (qt + 3 < NQ) load(qt + 3);
+      }
+    }
+  }
+};
+
+// The A fragments of 32-wide chunk c of quarter qt for the four 16-row tiles: rows 16 i + l16 (row & 15 = l16),
+// k = 32 c + 8 q .. + 7, from the three planes
+__device__ __forceinline__ void bf3_x_fragments(const uint32_t* xs, int qt, int c, int q, int l16, u32x4_t (&xh)[4],
+                                                u32x4_t (&xm)[4], u32x4_t (&xlo)[4]) {
+  const uint32_t* xb = xs + (qt & 1) * kBf3Buf + l16 * (kBf3QK / 2);
+  const int pos = 4 * ((4 * c + q) ^ l16);  // uint32 offset of the quad
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t* r = xb + 16 * i * (kBf3QK / 2) + pos;
+    xh[i] = *reinterpret_cast<const u32x4_t*>(r);
+    xm[i] = *reinterpret_cast<const u32x4_t*>(r + kBf3Plane / 2);
+    xlo[i] = *reinterpret_cast<const u32x4_t*>(r + kBf3Plane);
+  }
+}
+
+// 4 floats of a W row for the register rings: one 16-byte load, or two 8-byte loads (kW8: rows 8-byte aligned)
+template <bool kW8>
+__device__ __forceinline__ float4 bf3_ldw(const float* p) {
+  if constexpr (kW8) {
+    const float2 a = *reinterpret_cast<const float2*>(p), b = *reinterpret_cast<const float2*>(p + 2);
+    return make_float4(a.x, a.y, b.x, b.y);
+  } else {
+    return *reinterpret_cast<const float4*>(p);
+  }
+}
 
 // kLN: the MLP block (512 outputs, LayerNorm + LeakyReLU epilogue); else a plain Linear, y = x W^T + b, over
 // 512-column blocks of W (blockIdx.y), e.g. the GRU's input projection for every step (decoder.py:41).
@@ -664,8 +654,7 @@ __global__ void __launch_bounds__(512) linear_bf3_kernel(
   constexpr int NQ = K / kBf3QK, NC = kBf3QK / 32;  // quarters; 32-wide chunks per quarter
   static_assert(K % kBf3QK == 0 && NQ >= 2, "K");
   static_assert((NQ * NC) % kP == 0 && NC % kP == 0, "ring");
-  // [buffer][plane hi/mid/lo][row][128 k] bf16, quads (8 bf16) at position Q ^ (row & 15)
-  __shared__ __attribute__((aligned(16))) uint32_t xs[2 * 3 * kBf3Plane / 2];
+  __shared__ __attribute__((aligned(16))) uint32_t xs[2 * kBf3Buf];
   __shared__ float red[8][kMlpRows];
   __shared__ float stat[kMlpRows];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
@@ -679,14 +668,7 @@ __global__ void __launch_bounds__(512) linear_bf3_kernel(
   // W fragment of this lane: column 64 wv + 16 j + l16, k = 32 h + 8 q .. + 7 (two float4)
   const float* wl = w + (int64_t)(64 * wv + l16) * w_ld + 8 * q;
   const int64_t wj = 16 * w_ld;
-  auto ldw = [](const float* p) -> float4 {
-    if constexpr (kW8) {
-      const float2 a = *reinterpret_cast<const float2*>(p), b = *reinterpret_cast<const float2*>(p + 2);
-      return make_float4(a.x, a.y, b.x, b.y);
-    } else {
-      return *reinterpret_cast<const float4*>(p);
-    }
-  };
+  auto ldw = bf3_ldw<kW8>;
   float4 wb[kP][4][2];
 #pragma unroll
   for (int p = 0; p < kP; ++p)
@@ -695,69 +677,28 @@ __global__ void __launch_bounds__(512) linear_bf3_kernel(
       wb[p][j][0] = ldw(wl + j * wj + 32 * p);
       wb[p][j][1] = ldw(wl + j * wj + 32 * p + 4);
     }
-  // split role: thread -> row t >> 3, k 16 (t & 7) .. + 15 of a quarter (quads Q = 2 (t & 7), + 1)
-  const int srow = t >> 3, sq = 2 * (t & 7);
-  const float* xsrc = x + (r0 + srow < R ? r0 + srow : R - 1) * x_ld + 8 * sq;  // rows >= R: never stored
-  float4 xv[4];
-  auto load_quarter = [&](int qt) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) xv[i] = *reinterpret_cast<const float4*>(xsrc + kBf3QK * qt + 4 * i);
-  };
-  auto store_quarter = [&](int buf) {
-    u32x4_t hq[2], mq[2], lq[2];
-    split_bf16x3(xv[0], xv[1], hq[0], mq[0], lq[0]);
-    split_bf16x3(xv[2], xv[3], hq[1], mq[1], lq[1]);
-    uint32_t* base = xs + buf * (3 * kBf3Plane / 2) + srow * (kBf3QK / 2);
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int pos = 4 * ((sq + e) ^ (srow & 15));  // uint32 offset of the quad
-      *reinterpret_cast<u32x4_t*>(base + pos) = hq[e];
-      *reinterpret_cast<u32x4_t*>(base + kBf3Plane / 2 + pos) = mq[e];
-      *reinterpret_cast<u32x4_t*>(base + kBf3Plane + pos) = lq[e];
-    }
-  };
-  load_quarter(0);
-  store_quarter(0);
-  load_quarter(1);
-  store_quarter(1);
-  load_quarter(2);  // in flight under quarter 0
-  __syncthreads();
+  Bf3XStage xst(x, x_ld, r0, R);
+  xst.prologue(xs);
   f32x4_t acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
   for (int qt = 0; qt < NQ; ++qt) {
-    const uint32_t* xb = xs + (qt & 1) * (3 * kBf3Plane / 2) + l16 * (kBf3QK / 2);  // row 16 i + l16: row & 15 = l16
 #pragma unroll
     for (int c0 = 0; c0 < NC; c0 += kP) {
 #pragma unroll
       for (int p = 0; p < kP; ++p) {
         const int c = c0 + p, h = qt * NC + c;
-        const int pos = 4 * ((4 * c + q) ^ l16);
         u32x4_t xh[4], xm[4], xlo[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const uint32_t* r = xb + 16 * i * (kBf3QK / 2) + pos;
-          xh[i] = *reinterpret_cast<const u32x4_t*>(r);
-          xm[i] = *reinterpret_cast<const u32x4_t*>(r + kBf3Plane / 2);
-          xlo[i] = *reinterpret_cast<const u32x4_t*>(r + kBf3Plane);
-        }
+        bf3_x_fragments(xs, qt, c, q, l16, xh, xm, xlo);
         const int hn = h + kP < NQ * NC ? h + kP : NQ * NC - 1;  // clamped: the same loads every iteration
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           u32x4_t wh, wm, wlo;
           split_bf16x3(wb[p][j][0], wb[p][j][1], wh, wm, wlo);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {  // small terms first
-            f32x4_t a = acc[i][j];
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xm[i]), as_bf16x8(wm), a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xlo[i]), as_bf16x8(wh), a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xh[i]), as_bf16x8(wlo), a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xm[i]), as_bf16x8(wh), a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xh[i]), as_bf16x8(wm), a, 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xh[i]), as_bf16x8(wh), a, 0, 0, 0);
-          }
+          for (int i = 0; i < 4; ++i) acc[i][j] = mfma_bf3(xh[i], xm[i], xlo[i], wh, wm, wlo, acc[i][j]);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -767,13 +708,7 @@ __global__ void __launch_bounds__(512) linear_bf3_kernel(
         __builtin_amdgcn_sched_barrier(0);  // keep the refill here (the scheduler would sink it to its use)
       }
     }
-    if (qt + 1 < NQ) {
-      __syncthreads();  // buffer qt & 1 fully read; the previous quarter's split writes visible
-      if (qt + 2 < NQ) {
-        store_quarter(qt & 1);  // quarter qt + 2
-        if (qt + 3 < NQ) load_quarter(qt + 3);
-      }
-    }
+    xst.advance(xs, qt, NQ);
   }
   if constexpr (kLN) {
     mlp_epilogue(acc, r0, K, w, w_ld, bias, e0, e1, e_ld, gamma, beta, eps, slope, y, y_ld, R, red, stat);
@@ -797,8 +732,8 @@ __global__ void __launch_bounds__(512) linear_bf3_kernel(
 // bf16 matrix cores with the fp32-accurate three-term split (the six products of linear_bf3_kernel), reading
 // both layers' parameters where they lie: output column c < n1 is W1 row c, n1 <= c < n1 + n2 is W2 row
 // c - n1.  K = 512 (the decoder's hidden size).  A workgroup: 64 rows x 192 columns (blockIdx.y: the 192-column
-// block); x is split once per workgroup into LDS planes a quarter of K at a time (linear_bf3_kernel's layout and
-// pipeline).  The 8 waves are 4 column groups of 48 x 2 halves of K: wave (cg, kh) takes columns 48 cg .. + 47
+// block); x is split once per workgroup into LDS planes a quarter of K at a time (Bf3XStage, as in
+// linear_bf3_kernel).  The 8 waves are 4 column groups of 48 x 2 halves of K: wave (cg, kh) takes columns 48 cg .. + 47
 // for ALL 64 rows (4 x 3 tiles, 72 MFMAs per 32-wide chunk) over the chunks of parity kh, splitting its own W
 // rows from a register ring, so every W element is split once per workgroup; the kh = 1 half is added to the
 // kh = 0 half through LDS at the end (the x planes' space), one fp32 add per output.  At config 2 (12,800 x 512
@@ -812,7 +747,7 @@ __global__ void __launch_bounds__(512) proj_bf3_sk_kernel(
     int n2, float* __restrict__ y, int64_t y_ld, int64_t R) {
   constexpr int K = 512, NQ = K / kBf3QK, NC = kBf3QK / 32, kP = 2, NH = NQ * NC;
   static_assert(NC == 2 * kP, "one ring slot per chunk parity step");
-  __shared__ __attribute__((aligned(16))) uint32_t xs[2 * 3 * kBf3Plane / 2];
+  __shared__ __attribute__((aligned(16))) uint32_t xs[2 * kBf3Buf];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int q = lane >> 4, l16 = lane & 15;
   const int kh = wv & 1, cg = wv >> 1;
@@ -831,83 +766,38 @@ __global__ void __launch_bounds__(512) proj_bf3_sk_kernel(
   for (int p = 0; p < kP; ++p)
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      wb[p][j][0] = *reinterpret_cast<const float4*>(wl[j] + 32 * (2 * p + kh));
-      wb[p][j][1] = *reinterpret_cast<const float4*>(wl[j] + 32 * (2 * p + kh) + 4);
+      wb[p][j][0] = bf3_ldw<false>(wl[j] + 32 * (2 * p + kh));
+      wb[p][j][1] = bf3_ldw<false>(wl[j] + 32 * (2 * p + kh) + 4);
     }
-  const int srow = t >> 3, sq = 2 * (t & 7);
-  const float* xsrc = x + (r0 + srow < R ? r0 + srow : R - 1) * x_ld + 8 * sq;  // rows >= R: never stored
-  float4 xv[4];
-  auto load_quarter = [&](int qt) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) xv[i] = *reinterpret_cast<const float4*>(xsrc + kBf3QK * qt + 4 * i);
-  };
-  auto store_quarter = [&](int buf) {
-    uint32_t* base = xs + buf * (3 * kBf3Plane / 2) + srow * (kBf3QK / 2);
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      u32x4_t hq, mq, lq;
-      split_bf16x3(xv[2 * e], xv[2 * e + 1], hq, mq, lq);
-      const int pos = 4 * ((sq + e) ^ (srow & 15));  // uint32 offset of the quad
-      *reinterpret_cast<u32x4_t*>(base + pos) = hq;
-      *reinterpret_cast<u32x4_t*>(base + kBf3Plane / 2 + pos) = mq;
-      *reinterpret_cast<u32x4_t*>(base + kBf3Plane + pos) = lq;
-    }
-  };
-  load_quarter(0);
-  store_quarter(0);
-  load_quarter(1);
-  store_quarter(1);
-  load_quarter(2);  // in flight under quarter 0
-  __syncthreads();
+  Bf3XStage xst(x, x_ld, r0, R);
+  xst.prologue(xs);
   f32x4_t acc[4][3];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
   for (int qt = 0; qt < NQ; ++qt) {
-    const uint32_t* xb = xs + (qt & 1) * (3 * kBf3Plane / 2) + l16 * (kBf3QK / 2);  // row 16 i + l16: row & 15 = l16
 #pragma unroll
     for (int p = 0; p < kP; ++p) {
       const int c = 2 * p + kh, h = qt * NC + c;
-      const int pos = 4 * ((4 * c + q) ^ l16);
       u32x4_t xh[4], xm[4], xlo[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const uint32_t* r = xb + 16 * i * (kBf3QK / 2) + pos;
-        xh[i] = *reinterpret_cast<const u32x4_t*>(r);
-        xm[i] = *reinterpret_cast<const u32x4_t*>(r + kBf3Plane / 2);
-        xlo[i] = *reinterpret_cast<const u32x4_t*>(r + kBf3Plane);
-      }
+      bf3_x_fragments(xs, qt, c, q, l16, xh, xm, xlo);
       const int hn = h + 2 * kP < NH ? h + 2 * kP : NH - 2 + kh;  // clamped: the same loads every iteration
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         u32x4_t wh, wm, wlo;
         split_bf16x3(wb[p][j][0], wb[p][j][1], wh, wm, wlo);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {  // small terms first
-          f32x4_t a = acc[i][j];
-          a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xm[i]), as_bf16x8(wm), a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xlo[i]), as_bf16x8(wh), a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xh[i]), as_bf16x8(wlo), a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xm[i]), as_bf16x8(wh), a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xh[i]), as_bf16x8(wm), a, 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(xh[i]), as_bf16x8(wh), a, 0, 0, 0);
-        }
+        for (int i = 0; i < 4; ++i) acc[i][j] = mfma_bf3(xh[i], xm[i], xlo[i], wh, wm, wlo, acc[i][j]);
       }
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        wb[p][j][0] = *reinterpret_cast<const float4*>(wl[j] + 32 * hn);
-        wb[p][j][1] = *reinterpret_cast<const float4*>(wl[j] + 32 * hn + 4);
+        wb[p][j][0] = bf3_ldw<false>(wl[j] + 32 * hn);
+        wb[p][j][1] = bf3_ldw<false>(wl[j] + 32 * hn + 4);
       }
       __builtin_amdgcn_sched_barrier(0);  // keep the refill here (the scheduler would sink it to its use)
     }
-    if (qt + 1 < NQ) {
-      __syncthreads();  // buffer qt & 1 fully read; the previous quarter's split writes visible
-      if (qt + 2 < NQ) {
-        store_quarter(qt & 1);  // quarter qt + 2
-        if (qt + 3 < NQ) load_quarter(qt + 3);
-      }
-    }
+    xst.advance(xs, qt, NQ);
   }
   // the kh = 1 half through LDS ([cg][48 values][64 lanes] floats in the x planes' space)
   __syncthreads();
@@ -955,22 +845,6 @@ constexpr int kWgN = 128, kWgR = 32, kWgBufs = 1;
 // conflict-free
 __device__ __forceinline__ int wgrad_quad(int col, int q) {
   return col * (kWgR / 8) + (q ^ ((0x78 >> (2 * ((col >> 2) & 3))) & 3) ^ ((col >> 1) & 1));
-}
-// split_bf16x3 with the two exact residual subtractions on packed fp32 (v_pk_add_f32): the same bits
-typedef float f32x2v_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void wgrad_split(const float* v, u32x4_t& hi, u32x4_t& mid, u32x4_t& lo) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const uint32_t u0 = __float_as_uint(v[2 * e]), u1 = __float_as_uint(v[2 * e + 1]);
-    const f32x2v_t x = {v[2 * e], v[2 * e + 1]};
-    const f32x2v_t h = {__uint_as_float(u0 & 0xffff0000u), __uint_as_float(u1 & 0xffff0000u)};
-    const f32x2v_t r = x - h;  // exact
-    const uint32_t m0 = __float_as_uint(r.x) & 0xffff0000u, m1 = __float_as_uint(r.y) & 0xffff0000u;
-    const f32x2v_t l = r - (f32x2v_t){__uint_as_float(m0), __uint_as_float(m1)};  // exact
-    hi[e] = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
-    mid[e] = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
-    lo[e] = __builtin_amdgcn_perm(__float_as_uint(l.y), __float_as_uint(l.x), 0x07060302u);
-  }
 }
 template <int WM>  // m-tiles per wave: the workgroup's dW tile is 64 WM x 128
 __global__ void __launch_bounds__(256) wgrad_bf3_kernel(const float* __restrict__ dy, int64_t dy_ld,
@@ -1025,7 +899,7 @@ __global__ void __launch_bounds__(256) wgrad_bf3_kernel(const float* __restrict_
     u32x4_t hi, mi, lo;
 #pragma unroll
     for (int h = 0; h < WM; ++h) {
-      wgrad_split(v.a[h], hi, mi, lo);
+      split_bf16x3_pk(v.a[h], hi, mi, lo);
       const int qa = wgrad_quad(am, ag + 4 / WM * h);
       reinterpret_cast<u32x4_t*>(la[buf][0])[qa] = hi;
       reinterpret_cast<u32x4_t*>(la[buf][1])[qa] = mi;
@@ -1033,7 +907,7 @@ __global__ void __launch_bounds__(256) wgrad_bf3_kernel(const float* __restrict_
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      wgrad_split(v.b[h], hi, mi, lo);
+      split_bf16x3_pk(v.b[h], hi, mi, lo);
       const int qb = wgrad_quad(bn, bg + 2 * h);
       reinterpret_cast<u32x4_t*>(lb[buf][0])[qb] = hi;
       reinterpret_cast<u32x4_t*>(lb[buf][1])[qb] = mi;
@@ -1062,15 +936,7 @@ __global__ void __launch_bounds__(256) wgrad_bf3_kernel(const float* __restrict_
       const u32x4_t bm = reinterpret_cast<const u32x4_t*>(lb[buf][1])[qb];
       const u32x4_t bl = reinterpret_cast<const u32x4_t*>(lb[buf][2])[qb];
 #pragma unroll
-      for (int u = 0; u < WM; ++u) {
-        f32x4_t a = acc[u][j];  // small terms first
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(am_[u]), as_bf16x8(bm), a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(al[u]), as_bf16x8(bh), a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(ah[u]), as_bf16x8(bl), a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(am_[u]), as_bf16x8(bh), a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(ah[u]), as_bf16x8(bm), a, 0, 0, 0);
-        acc[u][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(ah[u]), as_bf16x8(bh), a, 0, 0, 0);
-      }
+      for (int u = 0; u < WM; ++u) acc[u][j] = mfma_bf3(ah[u], am_[u], al[u], bh, bm, bl, acc[u][j]);
     }
   };
   // chunk k's loads land in register set k & 1; iteration c: MFMAs on the LDS tile, chunk c + 1 into LDS behind a
@@ -1217,10 +1083,8 @@ int ddsp_hip_layer_norm_leaky_relu(const float* x, int64_t x_ld, const float* w1
     return DDSP_HIP_ERANGE;  // callers keep torch's LayerNorm + LeakyReLU
   const dim3 grid((unsigned)((rows + 3) / 4));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (cols == 512)
-    hipLaunchKernelGGL(ln_leaky_kernel<2>, grid, dim3(256), 0, st, x, x_ld, w1, b1, gamma, beta, eps, slope, y, y_ld, rows);
-  else
-    hipLaunchKernelGGL(ln_leaky_kernel<4>, grid, dim3(256), 0, st, x, x_ld, w1, b1, gamma, beta, eps, slope, y, y_ld, rows);
+  const auto kern = cols == 512 ? ln_leaky_kernel<2> : ln_leaky_kernel<4>;
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, x, x_ld, w1, b1, gamma, beta, eps, slope, y, y_ld, rows);
   return launch_status();
 }
 
@@ -1251,12 +1115,9 @@ int ddsp_hip_layer_norm_leaky_relu_backward(const float* x, int64_t x_ld, const 
   float* part = params ? reinterpret_cast<float*>(ws) : nullptr;
   const int64_t need = (rows + 3) / 4;
   const unsigned grid = (unsigned)std::min<int64_t>(kLnBwdGrid, need);
-  if (cols == 512)
-    hipLaunchKernelGGL(ln_leaky_bwd_kernel<2>, dim3(grid), dim3(256), 0, st, x, x_ld, gamma, beta, eps, slope, grad_y,
-                       dy_ld, grad_x, dx_ld, part, rows);
-  else
-    hipLaunchKernelGGL(ln_leaky_bwd_kernel<4>, dim3(grid), dim3(256), 0, st, x, x_ld, gamma, beta, eps, slope, grad_y,
-                       dy_ld, grad_x, dx_ld, part, rows);
+  const auto kern = cols == 512 ? ln_leaky_bwd_kernel<2> : ln_leaky_bwd_kernel<4>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, x, x_ld, gamma, beta, eps, slope, grad_y, dy_ld, grad_x, dx_ld,
+                     part, rows);
   if (params)
     hipLaunchKernelGGL(ln_leaky_bwd_sum_kernel, dim3((unsigned)((2 * cols + 63) / 64)), dim3(256), 0, st, part,
                        (int)grid, (int)cols, grad_gamma, grad_beta);
@@ -1281,25 +1142,17 @@ int ddsp_hip_mlp_block(const float* x, int64_t x_ld, int64_t in_features, const 
   const dim3 grid((unsigned)((rows + kMlpRows - 1) / kMlpRows));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool x16 = x_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  if (in_features == kMlpResK && x16 && (flags & DDSP_HIP_MLP_EXACT_F32) == 0 && vec == 4)  // the decoder's blocks
-    hipLaunchKernelGGL((linear_bf3_kernel<2, kMlpResK, true>), grid, dim3(512), 0, st, x, x_ld, w, w_ld, bias, e0, e1,
-                       e_ld, gamma, beta, eps, slope, y, y_ld, rows);
-  else if (in_features == kMlpResK && x16 && (flags & DDSP_HIP_MLP_EXACT_F32) == 0 && w_ld % 2 == 0 &&
-           (reinterpret_cast<uintptr_t>(w) & 7) == 0)  // W rows 8-byte aligned: the out_mlp's first block
-    hipLaunchKernelGGL((linear_bf3_kernel<2, kMlpResK, true, true>), grid, dim3(512), 0, st, x, x_ld, w, w_ld, bias, e0,
-                       e1, e_ld, gamma, beta, eps, slope, y, y_ld, rows);
-  else if (in_features == kMlpResK && vec == 4)  // x resident, W streamed to registers, f32 MFMA
-    hipLaunchKernelGGL(mlp_block_res_kernel<4>, grid, dim3(512), 0, st, x, x_ld, w, w_ld, bias, e0, e1, e_ld, gamma,
+  const bool w8 = w_ld % 2 == 0 && (reinterpret_cast<uintptr_t>(w) & 7) == 0;
+  if (in_features == kBf3MlpK && x16 && (flags & DDSP_HIP_MLP_EXACT_F32) == 0 && (vec == 4 || w8)) {
+    // the decoder's blocks; W rows only 8-byte aligned: the out_mlp's first block
+    const auto kern = vec == 4 ? linear_bf3_kernel<2, kBf3MlpK, true> : linear_bf3_kernel<2, kBf3MlpK, true, true>;
+    hipLaunchKernelGGL(kern, grid, dim3(512), 0, st, x, x_ld, w, w_ld, bias, e0, e1, e_ld, gamma, beta, eps, slope, y,
+                       y_ld, rows);
+  } else {  // the f32-input MFMA: any K, and DDSP_HIP_MLP_EXACT_F32
+    const auto kern = vec == 4 ? mlp_block_kernel<4> : vec == 2 ? mlp_block_kernel<2> : mlp_block_kernel<1>;
+    hipLaunchKernelGGL(kern, grid, dim3(512), 0, st, x, x_ld, (int)in_features, w, w_ld, bias, e0, e1, e_ld, gamma,
                        beta, eps, slope, y, y_ld, rows);
-  else if (vec == 4)
-    hipLaunchKernelGGL(mlp_block_kernel<4>, grid, dim3(512), 0, st, x, x_ld, (int)in_features, w, w_ld, bias, e0, e1,
-                       e_ld, gamma, beta, eps, slope, y, y_ld, rows);
-  else if (vec == 2)
-    hipLaunchKernelGGL(mlp_block_kernel<2>, grid, dim3(512), 0, st, x, x_ld, (int)in_features, w, w_ld, bias, e0, e1,
-                       e_ld, gamma, beta, eps, slope, y, y_ld, rows);
-  else
-    hipLaunchKernelGGL(mlp_block_kernel<1>, grid, dim3(512), 0, st, x, x_ld, (int)in_features, w, w_ld, bias, e0, e1,
-                       e_ld, gamma, beta, eps, slope, y, y_ld, rows);
+  }
   return launch_status();
 }
 
@@ -1315,15 +1168,12 @@ int ddsp_hip_linear(const float* x, int64_t x_ld, int64_t in_features, const flo
     return DDSP_HIP_ERANGE;  // callers keep their library GEMM
   const dim3 grid((unsigned)((rows + kMlpRows - 1) / kMlpRows), (unsigned)(out_features / kMlpN));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (in_features == 1536)  // the GRU input gradient (3 gates x 512 -> 1024 under autograd)
-    hipLaunchKernelGGL((linear_bf3_kernel<2, 1536, false>), grid, dim3(512), 0, st, x, x_ld, w, w_ld, bias, nullptr,
-                       nullptr, 0, nullptr, nullptr, 0.0f, 0.0f, y, y_ld, rows);
-  else if (in_features == 1024)
-    hipLaunchKernelGGL((linear_bf3_kernel<2, 1024, false>), grid, dim3(512), 0, st, x, x_ld, w, w_ld, bias, nullptr,
-                       nullptr, 0, nullptr, nullptr, 0.0f, 0.0f, y, y_ld, rows);
-  else
-    hipLaunchKernelGGL((linear_bf3_kernel<2, 512, false>), grid, dim3(512), 0, st, x, x_ld, w, w_ld, bias, nullptr,
-                       nullptr, 0, nullptr, nullptr, 0.0f, 0.0f, y, y_ld, rows);
+  // 1536: the GRU input gradient (3 gates x 512 -> 1024 under autograd)
+  const auto kern = in_features == 1536   ? linear_bf3_kernel<2, 1536, false>
+                    : in_features == 1024 ? linear_bf3_kernel<2, 1024, false>
+                                          : linear_bf3_kernel<2, 512, false>;
+  hipLaunchKernelGGL(kern, grid, dim3(512), 0, st, x, x_ld, w, w_ld, bias, nullptr, nullptr, 0, nullptr, nullptr, 0.0f,
+                     0.0f, y, y_ld, rows);
   return launch_status();
 }
 
@@ -1363,12 +1213,9 @@ int ddsp_hip_linear_weight_grad(const float* grad_y, int64_t dy_ld, const float*
   if (rows > 0 && (!grad_y || !x || dy_ld < out_features || x_ld < in_features)) return DDSP_HIP_EINVAL;
   if (out_features > (1 << 24) || in_features > (1 << 24)) return DDSP_HIP_ERANGE;  // callers keep their library GEMM
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (rows == 0) {
-    for (int64_t m = 0; m < out_features; ++m)
-      if (hipMemsetAsync(grad_w + m * dw_ld, 0, sizeof(float) * (size_t)in_features, st) != hipSuccess)
-        return DDSP_HIP_ELAUNCH;
-    return DDSP_HIP_OK;
-  }
+  if (rows == 0)  // dW = 0: its in_features columns of every row, whatever lies between the rows untouched
+    return hipMemset2DAsync(grad_w, sizeof(float) * (size_t)dw_ld, 0, sizeof(float) * (size_t)in_features,
+                            (size_t)out_features, st) == hipSuccess ? DDSP_HIP_OK : DDSP_HIP_ELAUNCH;
   const int M = (int)out_features, N = (int)in_features;
   const WgradShape g = wgrad_shape(M, N);
   const int64_t chunks = (rows + kWgR - 1) / kWgR;
@@ -1379,12 +1226,9 @@ int ddsp_hip_linear_weight_grad(const float* grad_y, int64_t dy_ld, const float*
   if (!ws || ws_bytes < ddsp_hip_linear_weight_grad_workspace_size(rows, out_features, in_features))
     return DDSP_HIP_EWORKSPACE;
   float* part = reinterpret_cast<float*>(ws);
-  if (g.wm == 2)
-    hipLaunchKernelGGL(wgrad_bf3_kernel<2>, dim3((unsigned)(tiles * g.S)), dim3(256), 0, st, grad_y, dy_ld, x, x_ld,
-                       part, rows, g.Mp, g.Np, g.S, per, M, N);
-  else
-    hipLaunchKernelGGL(wgrad_bf3_kernel<1>, dim3((unsigned)(tiles * g.S)), dim3(256), 0, st, grad_y, dy_ld, x, x_ld,
-                       part, rows, g.Mp, g.Np, g.S, per, M, N);
+  const auto kern = g.wm == 2 ? wgrad_bf3_kernel<2> : wgrad_bf3_kernel<1>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * g.S)), dim3(256), 0, st, grad_y, dy_ld, x, x_ld, part, rows, g.Mp,
+                     g.Np, g.S, per, M, N);
   const int vec = !(dw_ld & 3) && !(reinterpret_cast<uintptr_t>(grad_w) & 15);
   hipLaunchKernelGGL(wgrad_sum_kernel, dim3((unsigned)(((int64_t)M * g.Np / 4 + 255) / 256)), dim3(256), 0, st, part,
                      g.S, g.Mp, g.Np, M, N, grad_w, dw_ld, vec);

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 
+#include "bf16x3.h"
 #include "common.h"
 
 namespace ddsp {
@@ -28,6 +29,39 @@ constexpr int kHS = 4;    // hidden units per workgroup
 // else (32, 16) (hidden % 64 == 0).
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// The cell (the header's equations) for one (item, unit), given the input projection's gates x*, the
+// recurrent sums h* = W_h* h_{t-1}, the recurrent biases and h_{t-1}.  Every forward kernel calls this one
+// definition, so the step, persistent-epilogue and rescue values agree bit for bit wherever their sums do.
+struct GruCell {
+  float r, z, n, hbn, h;  // hbn = W_hn h + b_hn (saved for the backward), h = h_t
+};
+__device__ __forceinline__ GruCell gru_cell(float xr, float xz, float xn, float hr, float hz, float hn, float br,
+                                            float bz, float bn, float hprev) {
+  GruCell c;
+  c.r = sigmoidf_(xr + (hr + br));
+  c.z = sigmoidf_(xz + (hz + bz));
+  c.hbn = hn + bn;
+  c.n = tanhf(xn + c.r * c.hbn);
+  c.h = (1.0f - c.z) * c.n + c.z * hprev;
+  return c;
+}
+
+// The cell's gradient for one (item, unit) from its saved r, z, n, hn = W_hn h_{t-1} + b_hn, its h_{t-1} and
+// the total dh reaching h_t (the BPTT equations below): dxp_t = (dar, daz, dan), dG_t = (dar, daz, dgn).
+struct GruCellGrad {
+  float dar, daz, dan, dgn;  // dgn = dan r
+};
+__device__ __forceinline__ GruCellGrad gru_cell_grad(float r, float z, float n, float hn, float hprev, float dh) {
+  const float dn = dh * (1.0f - z);
+  const float dz = dh * (hprev - n);
+  GruCellGrad g;
+  g.dan = dn * (1.0f - n * n);
+  g.daz = dz * z * (1.0f - z);
+  g.dar = g.dan * hn * r * (1.0f - r);
+  g.dgn = g.dan * r;
+  return g;
+}
 
 // grid (H / kHS, ceil(B / kBS)); LDS: W slice [3 kHS][H] + per-wave partials [kNT / 64][3 kHS][kBS].
 // A step is a chain of dependent latencies, not work (100 MFLOP per step at config 2), so every
@@ -137,18 +171,15 @@ __global__ void __launch_bounds__(kBS * kKC) gru_step_kernel(const float* __rest
       hz += part[(w * R + 1 * kHS + u) * kBS + bb];
       hn += part[(w * R + 2 * kHS + u) * kBS + bb];
     }
-    const float r = sigmoidf_(ex_r + (hr + eb_r));
-    const float z = sigmoidf_(ex_z + (hz + eb_z));
-    const float n = tanhf(ex_n + r * (hn + eb_n));
-    const float hn_t = (1.0f - z) * n + z * ehp;
-    h_out[(int64_t)ebi * ho_ld + ej] = hn_t;
-    if (h_copy) h_copy[(int64_t)ebi * H + ej] = hn_t;  // the last step's h_T, [B, H]
+    const GruCell c = gru_cell(ex_r, ex_z, ex_n, hr, hz, hn, eb_r, eb_z, eb_n, ehp);
+    h_out[(int64_t)ebi * ho_ld + ej] = c.h;
+    if (h_copy) h_copy[(int64_t)ebi * H + ej] = c.h;  // the last step's h_T, [B, H]
     if (save) {  // training: r, z, n and W_hn h + b_hn of this step, [4][B, T, H] (same row layout as h_out)
       float* sv = save + (int64_t)ebi * ho_ld + ej;
-      sv[0] = r;
-      sv[save_plane] = z;
-      sv[2 * save_plane] = n;
-      sv[3 * save_plane] = hn + eb_n;
+      sv[0] = c.r;
+      sv[save_plane] = c.z;
+      sv[2 * save_plane] = c.n;
+      sv[3 * save_plane] = c.hbn;
     }
   }
 }
@@ -172,7 +203,7 @@ __global__ void __launch_bounds__(kBS * kKC) gru_step_kernel(const float* __rest
 // The h_t addresses are fresh every step (the output sequence), so no cache holds an older copy.  Every
 // wait is bounded: a launch whose workgroups cannot all be resident at once sets an abort word and ends
 // (garbage out) instead of hanging.  The slot's 48 rows of W_hh (gates r, z, n of its 16 units) live in
-// REGISTERS for the whole sequence, split once into three bf16 terms (common.h split_bf16x3) as the A
+// REGISTERS for the whole sequence, split once into three bf16 terms (bf16x3.h split_bf16x3) as the A
 // fragments of v_mfma_f32_16x16x32_bf16: wave w owns k in [64 w, 64 w + 64) — two 32-wide chunks — and per
 // gate one 16 x 32 tile (rows = the slot's 16 units) per chunk.  Per step h_{t-1} of the group's items is
 // staged once into LDS (16 KB); each wave splits its 64 k of the 8 items into B fragments (items are the
@@ -310,15 +341,8 @@ __device__ __forceinline__ void gru_persistent_body(const float* __restrict__ xp
       u32x4_t hb[3];
       split_bf16x3(a, b, hb[0], hb[1], hb[2]);
 #pragma unroll
-      for (int gt = 0; gt < 3; ++gt) {  // small terms first
-        f32x4_t v = acc[gt];
-        v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[gt][c][1]), as_bf16x8(hb[1]), v, 0, 0, 0);
-        v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[gt][c][2]), as_bf16x8(hb[0]), v, 0, 0, 0);
-        v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[gt][c][0]), as_bf16x8(hb[2]), v, 0, 0, 0);
-        v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[gt][c][1]), as_bf16x8(hb[0]), v, 0, 0, 0);
-        v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[gt][c][0]), as_bf16x8(hb[1]), v, 0, 0, 0);
-        acc[gt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[gt][c][0]), as_bf16x8(hb[0]), v, 0, 0, 0);
-      }
+      for (int gt = 0; gt < 3; ++gt)
+        acc[gt] = mfma_bf3(wa[gt][c][0], wa[gt][c][1], wa[gt][c][2], hb[0], hb[1], hb[2], acc[gt]);
     }
     // acc[gt][e]: unit 4 q + e, item l16 -> part[w][item][gt * 16 + unit]
     if (l16 < kPI) {
@@ -336,11 +360,8 @@ __device__ __forceinline__ void gru_persistent_body(const float* __restrict__ xp
         hz += part[v][ei][kPU + eu];
         hn += part[v][ei][2 * kPU + eu];
       }
-      const float r = sigmoidf_(exr + (hr + ebr));
-      const float z = sigmoidf_(exz + (hz + ebz));
-      const float hbn = hn + ebn;
-      const float n = tanhf(exn + r * hbn);
-      const float hnew = (1.0f - z) * n + z * ehp;
+      const GruCell cell = gru_cell(exr, exz, exn, hr, hz, hn, ebr, ebz, ebn, ehp);
+      const float r = cell.r, z = cell.z, n = cell.n, hbn = cell.hbn, hnew = cell.h;
       const int64_t oi = (int64_t)eb * item_stride + (int64_t)t * kPH + u0 + eu;
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(hnew), rout, (int)(oi * 4), 0, kStoreAux);
       if (save) {
@@ -469,18 +490,16 @@ __global__ void __launch_bounds__(512) gru_rescue_kernel(const float* __restrict
     }
     __syncthreads();
     const float* xr = xp + ((int64_t)b * T + t) * 3 * kPH;
-    const float r = sigmoidf_(xr[tid] + (rows[tid] + br));
-    const float z = sigmoidf_(xr[kPH + tid] + (rows[kPH + tid] + bz));
-    const float hn = rows[2 * kPH + tid];
-    const float n = tanhf(xr[2 * kPH + tid] + r * (hn + bn));
-    hp = (1.0f - z) * n + z * hp;
+    const GruCell cell = gru_cell(xr[tid], xr[kPH + tid], xr[2 * kPH + tid], rows[tid], rows[kPH + tid],
+                                  rows[2 * kPH + tid], br, bz, bn, hp);
+    hp = cell.h;
     const int64_t oi = ((int64_t)b * T + t) * kPH + tid;
     out[oi] = hp;
     if (save) {
-      save[oi] = r;
-      save[plane + oi] = z;
-      save[2 * plane + oi] = n;
-      save[3 * plane + oi] = hn + bn;
+      save[oi] = cell.r;
+      save[plane + oi] = cell.z;
+      save[2 * plane + oi] = cell.n;
+      save[3 * plane + oi] = cell.hbn;
     }
     hs[tid] = hp;  // every read of h_{t-1} (the row pass) is behind the barrier above
     __syncthreads();
@@ -506,15 +525,11 @@ __global__ void __launch_bounds__(512) gru_rescue_kernel(const float* __restrict
 __device__ __forceinline__ void gru_bwd_elem_v(float r, float z, float n, float hn, int64_t idx, float hprev,
                                                float dh, float* __restrict__ dxp, int64_t xi, int H,
                                                float* __restrict__ dgn) {
-  const float dn = dh * (1.0f - z);
-  const float dz = dh * (hprev - n);
-  const float dan = dn * (1.0f - n * n);
-  const float daz = dz * z * (1.0f - z);
-  const float dar = dan * hn * r * (1.0f - r);
-  dxp[xi] = dar;
-  dxp[xi + H] = daz;
-  dxp[xi + 2 * H] = dan;
-  dgn[idx] = dan * r;
+  const GruCellGrad g = gru_cell_grad(r, z, n, hn, hprev, dh);
+  dxp[xi] = g.dar;
+  dxp[xi + H] = g.daz;
+  dxp[xi + 2 * H] = g.dan;
+  dgn[idx] = g.dgn;
 }
 
 __device__ __forceinline__ void gru_bwd_elem(const float* __restrict__ save, int64_t plane, int64_t idx, float hprev,
@@ -805,12 +820,9 @@ __global__ void __launch_bounds__(512) gru_bptt_persistent_kernel(
   };
   auto elem = [&](int t, float dh, const Elem& ev) {
     const int64_t idx = ((int64_t)eb * T + t) * kPH + j;
-    const float r = ev.r, z = ev.z, n = ev.n, hn = ev.hn, hprev = ev.hprev;
-    const float dn = dh * (1.0f - z);
-    const float dz = dh * (hprev - n);
-    const float dan = dn * (1.0f - n * n);
-    const float daz = dz * z * (1.0f - z);
-    const float dar = dan * hn * r * (1.0f - r);
+    const GruCellGrad cg = gru_cell_grad(ev.r, ev.z, ev.n, ev.hn, ev.hprev, dh);
+    // (the hand-off stores below stand as they were; their dan * r is cg.dgn's expression)
+    const float dar = cg.dar, daz = cg.daz, dan = cg.dan, r = ev.r;
     const int xo = (int)((((int64_t)eb * T + t) * 3 * kPH + j) * 4);
     const int go = (int)(idx * 4);
     if (local) {
@@ -871,12 +883,7 @@ __global__ void __launch_bounds__(512) gru_bptt_persistent_kernel(
       }
       u32x4_t gb[3];
       split_bf16x3(a, b, gb[0], gb[1], gb[2]);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[c][1]), as_bf16x8(gb[1]), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[c][2]), as_bf16x8(gb[0]), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[c][0]), as_bf16x8(gb[2]), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[c][1]), as_bf16x8(gb[0]), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[c][0]), as_bf16x8(gb[1]), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(wa[c][0]), as_bf16x8(gb[0]), acc, 0, 0, 0);
+      acc = mfma_bf3(wa[c][0], wa[c][1], wa[c][2], gb[0], gb[1], gb[2], acc);
     }
     if (l16 < kPI)  // acc[e]: unit 4 q + e, item l16
       *reinterpret_cast<float4*>(&part[w][l16][4 * q]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
@@ -914,19 +921,15 @@ __global__ void __launch_bounds__(512) gru_bwd_rescue_kernel(
     const int64_t idx = ((int64_t)b * T + t) * kPH + j;
     const float r = save[idx], z = save[plane + idx], n = save[2 * plane + idx], hn = save[3 * plane + idx];
     const float hprev = t >= 1 ? out[idx - kPH] : (h0 ? h0[(int64_t)b * kPH + j] : 0.0f);
-    const float dn = dh * (1.0f - z);
-    const float dz = dh * (hprev - n);
-    const float dan = dn * (1.0f - n * n);
-    const float daz = dz * z * (1.0f - z);
-    const float dar = dan * hn * r * (1.0f - r);
+    const GruCellGrad g = gru_cell_grad(r, z, n, hn, hprev, dh);
     const int64_t xi = ((int64_t)b * T + t) * 3 * kPH + j;
-    dxp[xi] = dar;
-    dxp[xi + kPH] = daz;
-    dxp[xi + 2 * kPH] = dan;
-    dgn[idx] = dan * r;
-    gs[j] = dar;
-    gs[kPH + j] = daz;
-    gs[2 * kPH + j] = dan * r;
+    dxp[xi] = g.dar;
+    dxp[xi + kPH] = g.daz;
+    dxp[xi + 2 * kPH] = g.dan;
+    dgn[idx] = g.dgn;
+    gs[j] = g.dar;
+    gs[kPH + j] = g.daz;
+    gs[2 * kPH + j] = g.dgn;
     return z;
   };
   float dh = (dout ? dout[((int64_t)b * T + (T - 1)) * kPH + j] : 0.0f) + (dh_last ? dh_last[(int64_t)b * kPH + j] : 0.0f);

@@ -269,8 +269,8 @@ int ddsp_hip_dense_rows(const ddsp_hip_dense_problem* problems, int n_problems, 
  * The Linear's arithmetic: at in_features 512 with 16-byte aligned rows (the decoder's blocks) both operands
  * split exactly into three bf16 terms and summed as six bf16 products per term pair on the bf16 matrix
  * cores — fp32-accurate (the dropped terms are ~2^-24 of each product), not the same bits as an fp32 fma
- * chain; flags = DDSP_HIP_MLP_EXACT_F32 (or any other shape) takes the f32-input MFMA, whose sums are
- * exactly k-ordered fp32 fma chains. */
+ * chain; flags = DDSP_HIP_MLP_EXACT_F32 (or any other shape) takes the f32-input MFMA (one kernel for every
+ * K, x and W staged through LDS), whose sums are exactly k-ordered fp32 fma chains. */
 enum { DDSP_HIP_MLP_EXACT_F32 = 1 };
 int ddsp_hip_mlp_block(const float* x, int64_t x_ld, int64_t in_features, const float* w, int64_t w_ld,
                        const float* bias, const float* e0, const float* e1, int64_t e_ld, const float* gamma,

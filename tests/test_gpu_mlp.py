@@ -132,7 +132,7 @@ def test_projections_read_live_parameters(dd):
 
 
 def _mlp_block_raw(dd, x, x_ld, lin, ln, rows, e0=None, e1=None, flags=0):
-    """ddsp_hip_mlp_block on a raw [rows, x_ld] buffer (x_ld > K selects the staged, unaligned-load form)."""
+    """ddsp_hip_mlp_block on a raw [rows, x_ld] buffer (x_ld = 514 selects the f32 form with 8-byte loads)."""
     L = dd._lib
     y = torch.empty(rows, 512, device="cuda")
     L.call("mlp_block", L.ptr(x), x_ld, 512, L.ptr(lin.weight), lin.weight.shape[1], L.ptr(lin.bias), L.ptr(e0),
@@ -142,11 +142,11 @@ def _mlp_block_raw(dd, x, x_ld, lin, ln, rows, e0=None, e1=None, flags=0):
 
 
 @pytest.mark.parametrize("rows,extras", [(12800, False), (1000, True), (65, False), (1, True)])
-def test_mlp_block_resident_form_equals_staged_form(dd, rows, extras):
-    """K = 512 with MLP_EXACT_F32 runs the x-resident f32 kernel (x tile in LDS, W streamed to registers, no
-    barrier in the K loop); an x buffer with row stride 514 floats runs the staged kernel.  Same MFMA operands
-    in the same k order: identical outputs, bit for bit, incl. the out_mlp's two extra columns.  The default
-    (bf16x3) form matches torch at the same tolerance."""
+def test_mlp_block_f32_form_load_widths_agree(dd, rows, extras):
+    """K = 512 with MLP_EXACT_F32 runs the staged f32-input MFMA kernel with 16-byte loads (8-byte ones where the
+    out_mlp's 514-float W rows allow no more); an x buffer with row stride 514 floats runs the same kernel with
+    8-byte loads of x and W.  Same MFMA operands in the same k order: identical outputs, bit for bit, incl. the
+    out_mlp's two extra columns.  The default (bf16x3) form matches torch at the same tolerance."""
     torch.manual_seed(rows)
     lin = torch.nn.Linear(514 if extras else 512, 512).cuda()
     ln = torch.nn.LayerNorm(512).cuda()

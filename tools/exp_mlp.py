@@ -1,5 +1,6 @@
-"""mlp_block at config 2's shape (12,800 rows x 512 -> 512): the x-resident kernel (contiguous x) against the
-staged kernel (x rows 514 floats apart), device time per launch by HIP events over back-to-back launches."""
+"""mlp_block at config 2's shape (12,800 rows x 512 -> 512): the bf16x3 kernel against the f32-input MFMA kernel
+with 16-byte loads (MLP_EXACT_F32, contiguous x) and with 8-byte loads (x rows 514 floats apart), device time per
+launch by HIP events over back-to-back launches."""
 import json
 import os
 import sys
@@ -25,8 +26,8 @@ def run(buf, ld, flags):
 
 
 res = {}
-for name, buf, ld, fl in (("bf16x3", x, 512, 0), ("resident", x, 512, 1), ("staged", wide, 514, 0),
-                          ("bf16x3_2", x, 512, 0), ("resident2", x, 512, 1), ("staged2", wide, 514, 0)):
+for name, buf, ld, fl in (("bf16x3", x, 512, 0), ("f32", x, 512, 1), ("f32_ld8", wide, 514, 0),
+                          ("bf16x3_2", x, 512, 0), ("f32_2", x, 512, 1), ("f32_ld8_2", wide, 514, 0)):
     for _ in range(20):
         run(buf, ld, fl)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -37,7 +38,7 @@ for name, buf, ld, fl in (("bf16x3", x, 512, 0), ("resident", x, 512, 1), ("stag
     torch.cuda.synchronize()
     res[name + "_us"] = round(e0.elapsed_time(e1) / 50 * 1e3, 2)
 flop = 2.0 * rows * 512 * 512
-res["tflops_resident"] = round(flop / (res["resident_us"] * 1e-6) / 1e12, 1)
+res["tflops_f32"] = round(flop / (res["f32_us"] * 1e-6) / 1e12, 1)
 res["tflops_bf16x3"] = round(flop / (res["bf16x3_us"] * 1e-6) / 1e12, 1)
 print(json.dumps(res))
 

@@ -87,13 +87,23 @@ constexpr float kInv2PiLo = 6.42063824329852652e-09f;   // fl32(1/(2*pi) - kInv2
 // x/(2pi) reduced to revolutions: n = rint(x/(2pi)) by the shifter (|x/(2pi)| < 2^22 for
 // |x| < kFastArgLimit), then x*kInv2Pi - n formed exactly inside one fma (a single rounding
 // of a value <= 0.5) and the representation error of kInv2Pi added back by a second fma:
-// |y| <= 0.55, |error| <= ~3e-8 rev.  4 VALU ops.
-__device__ __forceinline__ float reduce_rev(float x) {
+// |y| <= 0.55, |error| <= ~3e-8 rev.  4 VALU ops: the shifter (rev_count) and the two fmas
+// (reduce_rev_by).
+__device__ __forceinline__ float rev_count(float x) {
   const float t = fmaf(x, kInv2Pi, kMagic);
-  const float n = t - kMagic;
+  return t - kMagic;
+}
+
+// x/(2pi) - n for a given integer n: the reduction's two fmas.  With n = rev_count(x) this is
+// reduce_rev; with the count of a nearby argument (synth_frame.hip: one count for a thread's four
+// consecutive samples) the product is still exact inside the first fma and only the magnitude at
+// which it rounds grows: |y| < 8 rounds to <= 2^-22 rev, and v_sin_f32 takes any |y| <= 256.
+__device__ __forceinline__ float reduce_rev_by(float x, float n) {
   const float y = fmaf(x, kInv2Pi, -n);
   return fmaf(x, kInv2PiLo, y);
 }
+
+__device__ __forceinline__ float reduce_rev(float x) { return reduce_rev_by(x, rev_count(x)); }
 
 // sin(2*pi*y) on the hardware sine (v_sin_f32 takes revolutions; it costs ~3 VALU issue
 // slots, measured).  With reduce_rev: |error| < 3.2e-7, rms 5.3e-8 vs the fp64 sine of the same

@@ -2,10 +2,11 @@
 // workgroup: harmonic controls + oscillator bank (modules.py:44-80), noise controls + filter
 // design + filtered noise (modules.py:111-128), and `signal = harmonic + noise`.
 //
-// Why fuse: the oscillator bank is VALU-bound (6 VALU ops + one hardware sine per sample x
-// harmonic) while the filtered-noise work is short, LDS- and latency-heavy phases.  In one
-// kernel the noise phases of some workgroups run beside the sine loops of others on the same
-// CU, the harmonic signal never makes an HBM round trip, and one launch replaces two.
+// Why fuse: the oscillator bank is VALU-bound (4.5 VALU ops + one hardware sine per sample x
+// harmonic; 6 where a frame keeps one revolution count per sample) while the filtered-noise work
+// is short, LDS- and latency-heavy phases.  In one kernel the noise phases of some workgroups run
+// beside the sine loops of others on the same CU, the harmonic signal never makes an HBM round
+// trip, and one launch replaces two.
 //
 // Mapping: thread t owns samples [4t, 4t+4) of the frame for both parts (bs <= 1024,
 // bs % 4 == 0), so the harmonic and noise values of a sample meet in registers.
@@ -36,6 +37,50 @@ __device__ __forceinline__ void osc_bank4(const float2* __restrict__ coef, int H
   }
 }
 
+// One revolution count per harmonic for the four consecutive samples of an aligned quad: each term still
+// reduces its own rounded product x_s = fl32(w_s (k+1)), but subtracts n = rint(x_ref / 2pi) of the quad's
+// reference sample instead of its own (common.h reduce_rev_by), so a quad issues one shifter per harmonic
+// instead of four: 18 VALU + 4 sines per harmonic instead of 24 + 4.  The reference is sample kRefSample = 1:
+// of the two middle samples (distance <= 2 to every other; 0 or 3 would make it 3) the one the numerics were
+// checked with.  Every form that has to give the same bits (the 4-samples-per-thread loop and the SPLIT
+// loop) takes this index.  |y_s| <= 0.5 + 2 H4 |dinc| / 2pi; frames where that bound is below
+// kSharedRevLimit take this loop (shared_rev_frame), where the first fma rounds at <= 2^-22 rev
+// (tools/sin_probe.hip: the hardware sine over |y| < 8), every other frame the per-sample loop.
+constexpr int kRefSample = 1;
+constexpr float kSharedRevLimit = 8.0f;
+
+__device__ __forceinline__ bool shared_rev_frame(float dinc, int H4) {
+  return 0.5f + 2.0f * (float)H4 * fabsf(dinc) * kInv2Pi < kSharedRevLimit;  // false for a NaN pitch
+}
+
+// x0 = a0 * c, x1 = a1 * c (the rounded fp32 products, v_mul_f32 as the compiler emits it) as one 8-byte
+// unit.  With one count per quad the scheduler starts the reference sample's chain early and drops the
+// other products, 4-byte encodings, in odd runs between the reduction's 8-byte instructions, which
+// pushes those off the loop's placement; in pairs the products keep every later address's
+// parity wherever they land.
+__device__ __forceinline__ void mul_pair(float a0, float a1, float c, float& x0, float& x1) {
+  asm("v_mul_f32_e32 %0, %2, %4\n\tv_mul_f32_e32 %1, %3, %4" : "=&v"(x0), "=v"(x1) : "v"(a0), "v"(a1), "v"(c));
+}
+
+__device__ __forceinline__ void osc_bank4_shared(const float2* __restrict__ coef, int H4, const float (&w)[4],
+                                                 float (&acc)[4]) {
+  const float4* coef2 = reinterpret_cast<const float4*>(coef);  // two harmonics per 16-byte LDS read
+  for (int k2 = 0; k2 < (H4 >> 1); k2 += 2) {  // 16 terms per iteration, as osc_bank4
+    const float4 c01 = coef2[k2], c23 = coef2[k2 + 1];
+    const float2 c[4] = {make_float2(c01.x, c01.y), make_float2(c01.z, c01.w), make_float2(c23.x, c23.y),
+                         make_float2(c23.z, c23.w)};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      float x[4];
+      mul_pair(w[0], w[1], c[u].x, x[0], x[1]);
+      mul_pair(w[2], w[3], c[u].x, x[2], x[3]);
+      const float n = rev_count(x[kRefSample]);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc[s] = fmaf(sin_rev(reduce_rev_by(x[s], n)), c[u].y, acc[s]);
+    }
+  }
+}
+
 // SPLIT (few-frame launches, e.g. the realtime stream's 4 frames per call): the workgroup has
 // G times the threads of one 4-samples-per-thread frame and the oscillator bank runs one sample
 // per thread, so one frame's latency is spread over G times the waves.
@@ -44,14 +89,13 @@ __device__ __forceinline__ void osc_bank4(const float2* __restrict__ coef, int H
 // at wave w0 of the workgroup) in the LDS region smem4; every wave of the workgroup calls it (its
 // barriers are workgroup barriers).  On return (true: the thread's samples j0..j0+3 are in the
 // frame) acc = harmonic, nz = filtered noise.
-// PAD: one s_nop ahead of the (non-SPLIT) sine loop where an instantiation needs it for the loop's fast
-// placement (phase 5; the controls-writing instantiations).  CTRL: also write the frame's controls
+// CTRL: also write the frame's controls
 // (the dicts DDSPDecoder.forward returns) to ctrl_out.  PREFIX: read the frame's phase prefix from
 // prefix[] (long renders) instead of summing the earlier frames; its own instantiations, so the
 // training / serving shapes run the code without the branch (1.9% of the kernel, same-box A/B).
 // CARRY: the item's phase at the start of the call (carry0, the realtime stream's running prefix) is added to
 // the frame's own prefix, so a stream of calls continues the oscillators of the call before.
-template <bool RNG, bool SPLIT, bool PAD, bool CTRL, bool PREFIX, bool CARRY = false>
+template <bool RNG, bool SPLIT, bool CTRL, bool PREFIX, bool CARRY = false>
 __device__ __forceinline__ bool frame_synth(
     const float* __restrict__ f0, const float* __restrict__ param, const float* __restrict__ mags,
     float bias, const float* __restrict__ noise, uint32_t k0, uint32_t k1, uint32_t off0, uint32_t off1,
@@ -223,6 +267,7 @@ __device__ __forceinline__ bool frame_synth(
   const bool active = j0 < bs;
   const double dinc = (double)phase_inc(pitch0, sr);
   j0_out = j0;
+  const bool shared = shared_rev_frame((float)dinc, H4);  // the same for the whole frame
   if (!SPLIT) {
     float w[4];
     bool fast = true;
@@ -233,13 +278,18 @@ __device__ __forceinline__ bool frame_synth(
       fast = fast && (fabsf(w[s]) * (float)H4 < kFastArgLimit);
     }
     // loop placement: the sine loop runs ~10% faster when its 8-byte instructions sit at odd dword
-    // addresses (tools/loop_align.py, pinned by tests/test_loop_align.py); PAD puts
-    // one dword of padding after an 8-byte alignment point ahead of it where an instantiation needs
-    // it (the alignment makes the placement independent of the code laid out before the kernel)
-    if constexpr (PAD) asm volatile(".p2align 3\n s_nop 0");
-    else asm volatile(".p2align 3");
+    // addresses (tools/loop_align.py, pinned by tests/test_loop_align.py).  Each of the
+    // two throughput loops sits behind an 8-byte alignment point of its own (which makes the placement
+    // independent of the code laid out before it): five dwords of loop set-up follow the point ahead
+    // of the shared-count loop, six ahead of the per-sample loop, which so takes one dword of padding.
+    // In every instantiation: the set-up is the same in all of them.  (The shared-count loop one dword
+    // off: 127.5-128.1 against 118.7-119.4 us)
     if (active) {
-      if (fast) {
+      if (fast && shared) {
+        asm volatile(".p2align 3");
+        osc_bank4_shared(coef, H4, w, acc);
+      } else if (fast) {
+        asm volatile(".p2align 3\n s_nop 0");
         osc_bank4(coef, H4, w, acc);
       } else {
         for (int k = 0; k < H; ++k) {
@@ -261,7 +311,25 @@ __device__ __forceinline__ bool frame_synth(
     for (int j = tid; j < bs; j += NT) {
       const float wj = (float)(S + (double)(j + 1) * dinc);
       float a = 0.0f;
-      if (fabsf(wj) * (float)H4 < kFastArgLimit) {
+      // the 4-samples-per-thread form takes the shared count when all four samples of the aligned quad
+      // are fast: the same condition and the same reference sample here
+      bool quad = shared;
+      float wr = wj;
+      if (shared) {
+        const int q0 = j & ~3;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const float ws = (float)(S + (double)(q0 + s + 1) * dinc);
+          quad = quad && (fabsf(ws) * (float)H4 < kFastArgLimit);
+          if (s == kRefSample) wr = ws;
+        }
+      }
+      if (quad) {
+        for (int k = 0; k < H4; ++k) {
+          const float2 c = coef[k];
+          a = fmaf(sin_rev(reduce_rev_by(wj * c.x, rev_count(wr * c.x))), c.y, a);
+        }
+      } else if (fabsf(wj) * (float)H4 < kFastArgLimit) {
         for (int k = 0; k < H4; ++k) {
           const float2 c = coef[k];
           a = fmaf(sin_reduced(wj * c.x), c.y, a);
@@ -322,7 +390,7 @@ __global__ void __launch_bounds__(256) synth_frame_kernel(
   __shared__ double red[32];
   float acc[4], nz[4];
   int j0;
-  if (!frame_synth<RNG, SPLIT, /*PAD=*/CTRL, CTRL, PREFIX>(f0, param, mags, bias, noise, k0, k1, off0, off1, counter, ctrl_out,
+  if (!frame_synth<RNG, SPLIT, CTRL, PREFIX>(f0, param, mags, bias, noise, k0, k1, off0, off1, counter, ctrl_out,
                                       (int)gridDim.y, F, H, NB, bs, sr, lo_end, tail_start, pad, blockIdx.x,
                                       blockIdx.y, threadIdx.x, blockDim.x, smem4, red, 0, acc, nz, j0, ldp, ldm,
                                       prefix))
@@ -382,7 +450,7 @@ __global__ void __launch_bounds__(256) synth_stream_kernel(
   int j0;
   const double c = carry[blockIdx.y];
   const double c0 = wrap ? wrap_2pi(c) : c;
-  if (!frame_synth<RNG, SPLIT, false, false, false, true>(f0, param, mags, bias, noise, k0, k1, 0u, 0u, counter, nullptr,
+  if (!frame_synth<RNG, SPLIT, false, false, true>(f0, param, mags, bias, noise, k0, k1, 0u, 0u, counter, nullptr,
                                                           (int)gridDim.y, F, H, NB, bs, sr, lo_end, tail_start, pad,
                                                           blockIdx.x, blockIdx.y, threadIdx.x, blockDim.x, smem4, red, 0,
                                                           acc, nz, j0, H + 1, NB, nullptr, c0))

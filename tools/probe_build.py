@@ -81,7 +81,8 @@ PROBES = {
     "notail": [("if (bs - tail_start == 64 && bs - 127 >= lo_end) {\n    if (tid < 64) {",
                 "if (bs - tail_start == 64 && bs - 127 >= lo_end) {\n    if (tid < 0) {")],
     "nohtaps": [("h[j] = ir_at_half(ir, ct, n, bs, j);", "h[j] = ir[j & 63];")],
-    "noosc": [("osc_bank4(coef, H4, w, acc);", "acc[0] = w[0]; acc[1] = w[1]; acc[2] = w[2]; acc[3] = w[3];")],
+    "noosc": [("osc_bank4(coef, H4, w, acc);", "acc[0] = w[0]; acc[1] = w[1]; acc[2] = w[2]; acc[3] = w[3];"),
+              ("osc_bank4_shared(coef, H4, w, acc);", "acc[0] = w[0]; acc[1] = w[1]; acc[2] = w[2]; acc[3] = w[3];")],
     "nofir": [("float4 y = fir4(h, x, j0, lo_end, bs, bs);", "float4 y = make_float4(x[j0], x[j0 + 1], h[j0], h[j0 + 3]);")],
 }
 

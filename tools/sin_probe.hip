@@ -5,6 +5,7 @@
 //      unit issue beside the VALU?); 5: bare v_sin + fma (transcendental rate)
 //   2: reduction directly in revolutions (two-term 1/(2pi) by fma), hardware v_sin_f32 [shipped:
 //      common.h reduce_rev + sin_rev]
+// Also the bare v_sin_f32 per band of |y| up to 8 revolutions (rev_bands: the shared revolution count's range).
 // Accuracy vs fp64 sin of the same fp32 argument (|x| < kFastArgLimit); throughput in a
 // register-resident loop shaped like the fused kernel's (4 samples per thread, amplitude per k).
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -Iinclude -Ibuild \
@@ -42,6 +43,41 @@ __global__ void eval(const float* x, float* a, float* b, float* c, int n) {
     a[i] = sin_poly(x[i]);
     b[i] = sin_hw1(x[i]);
     c[i] = sin_hw2(x[i]);
+  }
+}
+
+// the bare hardware sine on an argument already in revolutions (common.h sin_rev)
+__global__ void eval_rev(const float* y, float* s, int n) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) s[i] = sin_rev(y[i]);
+}
+
+// sin_rev(y) against sin(2 pi y) in fp64 for fp32 y of both signs in [lo, hi): the range of the shared
+// revolution count (synth_frame.hip osc_bank4_shared, |y| < kSharedRevLimit) beyond reduce_rev's |y| <= 0.55.
+// The argument is the exact fp32 value, so an error above the first band's is the instruction's own.
+static void rev_bands(float* dx, float* ds) {
+  const int n = 1 << 20;
+  const double kTwoPi = 6.283185307179586476925;
+  const float bands[6] = {0.0f, 0.5f, 1.0f, 2.0f, 4.0f, 8.0f};
+  std::vector<float> hy(n), hs(n);
+  for (int b = 0; b < 5; ++b) {
+    const double lo = bands[b], hi = bands[b + 1];
+    for (int i = 0; i < n; ++i) {
+      float v = (float)(lo + (hi - lo) * ((i + 0.37) / n));
+      if (v >= (float)hi) v = std::nextafterf((float)hi, 0.0f);
+      hy[i] = i & 1 ? -v : v;
+    }
+    hipMemcpy(dx, hy.data(), n * 4, hipMemcpyHostToDevice);
+    hipLaunchKernelGGL(eval_rev, dim3(n / 256), dim3(256), 0, 0, dx, ds, n);
+    hipMemcpy(hs.data(), ds, n * 4, hipMemcpyDeviceToHost);
+    double m = 0, s = 0;
+    for (int i = 0; i < n; ++i) {
+      const double e = hs[i] - std::sin(kTwoPi * (double)hy[i]);
+      m = std::max(m, std::fabs(e)); s += e * e;
+    }
+    const double spacing = std::nextafterf((float)hi, 0.0f) - std::nextafterf(std::nextafterf((float)hi, 0.0f), 0.0f);
+    printf("sin_rev band [%.1f, %.1f): max %.3e rms %.3e (fp32 spacing %.3e rev = %.3e rad)\n", lo, hi, m,
+           std::sqrt(s / n), spacing, kTwoPi * spacing);
   }
 }
 
@@ -101,6 +137,7 @@ int main() {
     }
     printf("accuracy variant %d: max %.3e rms %.3e mean %.3e\n", v, m, std::sqrt(s / n), bias / n);
   }
+  rev_bands(dx, da);
   float* dout; hipMalloc(&dout, 25600 * 256 * 4);
   float* damp; hipMalloc(&damp, 128 * 8 * 4);
   std::vector<float> hamp(128 * 8, 0.0f);

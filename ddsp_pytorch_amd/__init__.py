@@ -9,6 +9,7 @@ Drop-in for hugofloresgarcia/ddsp_pytorch's synthesis hot path:
 * ``install(ddsp)`` rebinds both inside an imported reference package;
 * analysis — ``core.extract_loudness``, ``core.mfcc`` and ``features.analyze``: the loudness and MFCC
   features the models consume, from raw audio on the device (ddsp/core.py:81-97, ddsp/preprocess.py:28-32);
+  ``features.StreamAnalyzer`` / ``core.stream_loudness`` / ``core.stream_mfcc``: the same per call of a stream;
 * ``DDSPDecoder`` and ``DDSPAutoencoder`` — the reference's two models (same state_dicts) running
   on these kernels.
 
@@ -21,7 +22,7 @@ from .core import (amp_to_impulse_response, fft_convolve, harmonic_synth, remove
 from .decoder import DDSPDecoder
 from .encoder import DDSPAutoencoder
 from . import features
-from .features import analyze
+from .features import StreamAnalyzer, analyze
 from .install import install
 from .modules import FilteredNoise, HarmonicSynth, Reverb
 from . import synth  # noqa: E402  (SynthPath, make_inputs: the bench's and the tests' synthesis-path driver)

@@ -111,6 +111,11 @@ SIGNATURES = {
     "ddsp_hip_loudness": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "ddsp_hip_mfcc_workspace_size": (_SZ, [_I64, _I64, _I64, _I64, _I64]),
     "ddsp_hip_mfcc": (_I, [_P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _F, _P, _SZ, _P]),
+    # streaming analysis (per-call loudness, MFCC with carried history)
+    "ddsp_hip_stream_features_state_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "ddsp_hip_stream_loudness": (_I, [_P, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64, _P]),
+    "ddsp_hip_stream_mfcc": (_I, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64, _I64, _I64, _F,
+                                  _P]),
     # backward
     "ddsp_hip_scale_function_backward": (_I, [_P, _P, _P, _I64, _F, _P]),
     "ddsp_hip_upsample_backward": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P]),

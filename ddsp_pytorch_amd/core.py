@@ -28,7 +28,7 @@ __all__ = [
     "amp_to_impulse_response", "fft_convolve", "phase", "harmonic_controls",
     "harmonic_synth_frames", "harmonic_synth_params", "synth_frames", "synth_signal", "filtered_noise", "reverb_build_impulse", "reverb_spectrum_floats",
     "reverb_spectrum", "reverb_impulse_spectrum", "reverb_apply", "reverb_forward", "reverb_cache_bytes", "set_noise_seed", "safe_log", "stft_magnitude", "multiscale_fft",
-    "extract_loudness", "mfcc",
+    "extract_loudness", "mfcc", "FeatureStreamState", "stream_loudness", "stream_mfcc", "stream_feature_delay",
 ]
 
 
@@ -1149,6 +1149,99 @@ def stream_advance(state, f0=None, block_size=1, sample_rate=1.0, wrap=True):
         raise RuntimeError("stream_advance: f0 [B,F,1] on the state's device and of its batch size expected")
     _lib.call("stream_advance", _lib.ptr(f0.contiguous()), _lib.ptr(state.counter), _lib.ptr(state.buf),
               state.buf.numel(), int(bool(wrap)), B, F, int(block_size), float(sample_rate), _lib.stream_of(f0))
+
+
+# ------------------------------------------------------------------------------------
+# streaming analysis (ddsp_hip_stream_loudness / ddsp_hip_stream_mfcc): the features of a stream call by
+# call, the history a window needs carried on the device.  With d = ceil((n_fft / 2) / hop), call k of N = R hop
+# samples emits the frames f = k R - d + 1 + j, j < R, of the stream (frame f: the n_fft samples from
+# f hop - n_fft / 2, zeros before the stream's start — no reflect padding), i.e. the features lag the offline
+# alignment by d - 1 frames.
+# ------------------------------------------------------------------------------------
+def stream_feature_delay(n_fft, hop):
+    """d - 1, the frames by which a streamed feature lags the offline alignment (frame f at sample f * hop):
+    call k's first frame is k R - (d - 1), d = ceil((n_fft / 2) / hop)."""
+    return -(-(int(n_fft) // 2) // int(hop)) - 1
+
+
+class FeatureStreamState:
+    """The device state of one streamed feature (loudness or MFCC): ``buf`` (uint8,
+    ddsp_hip_stream_features_state_bytes: per item a ring of the carried samples plus one call, then the
+    MFCC's running maximum per item) and ``counter`` (int64[1], the call index).  Zero-filled is a fresh
+    stream.  ``counter``: another state's counter tensor to share (a ``StreamState``'s, so that one
+    ``stream_advance`` ends the call for synthesis and analysis alike); ``reset()`` then zeroes it for both."""
+
+    def __init__(self, batch, device, call_samples, n_fft, hop, counter=None):
+        self.batch, self.call_samples, self.n_fft, self.hop = int(batch), int(call_samples), int(n_fft), int(hop)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("ddsp_hip: the stream state lives on a HIP device (no CPU fallback)")
+        if self.batch < 1:
+            raise RuntimeError("FeatureStreamState: batch must be at least 1")
+        nbytes = int(_lib.query("stream_features_state_bytes", self.batch, self.call_samples, self.n_fft, self.hop))
+        if nbytes == 0:
+            raise RuntimeError("FeatureStreamState: n_fft must be a power of two in [16, 4096] and call_samples "
+                               f"1 to 32 whole hops; got n_fft {self.n_fft}, call_samples {self.call_samples}, "
+                               f"hop {self.hop}")
+        self.frames = self.call_samples // self.hop
+        self.delay_frames = stream_feature_delay(self.n_fft, self.hop)
+        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        if counter is None:
+            counter = torch.zeros(1, dtype=torch.int64, device=device)
+        elif counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != self.buf.device:
+            raise RuntimeError("FeatureStreamState: counter must be an int64[1] tensor on the state's device")
+        self.counter = counter
+
+    def reset(self):
+        self.buf.zero_()
+        self.counter.zero_()
+
+
+def _stream_call_rows(x, state, block_size, n_fft, name):
+    """x [B, N] or [B, N, 1] of one call -> contiguous detached [B, N], checked against the state."""
+    _dev(x)
+    if x.dim() not in (2, 3) or x.numel() != x.shape[0] * x.shape[1]:
+        raise RuntimeError(f"{name}: expected one call of audio [batch, samples] or [batch, samples, 1], got "
+                           f"{tuple(x.shape)}")
+    B, N = x.shape[0], x.shape[1]
+    if (state.batch, state.call_samples, state.n_fft, state.hop) != (B, N, int(n_fft), int(block_size)) \
+            or state.buf.device != x.device:
+        raise RuntimeError(f"{name}: the stream state is for another batch, call size, n_fft, hop or device")
+    return _c(x.detach().reshape(B, N))
+
+
+def stream_loudness(x, sample_rate, block_size, state, n_fft=2048):
+    """``extract_loudness`` (ddsp/core.py:81-97) for one call of a stream: x [B, N] or [B, N, 1] (HIP, fp32), the
+    stream's next N samples -> [B, N // block_size], the frames the call completes (see above: delayed by
+    ``state.delay_frames``).  ``state``: a ``FeatureStreamState(B, device, N, n_fft, block_size)``; the call reads
+    its counter and writes its ring, ``stream_advance`` ends the call.  One launch; tables cached as
+    ``extract_loudness``'s, no host synchronisation after the first call."""
+    xc = _stream_call_rows(x, state, block_size, n_fft, "stream_loudness")
+    n_fft = int(n_fft)
+    (w,) = _feature_tables("a_weighting", (float(sample_rate), n_fft), xc.device,
+                           lambda: (a_weighting_table(sample_rate, n_fft),))
+    B, N = xc.shape
+    out = torch.empty(B, state.frames, dtype=torch.float32, device=xc.device)
+    _lib.call("stream_loudness", _lib.ptr(xc), _lib.ptr(w), _lib.ptr(out), _lib.ptr(state.counter),
+              _lib.ptr(state.buf), state.buf.numel(), B, N, n_fft, int(block_size), _lib.stream_of(xc))
+    return out
+
+
+def stream_mfcc(x, sample_rate, block_size, state, n_mfcc=30, n_fft=1024, n_mels=128, fmin=20.0, fmax=8000.0,
+                top_db=80.0):
+    """``mfcc`` (ddsp/preprocess.py:30-32) for one call of a stream: x [B, N] or [B, N, 1] -> [B, N // block_size,
+    n_mfcc].  The top_db clamp is causal: against the item's maximum over everything the stream has emitted so
+    far (carried in ``state``), which is the offline clamp once the item's loudest frame has passed.  ``state``:
+    a ``FeatureStreamState(B, device, N, n_fft, block_size)`` of its own (not the loudness's).  One launch."""
+    xc = _stream_call_rows(x, state, block_size, n_fft, "stream_mfcc")
+    band_start, band_count, band_weights, dct = mfcc_tables(sample_rate, n_mfcc, n_fft, n_mels, fmin, fmax, xc.device)
+    B, N = xc.shape
+    out = torch.empty(B, state.frames, int(n_mfcc), dtype=torch.float32, device=xc.device)
+    _lib.call("stream_mfcc", _lib.ptr(xc), _lib.ptr(band_start), _lib.ptr(band_count), _lib.ptr(band_weights),
+              band_weights.numel(), _lib.ptr(dct), _lib.ptr(out), _lib.ptr(state.counter), _lib.ptr(state.buf),
+              state.buf.numel(), B, N, int(n_fft), int(block_size), int(n_mels), int(n_mfcc), float(top_db),
+              _lib.stream_of(xc))
+    return out
 
 
 from . import grad as _grad  # noqa: E402  (autograd Functions over the backward kernels)

@@ -16,6 +16,10 @@
 // workgroup maxima, clamps and applies the DCT.  Every reduction has a fixed order and there are no atomics:
 // results are bit-reproducible and an item's values do not depend on the batch around it.
 //
+// The same two features call by call for a realtime stream (ddsp_hip_stream_loudness / ddsp_hip_stream_mfcc, further
+// down): the samples a window needs from before the call are carried in a ring per item, the frames are the
+// stream's own (zeros before its start, no reflect padding), the MFCC's clamp is causal, one launch per feature.
+//
 // A workgroup transforms kPoints<N> points: 2048 (128 threads, 34 KB of LDS, 2048/N transforms) or, for
 // N = 4096, one transform of 4096 (256 threads, 68 KB: gfx950's LDS is 160 KB per CU).
 #include <hip/hip_runtime.h>
@@ -39,20 +43,50 @@ constexpr int kDctChunk = 32;  // mel columns of the DCT table staged per pass
 template <int N>
 constexpr int kPoints = N == 4096 ? 4096 : 2048;  // points per workgroup; threads = points / 16
 
-// Frames fa and fa + 1 of row xr, windowed (periodic Hann(N) from the fp64 table), through one complex FFT;
-// on return this transform's LDS slots hold Z (index k at lds_idx(k)) and the workgroup is synchronised.
+// Where a frame's samples come from: fetch(f, i) is sample i (0 <= i < N) of frame f's N-sample window, 0.0f for a
+// frame the caller does not have.  Offline: frame f of row xr[T] is centred at f * hop with reflect padding.
 template <int N>
-__device__ __forceinline__ void packed_spectrum(const float* __restrict__ xr, int64_t T, int hop, int frames, int fa,
-                                                int t, double2* lds) {
+struct ReflectFetch {
+  const float* __restrict__ xr;
+  int64_t T;
+  int hop, frames;
+  __device__ __forceinline__ float operator()(int f, int i) const {
+    return f < frames ? reflect_load(xr, T, (int64_t)f * hop + i - N / 2) : 0.0f;
+  }
+};
+
+// One call of a stream (include/ddsp_hip.h, "streaming analysis"): call k holds the samples [kN, (k+1)N) of the
+// stream in xc; the hs samples before them are in the item's ring of len >= hs + n floats, sample s at s mod len;
+// samples before the stream's start are zero.  The call's frame j (0 <= j < frames) starts rel0 + j * hop samples
+// from the call's first sample (rel0 = -hs), so every index rel below lies in [-hs, n).
+struct StreamFetch {
+  const float* __restrict__ ring;  // the item's ring
+  const float* __restrict__ xc;    // the item's call input [n]
+  int base;                        // (k n) mod len: the ring position of the call's first sample
+  int len, first;                  // first: the smallest rel that lies inside the stream, max(-hs, -k n)
+  int rel0, hop, frames;
+  __device__ __forceinline__ float operator()(int j, int i) const {
+    if (j >= frames) return 0.0f;
+    const int rel = rel0 + j * hop + i;
+    if (rel >= 0) return xc[rel];
+    if (rel < first) return 0.0f;
+    const int p = base + rel;
+    return ring[p < 0 ? p + len : p];
+  }
+};
+
+// Frames fa and fa + 1 of fetch, windowed (periodic Hann(N) from the fp64 table), through one complex FFT;
+// on return this transform's LDS slots hold Z (index k at lds_idx(k)) and the workgroup is synchronised.
+template <int N, class Fetch>
+__device__ __forceinline__ void packed_spectrum(const Fetch& fetch, int fa, int t, double2* lds) {
   constexpr int Q = N / 16, STEP = 4096 / N;
-  const int fb = fa + 1;
   double2 v[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int m = t + Q * r;
     const double w = 0.5 - 0.5 * kTwiddle4096D[2 * ((m * STEP) & 4095)];
-    const double a = fa < frames ? (double)reflect_load(xr, T, (int64_t)fa * hop + m - N / 2) * w : 0.0;
-    const double b = fb < frames ? (double)reflect_load(xr, T, (int64_t)fb * hop + m - N / 2) * w : 0.0;
+    const double a = (double)fetch(fa, m) * w;
+    const double b = (double)fetch(fa + 1, m) * w;
     v[r] = make_double2(a, b);
   }
   fft_n_f64<N, false>(v, lds, t);  // lds untouched so far
@@ -88,6 +122,23 @@ __device__ __forceinline__ void transform_sum2(double& a, double& b, double* scr
   }
 }
 
+// The two packed frames' sums over the bins of ln(|X[k]| + 1e-7) + w[k] (fp32 log, fp64 sum in a fixed order), valid
+// in the transform's thread t == 0; every thread of the workgroup calls this.
+template <int N>
+__device__ __forceinline__ void loudness_sums(const double2* lds, const float* __restrict__ w, int t, int tr,
+                                              double* red, double& sa, double& sb) {
+  constexpr int Q = N / 16, BINS = N / 2 + 1;
+  sa = 0.0;
+  sb = 0.0;
+  for (int k = t; k < BINS; k += Q) {
+    const double2 p = packed_power<N>(lds, k);
+    const float wk = w ? w[k] : 0.0f;
+    sa += (double)(logf((float)sqrt(p.x) + 1e-7f) + wk);
+    sb += (double)(logf((float)sqrt(p.y) + 1e-7f) + wk);
+  }
+  transform_sum2<Q>(sa, sb, red, tr);
+}
+
 // grid (ceil(frames / (2 * kPoints/N)), B), kPoints/16 threads; out[B, frames]
 template <int N>
 __global__ void __launch_bounds__(kPoints<N> / 16) loudness_kernel(const float* __restrict__ x, int64_t T, int hop,
@@ -100,15 +151,9 @@ __global__ void __launch_bounds__(kPoints<N> / 16) loudness_kernel(const float* 
   double2* lds = lds_all + tr * (N + N / 16);
   const int b = blockIdx.y;
   const int fa = 2 * (blockIdx.x * TPW + tr);
-  packed_spectrum<N>(x + (int64_t)b * T, T, hop, frames, fa, t, lds);
-  double sa = 0.0, sb = 0.0;
-  for (int k = t; k < BINS; k += Q) {
-    const double2 p = packed_power<N>(lds, k);
-    const float wk = w ? w[k] : 0.0f;
-    sa += (double)(logf((float)sqrt(p.x) + 1e-7f) + wk);
-    sb += (double)(logf((float)sqrt(p.y) + 1e-7f) + wk);
-  }
-  transform_sum2<Q>(sa, sb, red, tr);
+  packed_spectrum<N>(ReflectFetch<N>{x + (int64_t)b * T, T, hop, frames}, fa, t, lds);
+  double sa, sb;
+  loudness_sums<N>(lds, w, t, tr, red, sa, sb);
   if (t != 0 || fa >= frames) return;
   float* o = out + (int64_t)b * frames + fa;
   o[0] = (float)(sa / (double)BINS);
@@ -119,6 +164,55 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
   return v;
+}
+
+// The mel rows' band tables into LDS for a workgroup of THREADS threads: s_start / s_count, cut to the spectrum's
+// BINS bins, and s_off, the rows' offsets into band_w (an exclusive scan of the counts; thread tid holds rows
+// RPT tid ..).  The caller's next barrier publishes them.
+template <int THREADS, int BINS>
+__device__ __forceinline__ void stage_bands(const int* __restrict__ band_start, const int* __restrict__ band_count,
+                                            int n_mels, int* s_start, int* s_count, int* s_off, int* s_wave) {
+  constexpr int RPT = kMaxMels / THREADS;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int st[RPT], cnt[RPT], sum = 0;
+#pragma unroll
+  for (int j = 0; j < RPT; ++j) {
+    const int m = RPT * tid + j;
+    st[j] = m < n_mels ? min(max(band_start[m], 0), BINS) : 0;
+    cnt[j] = m < n_mels ? min(max(band_count[m], 0), 1 << 20) : 0;
+    sum += cnt[j];
+  }
+  int v = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  if (lane == 63) s_wave[wid] = v;
+  __syncthreads();
+  int off = v - sum;
+  for (int i = 0; i < wid; ++i) off += s_wave[i];
+#pragma unroll
+  for (int j = 0; j < RPT; ++j) {
+    const int m = RPT * tid + j;
+    s_off[m] = off;
+    s_start[m] = st[j];
+    s_count[m] = min(cnt[j], BINS - st[j]);
+    off += cnt[j];
+  }
+}
+
+// Mel row m of the two packed frames whose powers are in lds: (10 log10(max(1e-10, energy_a)), the same of b).
+__device__ __forceinline__ float2 mel_db_pair(const double2* lds, const float* __restrict__ band_w, int n_w, int s0,
+                                              int c, int off) {
+  double ea = 0.0, eb = 0.0;
+  for (int j = 0; j < c; ++j) {
+    const double wj = off + j < n_w ? (double)band_w[off + j] : 0.0;
+    const double2 p = lds[lds_idx(s0 + j)];
+    ea = fma(wj, p.x, ea);
+    eb = fma(wj, p.y, eb);
+  }
+  return make_float2(10.0f * log10f(fmaxf(1e-10f, (float)ea)), 10.0f * log10f(fmaxf(1e-10f, (float)eb)));
 }
 
 // MFCC launch (a).  grid (ceil(frames / (2 * kPoints/N)), B), kPoints/16 threads.  Mel row m is the band
@@ -133,46 +227,19 @@ __global__ void __launch_bounds__(kPoints<N> / 16) mel_db_kernel(const float* __
                                                                  int n_mels, float* __restrict__ D,
                                                                  float* __restrict__ wgmax) {
   constexpr int Q = N / 16, THREADS = kPoints<N> / 16, TPW = kPoints<N> / N, BINS = N / 2 + 1;
-  constexpr int RPT = kMaxMels / THREADS, WAVES = THREADS / 64;  // mel rows per thread in the offset scan
+  constexpr int WAVES = THREADS / 64;
   __shared__ double2 lds_all[TPW * (N + N / 16)];
   __shared__ int s_start[kMaxMels], s_count[kMaxMels], s_off[kMaxMels];
   __shared__ int s_wave[WAVES];
   __shared__ float s_max[WAVES];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  // the rows' offsets into band_w: exclusive scan of the counts (thread tid holds rows RPT tid ..)
-  {
-    int st[RPT], cnt[RPT], sum = 0;
-#pragma unroll
-    for (int j = 0; j < RPT; ++j) {
-      const int m = RPT * tid + j;
-      st[j] = m < n_mels ? min(max(band_start[m], 0), BINS) : 0;
-      cnt[j] = m < n_mels ? min(max(band_count[m], 0), 1 << 20) : 0;
-      sum += cnt[j];
-    }
-    int v = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(v, o, 64);
-      if (lane >= o) v += u;
-    }
-    if (lane == 63) s_wave[wid] = v;
-    __syncthreads();
-    int off = v - sum;
-    for (int i = 0; i < wid; ++i) off += s_wave[i];
-#pragma unroll
-    for (int j = 0; j < RPT; ++j) {
-      const int m = RPT * tid + j;
-      s_off[m] = off;
-      s_start[m] = st[j];
-      s_count[m] = min(cnt[j], BINS - st[j]);
-      off += cnt[j];
-    }
-  }
+  stage_bands<THREADS, BINS>(band_start, band_count, n_mels, s_start, s_count, s_off, s_wave);
   const int tr = tid / Q, t = tid - tr * Q;
   double2* lds = lds_all + tr * (N + N / 16);
   const int b = blockIdx.y;
   const int fa = 2 * (blockIdx.x * TPW + tr);
-  packed_spectrum<N>(x + (int64_t)b * T, T, hop, frames, fa, t, lds);  // (its barriers publish s_*)
+  // (its barriers publish s_*)
+  packed_spectrum<N>(ReflectFetch<N>{x + (int64_t)b * T, T, hop, frames}, fa, t, lds);
   // power of both frames over the spectrum, in place: the thread that owns the pair {k, N-k} writes slot k
   // (no other thread reads k or N-k)
   for (int k = t; k < BINS; k += Q) lds[lds_idx(k)] = packed_power<N>(lds, k);
@@ -181,16 +248,8 @@ __global__ void __launch_bounds__(kPoints<N> / 16) mel_db_kernel(const float* __
   float* Da = D + ((int64_t)b * frames + (va ? fa : 0)) * n_mels;
   float mx = -INFINITY;
   for (int m = t; m < n_mels; m += Q) {
-    const int s0 = s_start[m], c = s_count[m], off = s_off[m];
-    double ea = 0.0, eb = 0.0;
-    for (int j = 0; j < c; ++j) {
-      const double wj = off + j < n_w ? (double)band_w[off + j] : 0.0;
-      const double2 p = lds[lds_idx(s0 + j)];
-      ea = fma(wj, p.x, ea);
-      eb = fma(wj, p.y, eb);
-    }
-    const float da = 10.0f * log10f(fmaxf(1e-10f, (float)ea));
-    const float db = 10.0f * log10f(fmaxf(1e-10f, (float)eb));
+    const float2 d = mel_db_pair(lds, band_w, n_w, s_start[m], s_count[m], s_off[m]);
+    const float da = d.x, db = d.y;
     if (va) {
       Da[m] = da;
       mx = fmaxf(mx, da);
@@ -268,6 +327,186 @@ __global__ void __launch_bounds__(256) mfcc_dct_kernel(const float* __restrict__
   }
 }
 
+// ---------------- streaming analysis: one call of a stream (include/ddsp_hip.h) ----------------
+// Call k = *counter holds samples [k n, (k+1) n) and emits the frames = n / hop frames f = k frames - d + 1 + j,
+// d = ceil((N/2) / hop): those whose windows the call completes.  Frame j's window starts hs = (d-1) hop + N/2
+// samples before the call plus j hop, so a call reads [k n - hs, k n) from the item's ring (len = hs + n floats,
+// sample s at s mod len) and the rest from its input, and writes its input over the ring's [k n, (k+1) n) — n
+// positions that, modulo len, are exactly the ones the hs read positions leave free.  No workgroup reads what
+// another writes: the copy needs no ordering, and a call run twice before the advance reads and writes the same
+// values.  The kernels read the counter; ddsp_hip_stream_advance moves it.
+constexpr int kStreamMaxFrames = 32;  // frames per call (the MFCC keeps the call's D in LDS)
+
+struct StreamCall {
+  uint64_t k;
+  int n, len, hs, hop, frames;
+  // the ring position of the call's first sample: (k n) mod len without a 64-bit overflow
+  __device__ __forceinline__ int base() const {
+    return (int)(((k % (uint64_t)len) * (uint64_t)n) % (uint64_t)len);
+  }
+  __device__ __forceinline__ StreamFetch fetch(const float* ring_b, const float* x_b) const {
+    // k n >= hs once k >= ceil(hs / n); before that the stream starts k n (< hs + n) samples back
+    const int first = k >= (uint64_t)((hs + n - 1) / n) ? -hs : -(int)k * n;
+    return StreamFetch{ring_b, x_b, base(), len, first, -hs, hop, frames};
+  }
+  // thread `i0` of `stride` copies its share of the call's input into the ring
+  __device__ __forceinline__ void store(float* ring_b, const float* __restrict__ x_b, int i0, int stride) const {
+    const int p0 = base();
+    for (int i = i0; i < n; i += stride) {
+      const int p = p0 + i;
+      ring_b[p >= len ? p - len : p] = x_b[i];
+    }
+  }
+};
+
+// grid (ceil(ceil(frames / 2) / (kPoints/N)), B), kPoints/16 threads; out[B, frames].  Frames (j, j + 1), j even,
+// share a transform.  The item's workgroups share the ring copy.
+template <int N>
+__global__ void __launch_bounds__(kPoints<N> / 16) stream_loudness_kernel(const float* __restrict__ x,
+                                                                          const float* __restrict__ w,
+                                                                          float* __restrict__ out,
+                                                                          const uint64_t* __restrict__ counter,
+                                                                          float* ring, int n, int len, int hs,
+                                                                          int hop, int frames) {
+  constexpr int Q = N / 16, TPW = kPoints<N> / N;
+  __shared__ double2 lds_all[TPW * (N + N / 16)];
+  __shared__ double red[8];
+  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;
+  double2* lds = lds_all + tr * (N + N / 16);
+  const int b = blockIdx.y;
+  const int fa = 2 * (blockIdx.x * TPW + tr);
+  const StreamCall call{*counter, n, len, hs, hop, frames};
+  float* rb = ring + (int64_t)b * len;
+  const float* xb = x + (int64_t)b * n;
+  call.store(rb, xb, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  packed_spectrum<N>(call.fetch(rb, xb), fa, t, lds);
+  double sa, sb;
+  loudness_sums<N>(lds, w, t, tr, red, sa, sb);
+  if (t != 0 || fa >= frames) return;
+  constexpr int BINS = N / 2 + 1;
+  float* o = out + (int64_t)b * frames + fa;
+  o[0] = (float)(sa / (double)BINS);
+  if (fa + 1 < frames) o[1] = (float)(sb / (double)BINS);
+}
+
+// One pass of the MFCC's loop: frames fa and fa + 1 of the call through the packed transform, then both frames'
+// power over the spectrum in place (the thread that owns the pair {k, N-k} writes slot k; no other thread reads k
+// or N-k), published by the closing barrier.  Kept out of line on purpose: inlined into the caller's loop over
+// passes, this code came out of the compiler wrong on gfx950 for every n_fft whose last FFT stage is not radix-2
+// (bin 0 exact, every other bin off by decibels; the same source as a function, or with the loop removed, is
+// exact).  The cause in the compiler was not found; tests/test_gpu_stream_features.py covers every size.
+template <int N>
+__device__ __noinline__ void spectrum_power_pass(const StreamFetch& fetch, int fa, int t, double2* lds) {
+  constexpr int Q = N / 16, BINS = N / 2 + 1;
+  packed_spectrum<N>(fetch, fa, t, lds);
+  for (int k = t; k < BINS; k += Q) lds[lds_idx(k)] = packed_power<N>(lds, k);
+  __syncthreads();
+}
+
+// The MFCC of one call in one launch: grid (B), kPoints/16 threads, one workgroup per item.  It loops over the
+// call's frame pairs (kPoints/N transforms per pass) as mel_db_kernel does, keeping D[frames, n_mels] in LDS; folds
+// the call's largest D with the item's carried maximum runmax[b] (taken as absent when the counter is 0, whatever
+// the stored bits) and stores the result; clamps D at that maximum - top_db; and applies the DCT out of LDS as
+// mfcc_dct_kernel does (kDctFrames frames per round, the table staged kDctChunk columns at a time in the
+// transforms' LDS, m ascending, fp64 accumulator).  A second run before the advance folds the same call into a
+// maximum that already holds it: the same bits.
+template <int N>
+__global__ void __launch_bounds__(kPoints<N> / 16) stream_mfcc_kernel(
+    const float* __restrict__ x, const int* __restrict__ band_start, const int* __restrict__ band_count,
+    const float* __restrict__ band_w, int n_w, const float* __restrict__ dct, float* __restrict__ out,
+    const uint64_t* __restrict__ counter, float* ring, float* runmax, int n, int len, int hs, int hop, int frames,
+    int n_mels, int n_mfcc, float top_db) {
+  constexpr int Q = N / 16, THREADS = kPoints<N> / 16, TPW = kPoints<N> / N, BINS = N / 2 + 1;
+  constexpr int WAVES = THREADS / 64, FR = kDctFrames, MC = kDctChunk;
+  constexpr int TASKS = FR * kMaxMels / THREADS;  // DCT outputs per thread and round
+  __shared__ double2 lds_all[TPW * (N + N / 16)];
+  __shared__ float sD[kStreamMaxFrames * kMaxMels];
+  __shared__ int s_start[kMaxMels], s_count[kMaxMels], s_off[kMaxMels];
+  __shared__ int s_wave[WAVES];
+  __shared__ float s_max[WAVES];
+  __shared__ float s_floor;
+  static_assert(sizeof(double2) * TPW * (N + N / 16) >= sizeof(float) * kMaxMels * (MC + 1), "the DCT table's LDS");
+  float* sT = reinterpret_cast<float*>(lds_all);
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  stage_bands<THREADS, BINS>(band_start, band_count, n_mels, s_start, s_count, s_off, s_wave);
+  const int tr = tid / Q, t = tid - tr * Q;
+  double2* lds = lds_all + tr * (N + N / 16);
+  const int b = blockIdx.x;
+  const uint64_t k = *counter;
+  const StreamCall call{k, n, len, hs, hop, frames};
+  float* rb = ring + (int64_t)b * len;
+  const float* xb = x + (int64_t)b * n;
+  call.store(rb, xb, tid, THREADS);
+  const StreamFetch fetch = call.fetch(rb, xb);
+  float mx = -INFINITY;
+  for (int f0 = 0; f0 < frames; f0 += 2 * TPW) {
+    const int fa = f0 + 2 * tr;
+    spectrum_power_pass<N>(fetch, fa, t, lds);  // (its barriers publish s_*)
+    const bool va = fa < frames, vb = fa + 1 < frames;
+    float* Da = sD + (va ? fa : 0) * n_mels;
+    for (int m = t; m < n_mels; m += Q) {
+      const float2 d = mel_db_pair(lds, band_w, n_w, s_start[m], s_count[m], s_off[m]);
+      if (va) {
+        Da[m] = d.x;
+        mx = fmaxf(mx, d.x);
+      }
+      if (vb) {
+        Da[n_mels + m] = d.y;
+        mx = fmaxf(mx, d.y);
+      }
+    }
+    __syncthreads();  // the powers consumed before the next pass (or the DCT table) overwrites them
+  }
+  mx = wave_max(mx);
+  if (lane == 0) s_max[wid] = mx;
+  __syncthreads();
+  if (tid == 0) {
+    float r = s_max[0];
+#pragma unroll
+    for (int i = 1; i < WAVES; ++i) r = fmaxf(r, s_max[i]);
+    if (k != 0) r = fmaxf(r, runmax[b]);
+    runmax[b] = r;
+    s_floor = r - top_db;
+  }
+  __syncthreads();
+  const float floor_db = s_floor;
+  for (int i = tid; i < frames * n_mels; i += THREADS) sD[i] = fmaxf(sD[i], floor_db);
+  for (int f0 = 0; f0 < frames; f0 += FR) {
+    const int nf = min(FR, frames - f0);
+    const int tasks = nf * n_mfcc;  // task o = f * n_mfcc + i, <= THREADS * TASKS
+    double acc[TASKS];
+#pragma unroll
+    for (int j = 0; j < TASKS; ++j) acc[j] = 0.0;
+    for (int m0 = 0; m0 < n_mels; m0 += MC) {
+      const int mc = min(MC, n_mels - m0);
+      __syncthreads();  // the clamp complete (first pass); the previous chunk consumed (later ones)
+      for (int idx = tid; idx < n_mfcc * MC; idx += THREADS) {
+        const int i = idx / MC, mm = idx - i * MC;
+        sT[i * (MC + 1) + mm] = mm < mc ? dct[(int64_t)i * n_mels + m0 + mm] : 0.0f;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < TASKS; ++j) {
+        const int o = tid + THREADS * j;
+        if (o < tasks) {
+          const int f = o / n_mfcc, i = o - f * n_mfcc;
+          const float* trow = sT + i * (MC + 1);
+          const float* dr = sD + (f0 + f) * n_mels + m0;
+          double a = acc[j];
+          for (int mm = 0; mm < mc; ++mm) a = fma((double)trow[mm], (double)dr[mm], a);
+          acc[j] = a;
+        }
+      }
+    }
+    float* ot = out + ((int64_t)b * frames + f0) * n_mfcc;
+#pragma unroll
+    for (int j = 0; j < TASKS; ++j) {
+      const int o = tid + THREADS * j;
+      if (o < tasks) ot[o] = (float)acc[j];
+    }
+  }
+}
+
 // The envelope both features share (include/ddsp_hip.h), checked before any HIP call.
 int check_features(int64_t B, int64_t T, int64_t n_fft, int64_t hop) {
   if (B < 0 || T < 1 || hop < 1 || n_fft < 1) return DDSP_HIP_EINVAL;
@@ -282,6 +521,26 @@ int check_mfcc(int64_t B, int64_t T, int64_t n_fft, int64_t hop, int64_t n_mels,
   const int st = check_features(B, T, n_fft, hop);
   if (st) return st;
   return n_mels > kMaxMels ? DDSP_HIP_ERANGE : DDSP_HIP_OK;
+}
+
+// The streaming envelope (include/ddsp_hip.h) and the sizes it implies.
+struct StreamSizes {
+  int64_t frames, hs, len;  // frames per call, carried samples, ring floats per item
+};
+
+int check_stream_features(int64_t B, int64_t n, int64_t n_fft, int64_t hop, StreamSizes* sz) {
+  if (B < 0 || n < 1 || hop < 1 || n_fft < 1 || n % hop) return DDSP_HIP_EINVAL;
+  if (n_fft < 16 || n_fft > 4096 || (n_fft & (n_fft - 1))) return DDSP_HIP_ERANGE;
+  if (n / hop > kStreamMaxFrames || B > 65535 || n > (1 << 24)) return DDSP_HIP_ERANGE;
+  const int64_t d = (n_fft / 2 + hop - 1) / hop;
+  sz->frames = n / hop;
+  sz->hs = (d - 1) * hop + n_fft / 2;  // < n_fft: (d - 1) hop < n_fft / 2
+  sz->len = sz->hs + n;
+  return DDSP_HIP_OK;
+}
+
+size_t stream_features_bytes(int64_t B, const StreamSizes& sz) {  // the rings, then one maximum per item
+  return (sizeof(float) * (size_t)B * (size_t)(sz.len + 1) + 15) / 16 * 16;
 }
 
 unsigned frame_blocks(int64_t n_fft, int64_t frames) {
@@ -328,6 +587,51 @@ int loudness_dispatch(const float* x, const float* w, float* out, int64_t B, int
 int mel_db_dispatch(const float* x, const int* bs, const int* bc, const float* bw, int n_w, int n_mels, float* D,
                     float* wgmax, int64_t B, int64_t T, int64_t n_fft, int hop, int frames, void* stream) {
 #define DDSP_CALL(N) mel_db_launch<N>(x, bs, bc, bw, n_w, n_mels, D, wgmax, B, T, hop, frames, stream)
+  DDSP_FOR_N_FFT(n_fft, DDSP_CALL)
+#undef DDSP_CALL
+}
+
+struct StreamArgs {
+  const float* x;
+  const uint64_t* counter;
+  float* ring;
+  int64_t B;
+  int n, len, hs, hop, frames;
+  void* stream;
+};
+
+template <int N>
+int stream_loudness_launch(const StreamArgs& a, const float* w, float* out) {
+  hipLaunchKernelGGL(stream_loudness_kernel<N>, dim3(frame_blocks(N, a.frames), (unsigned)a.B), dim3(kPoints<N> / 16),
+                     0, S(a.stream), a.x, w, out, a.counter, a.ring, a.n, a.len, a.hs, a.hop, a.frames);
+  return launch_status();
+}
+
+struct MfccTables {
+  const int *start, *count;
+  const float* w;
+  int n_w;
+  const float* dct;
+  int n_mels, n_mfcc;
+  float top_db;
+};
+
+template <int N>
+int stream_mfcc_launch(const StreamArgs& a, const MfccTables& m, float* runmax, float* out) {
+  hipLaunchKernelGGL(stream_mfcc_kernel<N>, dim3((unsigned)a.B), dim3(kPoints<N> / 16), 0, S(a.stream), a.x, m.start,
+                     m.count, m.w, m.n_w, m.dct, out, a.counter, a.ring, runmax, a.n, a.len, a.hs, a.hop, a.frames,
+                     m.n_mels, m.n_mfcc, m.top_db);
+  return launch_status();
+}
+
+int stream_loudness_dispatch(const StreamArgs& a, int64_t n_fft, const float* w, float* out) {
+#define DDSP_CALL(N) stream_loudness_launch<N>(a, w, out)
+  DDSP_FOR_N_FFT(n_fft, DDSP_CALL)
+#undef DDSP_CALL
+}
+
+int stream_mfcc_dispatch(const StreamArgs& a, int64_t n_fft, const MfccTables& m, float* runmax, float* out) {
+#define DDSP_CALL(N) stream_mfcc_launch<N>(a, m, runmax, out)
   DDSP_FOR_N_FFT(n_fft, DDSP_CALL)
 #undef DDSP_CALL
 }
@@ -379,6 +683,47 @@ int ddsp_hip_mfcc(const float* x, const int32_t* band_start, const int32_t* band
   hipLaunchKernelGGL(mfcc_dct_kernel, dim3(gx, (unsigned)batch), dim3(256), 0, S(stream), D, wgmax, (int)nblk, frames,
                      (int)n_mels, (int)n_mfcc, dct, top_db, out);
   return launch_status();
+}
+
+size_t ddsp_hip_stream_features_state_bytes(int64_t batch, int64_t call_samples, int64_t n_fft, int64_t hop) {
+  StreamSizes sz;
+  if (batch < 1 || check_stream_features(batch, call_samples, n_fft, hop, &sz)) return 0;
+  return stream_features_bytes(batch, sz);
+}
+
+int ddsp_hip_stream_loudness(const float* x, const float* weights, float* out, const uint64_t* counter, void* state,
+                             size_t state_bytes, int64_t batch, int64_t call_samples, int64_t n_fft, int64_t hop,
+                             void* stream) {
+  StreamSizes sz;
+  const int st = check_stream_features(batch, call_samples, n_fft, hop, &sz);
+  if (st) return st;
+  if (batch == 0) return DDSP_HIP_OK;
+  if (!x || !out || !counter || !state) return DDSP_HIP_EINVAL;
+  if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
+  const StreamArgs a{x, counter, reinterpret_cast<float*>(state), batch, (int)call_samples, (int)sz.len, (int)sz.hs,
+                     (int)hop, (int)sz.frames, stream};
+  return stream_loudness_dispatch(a, n_fft, weights, out);
+}
+
+int ddsp_hip_stream_mfcc(const float* x, const int32_t* band_start, const int32_t* band_count,
+                         const float* band_weights, int64_t n_band_weights, const float* dct, float* out,
+                         const uint64_t* counter, void* state, size_t state_bytes, int64_t batch,
+                         int64_t call_samples, int64_t n_fft, int64_t hop, int64_t n_mels, int64_t n_mfcc, float top_db,
+                         void* stream) {
+  if (n_band_weights < 0 || n_band_weights > INT32_MAX || !(top_db >= 0.0f)) return DDSP_HIP_EINVAL;
+  if (n_mels < 1 || n_mfcc < 1 || n_mfcc > n_mels) return DDSP_HIP_EINVAL;
+  StreamSizes sz;
+  const int st = check_stream_features(batch, call_samples, n_fft, hop, &sz);
+  if (st) return st;
+  if (n_mels > kMaxMels) return DDSP_HIP_ERANGE;
+  if (batch == 0) return DDSP_HIP_OK;
+  if (!x || !band_start || !band_count || !band_weights || !dct || !out || !counter || !state) return DDSP_HIP_EINVAL;
+  if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
+  float* ring = reinterpret_cast<float*>(state);
+  const StreamArgs a{x, counter, ring, batch, (int)call_samples, (int)sz.len, (int)sz.hs, (int)hop, (int)sz.frames,
+                     stream};
+  const MfccTables m{band_start, band_count, band_weights, (int)n_band_weights, dct, (int)n_mels, (int)n_mfcc, top_db};
+  return stream_mfcc_dispatch(a, n_fft, m, ring + (size_t)batch * (size_t)sz.len, out);
 }
 
 }  // extern "C"

@@ -296,6 +296,6 @@ const char* ddsp_hip_status_string(int status) {
   }
 }
 
-int ddsp_hip_version(void) { return 104; }
+int ddsp_hip_version(void) { return 105; }
 
 }  // extern "C"

@@ -448,6 +448,59 @@ at::Tensor mfcc(const at::Tensor& x, const at::Tensor& band_start, const at::Ten
   return x.dim() == 1 ? out.select(0, 0) : out;
 }
 
+// ---------------- streaming analysis: one call of a stream (ddsp_hip_stream_loudness / _mfcc) ----------------
+// x [B, N] or [B, N, 1] -> the rows [B, N] contiguous
+at::Tensor call_rows(const at::Tensor& x, const char* op) {
+  check_dev(x, "x");
+  TORCH_CHECK((x.dim() == 2 || x.dim() == 3) && x.numel() == x.size(0) * x.size(1), op,
+              ": x [batch, call_samples] or [batch, call_samples, 1] expected");
+  return c16(x.reshape({x.size(0), x.size(1)}));
+}
+
+at::Tensor loudness_stream(const at::Tensor& x, const std::optional<at::Tensor>& weights, int64_t n_fft, int64_t hop,
+                           const at::Tensor& counter, at::Tensor& state) {
+  at::Tensor xc = call_rows(x, "loudness_stream");
+  check_stream(counter, state, xc);
+  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "loudness_stream: call_samples must be a multiple of hop");
+  const int64_t B = xc.size(0), N = xc.size(1);
+  at::Tensor w;
+  if (weights.has_value() && weights->defined()) {
+    check_dev(*weights, "weights");
+    TORCH_CHECK(weights->numel() == n_fft / 2 + 1, "loudness_stream: weights must hold n_fft/2+1 values");
+    w = weights->contiguous();
+  }
+  at::Tensor out = at::empty({B, N / hop}, xc.options());
+  ok(ddsp_hip_stream_loudness(xc.data_ptr<float>(), w.defined() ? w.data_ptr<float>() : nullptr, out.data_ptr<float>(),
+                              reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
+                              (size_t)state.numel(), B, N, n_fft, hop, stream_of(xc)),
+     "stream_loudness");
+  return out;
+}
+
+at::Tensor mfcc_stream(const at::Tensor& x, const at::Tensor& band_start, const at::Tensor& band_count,
+                       const at::Tensor& band_weights, const at::Tensor& dct, int64_t n_fft, int64_t hop, double top_db,
+                       const at::Tensor& counter, at::Tensor& state) {
+  at::Tensor xc = call_rows(x, "mfcc_stream");
+  check_stream(counter, state, xc);
+  check_dev(band_weights, "band_weights");
+  check_dev(dct, "dct");
+  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "mfcc_stream: call_samples must be a multiple of hop");
+  TORCH_CHECK(dct.dim() == 2, "mfcc_stream: dct [n_mfcc, n_mels] expected");
+  const int64_t B = xc.size(0), N = xc.size(1), n_mfcc = dct.size(0), n_mels = dct.size(1);
+  for (const at::Tensor* t : {&band_start, &band_count})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->numel() == n_mels,
+                "mfcc_stream: band_start and band_count must be int32 HIP tensors of n_mels values");
+  at::Tensor bs = band_start.contiguous(), bc = band_count.contiguous(), bw = band_weights.contiguous(),
+             d = dct.contiguous();
+  at::Tensor out = at::empty({B, N / hop, n_mfcc}, xc.options());
+  ok(ddsp_hip_stream_mfcc(xc.data_ptr<float>(), bs.data_ptr<int32_t>(), bc.data_ptr<int32_t>(), bw.data_ptr<float>(),
+                          bw.numel(), d.data_ptr<float>(), out.data_ptr<float>(),
+                          reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
+                          (size_t)state.numel(), B, N, n_fft, hop, n_mels, n_mfcc, (float)top_db, stream_of(xc)),
+     "stream_mfcc");
+  return out;
+}
+
 }  // namespace
 
 // ---------------- decoder.py:33-68: the GRU recurrence ----------------
@@ -506,6 +559,9 @@ TORCH_LIBRARY(ddsp_hip, m) {
   m.def("loudness(Tensor x, Tensor? weights, int n_fft, int hop) -> Tensor");
   m.def("mfcc(Tensor x, Tensor band_start, Tensor band_count, Tensor band_weights, Tensor dct, int n_fft, int hop,"
         " float top_db) -> Tensor");
+  m.def("loudness_stream(Tensor x, Tensor? weights, int n_fft, int hop, Tensor counter, Tensor(a!) state) -> Tensor");
+  m.def("mfcc_stream(Tensor x, Tensor band_start, Tensor band_count, Tensor band_weights, Tensor dct, int n_fft,"
+        " int hop, float top_db, Tensor counter, Tensor(a!) state) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA key on ROCm
@@ -531,4 +587,6 @@ TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA 
   m.impl("gru", &gru);
   m.impl("loudness", &loudness);
   m.impl("mfcc", &mfcc);
+  m.impl("loudness_stream", &loudness_stream);
+  m.impl("mfcc_stream", &mfcc_stream);
 }

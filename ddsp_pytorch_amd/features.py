@@ -5,12 +5,15 @@ The reference computes ``batch['loudness']`` and ``batch['mfcc']`` on the host, 
 model as [frames, 1], [frames, 1] and [frames, 30].  ``analyze`` produces the same dict from audio that is
 already on the HIP device (``core.extract_loudness``, ``core.mfcc``: csrc/features.hip).  Pitch (the reference's
 CREPE network, ``extract_pitch``) is not computed here: ``f0`` stays an input.
+
+``StreamAnalyzer`` is the same front end for a realtime stream: audio comes in call by call and each call returns
+the frames it completes (``core.stream_loudness``, ``core.stream_mfcc``), the history carried on the device.
 """
 import torch
 
 from . import core
 
-__all__ = ["analyze"]
+__all__ = ["analyze", "StreamAnalyzer"]
 
 
 def analyze(signal, pitch, sample_rate, block_size, mean_loudness=None, std_loudness=None):
@@ -32,3 +35,48 @@ def analyze(signal, pitch, sample_rate, block_size, mean_loudness=None, std_loud
         raise RuntimeError(f"analyze: pitch must hold {B} x {F} values (T // block_size per item), got "
                            f"{tuple(pitch.shape)}")
     return {"pitch": pitch.reshape(B, F, 1), "loudness": loudness.unsqueeze(-1), "mfcc": mfcc}
+
+
+class StreamAnalyzer:
+    """Loudness and MFCC of a stream, call by call: ``analyzer(audio)`` takes the stream's next ``call_samples``
+    samples, audio [B, N] or [B, N, 1] on the device, and returns ``{'loudness': [B, R, 1], 'mfcc': [B, R, 30]}``
+    for the R = N // block_size frames the call completes, then advances the stream (one launch per feature and one
+    for the advance).  The frames are the stream's own (zeros before its start, no reflect padding); call k holds
+    frames ``k R + first_frame[name] + j`` of the offline alignment (frame f centred at sample f * block_size), so
+    each feature lags by ``delay_frames[name]`` frames (loudness: n_fft 2048, MFCC: n_fft 1024 as in
+    ``analyze``).  The MFCC's top_db clamp is causal (``core.stream_mfcc``).  ``mean_loudness`` / ``std_loudness``
+    as in ``analyze``.  After one warm-up call (the tables) nothing synchronises with the host: a call can be
+    captured in a HIP graph over a static input buffer.  ``counter``: a stream counter to share (e.g. a
+    ``core.StreamState``'s), with ``advance=False`` when that stream's own advance ends the call."""
+
+    N_FFT = {"loudness": 2048, "mfcc": 1024}
+
+    def __init__(self, sample_rate, block_size, call_samples, batch=1, device="cuda", mean_loudness=None,
+                 std_loudness=None, counter=None, advance=True):
+        if (mean_loudness is None) != (std_loudness is None):
+            raise ValueError("StreamAnalyzer: mean_loudness and std_loudness go together")
+        self.sample_rate, self.block_size, self.call_samples = float(sample_rate), int(block_size), int(call_samples)
+        self.mean_loudness, self.std_loudness = mean_loudness, std_loudness
+        self.advance = bool(advance)
+        self.loudness_state = core.FeatureStreamState(batch, device, call_samples, self.N_FFT["loudness"], block_size,
+                                                      counter=counter)
+        self.counter = self.loudness_state.counter
+        self.mfcc_state = core.FeatureStreamState(batch, device, call_samples, self.N_FFT["mfcc"], block_size,
+                                                  counter=self.counter)
+        self.delay_frames = {"loudness": self.loudness_state.delay_frames, "mfcc": self.mfcc_state.delay_frames}
+        self.first_frame = {k: -v for k, v in self.delay_frames.items()}
+
+    def reset(self):
+        self.loudness_state.reset()
+        self.mfcc_state.reset()
+
+    @torch.no_grad()
+    def __call__(self, audio):
+        loudness = core.stream_loudness(audio, self.sample_rate, self.block_size, self.loudness_state,
+                                        n_fft=self.N_FFT["loudness"])
+        if self.mean_loudness is not None:
+            loudness = (loudness - self.mean_loudness) / self.std_loudness
+        mfcc = core.stream_mfcc(audio, self.sample_rate, self.block_size, self.mfcc_state, n_fft=self.N_FFT["mfcc"])
+        if self.advance:
+            core.stream_advance(self.loudness_state)
+        return {"loudness": loudness.unsqueeze(-1), "mfcc": mfcc}

@@ -26,6 +26,11 @@ advance also moves the carry (``wrap``: modulo 2 pi, so omega keeps its fp32 res
 the same number of launches.  ``reverb=True`` adds the streamed reverb (`ddsp_hip_stream_reverb`, one
 more launch) with the model's reverb parameters and the impulse response at its full length, so K
 calls of N samples are the K N samples the offline model renders.
+
+``loudness_from_audio=True`` makes the input side seamless too: the second input of a call is the stream's
+audio, and the graph computes the loudness from it (`ddsp_hip_stream_loudness`, one more launch: the reference's
+`extract_loudness`, core.py:81-97, with the history a 2048-sample window needs carried on the device) before
+the normalisation and the control network.
 """
 from collections import namedtuple
 
@@ -50,11 +55,19 @@ class RealtimeGraph:
     then: the carry is kept modulo 2 pi).  ``reverb=True`` (needs ``continuous`` and a power-of-two
     ``call_samples`` in [64, 2048]): the model's reverb runs in the stream with its full impulse
     response, built at construction (`refresh()` rebuilds it after the parameters change).  The
-    stream's device state is `self.stream` (core.StreamState); `reset()` zeroes it too."""
+    stream's device state is `self.stream` (core.StreamState); `reset()` zeroes it too.
+
+    ``loudness_from_audio=True``: ``__call__(pitch, audio)`` — the second input is the call's audio [1, N, 1],
+    and the graph runs `core.stream_loudness` (n_fft 2048, hop = block_size) on it in place of a loudness input.
+    A frame's window is complete only `loudness_delay_samples` (= (ceil(1024 / block_size) - 1) block_size: 768 at
+    block 256) after its centre, so the loudness that drives a call's frames is that much older than the call's
+    samples.  The pitch is NOT delayed to match: pitch trackers bring a latency of their own, and aligning the
+    two is the caller's.  The analysis shares the stream's call counter (with ``continuous`` the `StreamState`'s),
+    its state is `self.analysis` (core.FeatureStreamState), and `reset()` zeroes it too."""
 
     def __init__(self, model, call_samples=1024, mean_loudness=0.0, std_loudness=1.0,
                  seed=0x5EEDDD5B, device=None, warmup=3, fused=True, gru_route="steps",
-                 continuous=False, reverb=False, wrap=None):
+                 continuous=False, reverb=False, wrap=None, loudness_from_audio=False):
         device = torch.device(device) if device is not None else next(model.parameters()).device
         if device.type != "cuda":
             raise RuntimeError("RealtimeGraph: the model must be on a HIP device")
@@ -93,6 +106,12 @@ class RealtimeGraph:
             if self.reverb:
                 self._spec = torch.empty(int(core._lib.query("stream_spectrum_floats", N, L)), device=device)
                 self.refresh()
+        self.loudness_from_audio = bool(loudness_from_audio)
+        self.analysis = None
+        self.loudness_delay_samples = 0
+        if self.loudness_from_audio:  # raises on a call size or block the streamed analysis cannot take
+            self.analysis = core.FeatureStreamState(1, device, N, 2048, bs, counter=self.counter)
+            self.loudness_delay_samples = self.analysis.delay_frames * bs
         self._inp_h = torch.zeros(2, N, 1).pin_memory()
         self._out_h = torch.zeros(1, N, 1).pin_memory()
         self.fused = bool(fused)
@@ -117,6 +136,8 @@ class RealtimeGraph:
         self.counter.zero_()
         if self.stream is not None:
             self.stream.reset()
+        if self.analysis is not None:
+            self.analysis.reset()
 
     def refresh(self):
         """Rebuild the streamed reverb's IR spectra from the model's reverb parameters (in place: the
@@ -140,6 +161,13 @@ class RealtimeGraph:
             out = core.stream_reverb(out, self._spec, self.stream)
         core.stream_advance(self.stream, f0, bs, self.sample_rate, wrap=self.wrap)
         return out
+
+    def _loudness_frames(self):
+        """The call's loudness, one value per frame: (tensor, its stride) — the input decimated by block_size,
+        or with ``loudness_from_audio`` the streamed analysis of the audio in the loudness buffer."""
+        if not self.loudness_from_audio:
+            return self.loudness, self.block_size
+        return core.stream_loudness(self.loudness, self.sample_rate, self.block_size, self.analysis), 1
 
     def _setup_fused(self):
         m, dev = self.model, self.device
@@ -172,9 +200,10 @@ class RealtimeGraph:
         di = core.dense_input
         inv = 1.0 / self.std_loudness
         f0m, lm, om = d.f0_mlp, d.loudness_mlp, d.out_mlp
+        loud, loud_ld = self._loudness_frames()
         core.dense_rows([  # mlp layers 1-2 (core.py:122-129), f0 and loudness
             ([di(self.pitch, ld=bs, first=f0m[0], norm=f0m[1], x_copy=b["f0"])], f0m[3], b["y2f"]),
-            ([di(self.loudness, ld=bs, scale=inv, shift=-self.mean_loudness * inv, first=lm[0], norm=lm[1],
+            ([di(loud, ld=loud_ld, scale=inv, shift=-self.mean_loudness * inv, first=lm[0], norm=lm[1],
                  x_copy=b["loud"])], lm[3], b["y2l"])], R, dev)
         core.dense_rows([([di(b["y2f"], norm=f0m[4])], f0m[6], b["y3f"]),
                          ([di(b["y2l"], norm=lm[4])], lm[6], b["y3l"])], R, dev)
@@ -204,7 +233,8 @@ class RealtimeGraph:
             return self._forward_fused()
         m, bs = self.model, self.block_size
         pitch = self.pitch[:, ::bs]
-        loudness = (self.loudness[:, ::bs] - self.mean_loudness) / self.std_loudness
+        loud, loud_ld = self._loudness_frames()
+        loudness = (loud.view(1, -1, 1)[:, ::loud_ld] - self.mean_loudness) / self.std_loudness
         hidden = gru_decoder_forward(m.decoder, pitch, loudness, None, realtime=True)
         param = m.harmonic_proj(hidden)
         mags = m.noise_proj(hidden)
@@ -215,11 +245,13 @@ class RealtimeGraph:
         self.counter.zero_()
         if self.stream is not None:
             self.stream.reset()
+        if self.analysis is not None:
+            self.analysis.reset()
 
     @torch.no_grad()
     def __call__(self, pitch, loudness):
         """pitch, loudness [1, N, 1] on the host (returns a host tensor) or on the device (returns
-        the device output buffer)."""
+        the device output buffer).  With ``loudness_from_audio`` the second input is the call's audio."""
         if tuple(pitch.shape) != (1, self.call_samples, 1) or tuple(loudness.shape) != tuple(pitch.shape):
             raise RuntimeError(f"RealtimeGraph: pitch and loudness must be [1, {self.call_samples}, 1]")
         stream = torch.cuda.current_stream(self.device)

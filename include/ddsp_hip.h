@@ -605,6 +605,61 @@ int ddsp_hip_stream_reverb(const float* x, const float* spectrum, size_t spectru
 int ddsp_hip_stream_advance(const float* f0, uint64_t* counter, void* state, size_t state_bytes, int wrap,
                             int64_t batch, int64_t frames, int64_t block_size, float sample_rate, void* stream);
 
+/* ---------------- streaming analysis: the features of a stream, call by call ----------------
+ * The input side of a realtime stream: each call hands over the next N = call_samples samples x[batch, N] of the
+ * stream x_all and receives the R = N / hop feature frames whose windows those samples complete, computed with the
+ * arithmetic of ddsp_hip_loudness / ddsp_hip_mfcc (periodic Hann(n_fft), unnormalised fp64 transform, fp32 logs,
+ * fixed-order reductions, no atomics: bit-reproducible and independent of the batch around an item).
+ *
+ * Frames.  Frame f is the n_fft samples x_all[f * hop - n_fft/2 + i], i = 0 .. n_fft-1, with 0 where the index is
+ * negative: samples before the stream's start are zero.  A stream has no "before", so the offline entry points'
+ * reflect padding does not apply (away from the first n_fft/2 samples the frames are the offline ones).  With
+ * d = ceil((n_fft/2) / hop), call k (the device counter; 0 for a fresh stream) receives samples [k N, (k+1) N) and
+ * emits
+ *     f = k R - d + 1 + j,   j = 0 .. R-1,
+ * the frames that have just become complete (the newest sample needed, (k+1) N - d hop + n_fft/2 - 1, is at most
+ * (k+1) N - 1).  Frames with f < 0 lie before the stream and are computed like any other, from zeros.  The
+ * features therefore lag the reference's decimated alignment (frame f at sample f * hop) by d - 1 frames: 768
+ * samples at n_fft 2048 and hop 256.  The call's frames ride two per complex transform as (j, j + 1), j even (R
+ * odd: the last alone), so the bits are not those of the offline entry points, whose pairs are (f, f + 1), f even.
+ *
+ * State: one caller-allocated device buffer of ddsp_hip_stream_features_state_bytes(batch, call_samples, n_fft,
+ * hop) bytes per feature, 16-byte aligned, zero-filled for a fresh stream: per item a ring of Hs + N floats
+ * (Hs = (d-1) hop + n_fft/2 carried samples; sample s of the stream at position s mod (Hs + N)), then one float
+ * per item, the MFCC's running maximum; the size rounded up to 16 bytes.  Call k reads [k N - Hs, k N) from the
+ * ring and [k N, (k+1) N) from x, and copies x over the ring's region for [k N, (k+1) N): with that length the
+ * region written is disjoint from everything the call reads, so the copy needs no ordering, and running call k
+ * twice before the advance gives the same bits.  The counter is the stream's (see above): these entry points read
+ * it, ddsp_hip_stream_advance ends the call — one advance for synthesis and analysis alike when they share it.
+ *
+ * Envelope, checked before any HIP call: n_fft a power of two in [16, 4096] (else DDSP_HIP_ERANGE), hop >= 1 and
+ * call_samples a positive multiple of hop (else DDSP_HIP_EINVAL), R <= 32, batch <= 65535 and call_samples <=
+ * 2^24 (else DDSP_HIP_ERANGE); for the MFCC 1 <= n_mfcc <= n_mels and top_db >= 0 (else DDSP_HIP_EINVAL), n_mels
+ * <= 256 (else DDSP_HIP_ERANGE).  Null pointers and negative sizes: DDSP_HIP_EINVAL; batch == 0: a no-op success;
+ * a short state: DDSP_HIP_EWORKSPACE.  ddsp_hip_stream_features_state_bytes is 0 outside the envelope and for
+ * batch < 1. */
+size_t ddsp_hip_stream_features_state_bytes(int64_t batch, int64_t call_samples, int64_t n_fft, int64_t hop);
+
+/* ddsp/core.py:81-97 extract_loudness over a stream: out[b, j] = mean over k' = 0..n_fft/2 of
+ * (ln(|X[b, f, k']| + 1e-7) + weights[k']) for the call's frames f = k R - d + 1 + j; weights as
+ * ddsp_hip_loudness (NULL = zeros).  out [batch, R].  One launch. */
+int ddsp_hip_stream_loudness(const float* x, const float* weights, float* out, const uint64_t* counter, void* state,
+                             size_t state_bytes, int64_t batch, int64_t call_samples, int64_t n_fft, int64_t hop,
+                             void* stream);
+
+/* ddsp/preprocess.py:30-32 librosa.feature.mfcc over a stream: D[b, j, m] = 10 log10(max(1e-10, mel energy)) of the
+ * call's frames f = k R - d + 1 + j (tables as ddsp_hip_mfcc), the clamp, then out[b, j, i] = sum_m dct[i, m]
+ * D[b, j, m] — out [batch, R, n_mfcc].  The clamp is causal: D <- max(D, runmax - top_db) with runmax the item's
+ * maximum over every D the stream has emitted up to and including this call, carried in the state ("no maximum
+ * yet" is taken from counter == 0, not from the stored bits).  It equals the offline clamp (the item's global
+ * maximum) once the item's loudest frame has passed; before that it differs from it by construction.  One launch,
+ * one workgroup per item, no workspace. */
+int ddsp_hip_stream_mfcc(const float* x, const int32_t* band_start, const int32_t* band_count,
+                         const float* band_weights, int64_t n_band_weights, const float* dct, float* out,
+                         const uint64_t* counter, void* state, size_t state_bytes, int64_t batch,
+                         int64_t call_samples, int64_t n_fft, int64_t hop, int64_t n_mels, int64_t n_mfcc, float top_db,
+                         void* stream);
+
 /* Two-stage serving pipeline (ddsp_pytorch_amd.synth.PipelinedSynthPath; no reference counterpart:
  * the reference synthesises one batch at a time, decoder.py:101-136).  A HIP stream restricted to
  * the CUs whose bits are set in cu_mask (mask_words 32-bit words, bit c = CU index c; HIP deals

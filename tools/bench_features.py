@@ -6,6 +6,11 @@ config 2's (64 x 102,400).  Each figure is the median over `--windows` event-tim
 after a warm-up of every timed callable.  Beside each time: the bytes the algorithm needs (x read once, the
 features written, and for the MFCC the D workspace written and read back) and the rate they make.  Prints one
 JSON line per (shape, leg); DESIGN.md 3f records a run.  Needs a HIP device: there is no CPU path.
+
+``--leg stream`` times the streaming analysis (core.stream_loudness, core.stream_mfcc) at the realtime shape (one
+item, calls of 1024 samples, block 256, 48 kHz), each leg captured in a HIP graph and replayed: the stream
+kernels, beside the route open without them — the offline kernels over a rolling window of Hs + N samples (the
+history a call's frames need plus the call), the window's shift included.  DESIGN.md 3g records a run.
 """
 import argparse
 import json
@@ -55,14 +60,79 @@ def timed(fn, reps, windows):
     return statistics.median(ms), min(ms), max(ms)
 
 
+def graphed(fn):
+    """fn captured in a HIP graph after a warm-up on a side stream -> the replay callable."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        keep = fn()
+    g.keep = keep  # the outputs live as long as the graph
+    return g.replay
+
+
+def stream_leg(dev, reps, windows):
+    """One item, calls of 1024 samples, block 256, 48 kHz; microseconds per replayed call."""
+    sr, hop, N = 48000, 256, 1024
+    x = 0.1 * torch.randn(1, N, device=dev)
+    sl = core.FeatureStreamState(1, dev, N, 2048, hop)
+    sm = core.FeatureStreamState(1, dev, N, 1024, hop, counter=sl.counter)
+    hs_l = core.stream_feature_delay(2048, hop) * hop + 1024
+    hs_m = core.stream_feature_delay(1024, hop) * hop + 512
+    win_l = torch.zeros(1, hs_l + N, device=dev)
+    win_m = torch.zeros(1, hs_m + N, device=dev)
+
+    def roll(win):  # the window moves on by one call: two small copies
+        win[:, :-N].copy_(win[:, N:].clone())
+        win[:, -N:].copy_(x)
+
+    def rolling_loudness():
+        roll(win_l)
+        return core.extract_loudness(win_l, sr, hop)
+
+    def rolling_mfcc():
+        roll(win_m)
+        return core.mfcc(win_m, sr, hop)
+
+    def stream_both():
+        out = core.stream_loudness(x, sr, hop, sl), core.stream_mfcc(x, sr, hop, sm)
+        core.stream_advance(sl)
+        return out
+
+    legs = [
+        ("stream loudness", lambda: core.stream_loudness(x, sr, hop, sl), 1),
+        ("stream mfcc", lambda: core.stream_mfcc(x, sr, hop, sm), 1),
+        ("stream both + advance", stream_both, 3),
+        ("advance alone", lambda: core.stream_advance(sl), 1),
+        ("rolling-window loudness (offline kernel)", rolling_loudness, 4),
+        ("rolling-window mfcc (offline kernels)", rolling_mfcc, 5),
+        ("rolling-window both", lambda: (rolling_loudness(), rolling_mfcc()), 9),
+    ]
+    for leg, fn, launches in legs:
+        med, lo, hi = timed(graphed(fn), reps, windows)
+        print(json.dumps({"shape": "stream 1x1024 block 256", "leg": leg, "graph_nodes": launches,
+                          "us": round(1e3 * med, 2), "us_min": round(1e3 * lo, 2), "us_max": round(1e3 * hi, 2)}),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=1000)
     ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--leg", choices=("offline", "stream", "all"), default="all")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_features: needs a HIP device (there is no CPU path)")
     dev = torch.device("cuda", 0)
+    if args.leg in ("stream", "all"):
+        stream_leg(dev, args.reps, args.windows)
+    if args.leg == "stream":
+        return
     for name, B, T, hop, sr in SHAPES:
         g = torch.Generator().manual_seed(B + T)
         t = torch.arange(T) / sr

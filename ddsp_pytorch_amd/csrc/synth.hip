@@ -101,8 +101,8 @@ template <int SPT, bool RAW>
 __global__ void __launch_bounds__(256) harmonic_frames_kernel(
     const float* __restrict__ f0, const float* __restrict__ amp, float* dist, int write_back,
     float* __restrict__ out, int F, int H, int bs, float sr) {
-  // per harmonic k: coef[k] = (k+1, A), A = dist*amp; H rounded up to 4 with zero amplitudes.
-  // Read back as wave-uniform (broadcast) LDS loads.
+  // coef[p] = (k+1, A) of harmonic k = H4 - 1 - p, A = dist*amp: the highest harmonic first, H rounded up
+  // to 4 with zero amplitudes (the padding comes first).  Read back as wave-uniform (broadcast) LDS loads.
   extern __shared__ float2 coef[];
   __shared__ double red[16];
 
@@ -128,7 +128,7 @@ __global__ void __launch_bounds__(256) harmonic_frames_kernel(
     double part2 = 0.0;
     for (int k = tid; k < H; k += NT) {
       const float v = controls_value(prow[1 + k], pitch0, k, half_sr);
-      coef[k].y = v;
+      coef[H4 - 1 - k].y = v;  // harmonic k + 1 sits at table position H4 - 1 - k (below)
       part2 += (double)v;
     }
     norm = (float)block_sum_double(part2, red);  // dist.sum(-1)
@@ -136,17 +136,20 @@ __global__ void __launch_bounds__(256) harmonic_frames_kernel(
   } else {
     a = amp[row];
   }
-  for (int k = tid; k < H4; k += NT) {
+  // the table runs from the highest harmonic down, so that the loops below sum in descending k, the small terms
+  // first (synth_frame.hip frame_synth phase 2, which this kernel matches)
+  for (int p = tid; p < H4; p += NT) {
+    const int k = H4 - 1 - p;
     float v = 0.0f;
     if (k < H) {
       if (RAW) {
-        v = (coef[k].y / norm) * a;  // (dist / sum) * amp, the reference's rounding order
+        v = (coef[p].y / norm) * a;  // (dist / sum) * amp, the reference's rounding order
       } else {
         v = dist[row * H + k] * a;
         if (write_back) dist[row * H + k] = v;
       }
     }
-    coef[k] = make_float2((float)(k + 1), v);
+    coef[p] = make_float2((float)(k + 1), v);
   }
   __syncthreads();
 
@@ -172,7 +175,7 @@ __global__ void __launch_bounds__(256) harmonic_frames_kernel(
         for (int s = 0; s < SPT; ++s) acc[s] = fmaf(sin_reduced(w[s] * c.x), c.y, acc[s]);
       }
     } else {
-      for (int k = 0; k < H; ++k) {
+      for (int k = H4 - H; k < H4; ++k) {  // the H real harmonics, past the padding
         const float2 c = coef[k];
 #pragma unroll
         for (int s = 0; s < SPT; ++s) {

@@ -24,9 +24,9 @@ namespace {
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // The oscillator bank over the (k+1, amplitude) table for 4 samples: acc[s] += A_k sin(fl32(w_s (k+1)))
-// in ascending k.  H4 % 4 == 0.  (A register double buffer of the next 4 coefficients was re-rolled by
-// the compiler into load-then-use; forced through inline assembly it gained the compiler's own waits
-// and 11-15 extra instructions per iteration: not kept.)
+// in table order, which is descending k (frame_synth phase 2).  H4 % 4 == 0.  (A register double buffer of
+// the next 4 coefficients was re-rolled by the compiler into load-then-use; forced through inline assembly it
+// gained the compiler's own waits and 11-15 extra instructions per iteration: not kept.)
 __device__ __forceinline__ void osc_bank4(const float2* __restrict__ coef, int H4, const float (&w)[4],
                                           float (&acc)[4]) {
 #pragma unroll 4
@@ -79,6 +79,22 @@ __device__ __forceinline__ void osc_bank4_shared(const float2* __restrict__ coef
       for (int s = 0; s < 4; ++s) acc[s] = fmaf(sin_rev(reduce_rev_by(x[s], n)), c[u].y, acc[s]);
     }
   }
+}
+
+// Tap 32 of the 128-tap irfft, (A0 + A64 + 2 sum_k A_k cos(pi k / 2)) / 128, summed by one thread in the order in
+// which frame_synth's lane-pair path sums it across a wave: t_k = A_k cos(pi k / 2) on lane k (t_0 = 0), then the
+// xor butterfly over 32, 16, ..., 1, whose lane 0 ends with the tree below (an addition's operand order is free).
+__device__ __forceinline__ float irfft128_tap32(const float* A) {
+  auto t = [&](int k) { return k >= 1 ? A[k] * kIrCos128[k * 64 + 32] : 0.0f; };
+  float v[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) v[i] = (t(i) + t(i + 32)) + (t(i + 16) + t(i + 48));
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {
+#pragma unroll
+    for (int i = 0; i < o; ++i) v[i] = v[i] + v[i + o];
+  }
+  return (A[0] + A[64] + 2.0f * v[0]) * (1.0f / 128.0f);
 }
 
 // SPLIT (few-frame launches, e.g. the realtime stream's 4 frames per call): the workgroup has
@@ -138,7 +154,7 @@ __device__ __forceinline__ bool frame_synth(
     const float sv = scale_fn(i >= H && i < H + NB ? raw + bias : raw);
     if (i < H) {
       const float v = sv * ((pitch0 * (float)(i + 1)) < half_sr ? kOnePlusEps : kEps);  // controls_value
-      coef[i].y = v;
+      coef[H4 - 1 - i].y = v;  // harmonic i + 1 sits at table position H4 - 1 - i (phase 2)
       part_d += (double)v;
     } else if (i < H + NB) {
       A[i - H] = sv;
@@ -171,9 +187,15 @@ __device__ __forceinline__ bool frame_synth(
   const float a = tail[0];                 // scale_function(amplitude)
 
   // ---- phase 2: harmonic coefficient table; even half of the noise filter taps ----
-  for (int k = tid; k < H4; k += NT) {
-    const float v = k < H ? (coef[k].y / norm) * a : 0.0f;  // (dist / sum) * amp
-    coef[k] = make_float2((float)(k + 1), v);
+  // The table runs from the highest harmonic down (position p holds harmonic H4 - p; the padding comes first), so
+  // that every oscillator loop sums in descending k: the small terms first.  Spectra fall with k, and the
+  // harmonics past Nyquist, scaled by 1e-4, are the highest.  Summed in ascending k they were added one by one to
+  // a sum that was already complete, each addition rounding at that sum's ulp: at H = 1024 and 20 kHz (one audible
+  // harmonic, 1023 masked ones) 3.4e-6 of sum |A_k| per frame, against 5e-7 this way.
+  for (int p = tid; p < H4; p += NT) {
+    const int k = H4 - 1 - p;
+    const float v = k < H ? (coef[p].y / norm) * a : 0.0f;  // (dist / sum) * amp
+    coef[p] = make_float2((float)(k + 1), v);
   }
   if (n == 128 && NT >= 128) {
     // irfft taps (core.py:150): ir[m] = (A0 + (-1)^m A64 + 2 (O(m) + E(m))) / 128 with O the odd-k and E
@@ -204,7 +226,11 @@ __device__ __forceinline__ bool frame_synth(
       if (tid == 64) ir[32] = (A[0] + A[64] + 2.0f * t) * (1.0f / 128.0f);
     }
   } else {
-    for (int m = tid; m <= half; m += NT) ir[m] = irfft_tap(A, ct, n, m);
+    // A block of 256 or less at 65 bands comes here in the 4-samples-per-thread form (NT = 64) and takes the
+    // lane-pair path above in the SPLIT form (NT = 256).  Every tap of that path is irfft_tap's sum term for term
+    // except tap 32, which its second wave sums by a butterfly: the same tree here, so that a frame does not
+    // depend on the launch shape (the two forms used to differ in the last bit of that tap).
+    for (int m = tid; m <= half; m += NT) ir[m] = (n == 128 && m == 32) ? irfft128_tap32(A) : irfft_tap(A, ct, n, m);
   }
   __syncthreads();
 
@@ -292,7 +318,7 @@ __device__ __forceinline__ bool frame_synth(
         asm volatile(".p2align 3\n s_nop 0");
         osc_bank4(coef, H4, w, acc);
       } else {
-        for (int k = 0; k < H; ++k) {
+        for (int k = H4 - H; k < H4; ++k) {  // the H real harmonics, past the padding
           const float2 c = coef[k];
 #pragma unroll
           for (int s = 0; s < 4; ++s) {
@@ -335,7 +361,7 @@ __device__ __forceinline__ bool frame_synth(
           a = fmaf(sin_reduced(wj * c.x), c.y, a);
         }
       } else {
-        for (int k = 0; k < H; ++k) {
+        for (int k = H4 - H; k < H4; ++k) {
           const float2 c = coef[k];
           const float xx = wj * c.x;
           a = fmaf(fabsf(xx) < kFastArgLimit ? sin_reduced(xx) : sin_slow(xx), c.y, a);
@@ -362,7 +388,7 @@ __device__ __forceinline__ bool frame_synth(
     asm volatile("" : "+s"(co));
     const int64_t BF = (int64_t)B * F;
     if (tid == 0) co[frame] = a;
-    for (int k = tid; k < H; k += NT) co[BF + frame * H + k] = coef[k].y;
+    for (int k = tid; k < H; k += NT) co[BF + frame * H + k] = coef[H4 - 1 - k].y;
     for (int k = tid; k < NB; k += NT) co[BF * (1 + H) + frame * NB + k] = A[k];
   }
   if (!active) return false;

@@ -28,8 +28,6 @@
 namespace ddsp {
 namespace {
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // d/dx scale_function(x) = 2 ln10 sigmoid(x)^ln10 (1 - sigmoid(x)), with 1 - sigmoid formed as
 // e * sigmoid (no cancellation for large x).
 __device__ __forceinline__ float scale_fn_grad(float x) {

@@ -242,6 +242,9 @@ __device__ __forceinline__ void group_sum_double2(double& a, double& b, double* 
   }
 }
 
+// the C ABI's opaque stream handle
+inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
 inline int launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? DDSP_HIP_OK : DDSP_HIP_ELAUNCH;

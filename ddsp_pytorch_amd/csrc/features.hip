@@ -34,8 +34,6 @@
 namespace ddsp {
 namespace {
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int kMaxMels = 256;  // n_mels cap (the band tables live in LDS)
 constexpr int kDctFrames = 8;  // frames per workgroup of the DCT launch
 constexpr int kDctChunk = 32;  // mel columns of the DCT table staged per pass

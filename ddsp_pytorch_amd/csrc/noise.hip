@@ -23,8 +23,6 @@
 namespace ddsp {
 namespace {
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // ---------------------------------------------------------------------------------
 // amp_to_impulse_response(amp[rows, NB], target) -> [rows, target]   (core.py:144-166)
 // ---------------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "impulse.h"
 #include "upols.h"
 
 namespace ddsp {
@@ -23,27 +24,18 @@ int direct_convolve(const float* sig, const float* ker, float* out, int64_t rows
 
 namespace {
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int64_t kDirectMaxN = 4096;  // fft_convolve: direct LDS convolution up to this N
 
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
-// Reverb.build_impulse (modules.py:21-26), t = fl32(i / sr) as torch.arange(L) / sr.
+// Reverb.build_impulse (modules.py:21-26): the tap of impulse.h
 __global__ void build_impulse_kernel(const float* __restrict__ noise, const float* __restrict__ decay,
                                      const float* __restrict__ wet, float* __restrict__ imp,
                                      int64_t L, float sr) {
-  const float d = -decay[0];
-  // softplus(-decay) with torch's threshold 20
-  const float sp = d > 20.0f ? d : log1pf(expf(d));
-  const float neg = -sp;
-  const float w = 1.0f / (1.0f + expf(-wet[0]));
+  const ImpulseParams ip = impulse_params(decay[0], wet[0]);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < L;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float t = (float)i / sr;
-    const float env = expf((neg * t) * 500.0f);
-    imp[i] = i == 0 ? 1.0f : (noise[i] * env) * w;
-  }
+       i += (int64_t)gridDim.x * blockDim.x)
+    imp[i] = impulse_tap(ip, i, impulse_env(ip, i, sr), i == 0 ? 0.0f : noise[i]);
 }
 
 // Reverb.build_impulse backward (modules.py:21-26): imp[i] = noise[i] env[i] w (i >= 1),
@@ -59,19 +51,13 @@ __global__ void __launch_bounds__(256) impulse_backward_kernel(
     const float* __restrict__ dimp, int64_t grad_len, int64_t L, float sr, float* __restrict__ d_noise,
     double* __restrict__ partials) {
   __shared__ double red[32];
-  const float d = -decay[0];
-  const float sp = d > 20.0f ? d : log1pf(expf(d));
-  const float neg = -sp;
-  const float w = 1.0f / (1.0f + expf(-wet[0]));
+  const ImpulseParams ip = impulse_params(decay[0], wet[0]);
   double aw = 0.0, ad = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < L; i += (int64_t)gridDim.x * blockDim.x) {
-    const float t = (float)i / sr;
-    const float env = expf((neg * t) * 500.0f);
+    const float t = impulse_time(i, sr);
+    const float env = impulse_env(ip, t);
     const float gi = (i >= 1 && i < grad_len) ? dimp[i] : 0.0f;
-    d_noise[i] = gi * env * w;
-    const float gne = gi * noise[i] * env;
-    aw += (double)gne;
-    ad += (double)gne * (double)t;
+    d_noise[i] = impulse_tap_grad(ip, gi, noise[i], env, t, aw, ad);
   }
   block_sum_double2(aw, ad, red);
   if (threadIdx.x == 0) {
@@ -97,11 +83,8 @@ __global__ void __launch_bounds__(64) impulse_backward_finish_kernel(const doubl
     ad += __shfl_down(ad, o, 64);
   }
   if (threadIdx.x != 0) return;
-  const float d = -decay[0];
-  const float spg = d > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-d));  // softplus'(d)
-  const float w = 1.0f / (1.0f + expf(-wet[0]));
-  d_wet[0] = (float)(aw * (double)w * (1.0 - (double)w));
-  d_decay[0] = (float)(ad * (double)w * 500.0 * (double)spg);
+  const float spg = impulse_slope(impulse_arg(decay[0]));
+  impulse_close(impulse_wet(wet[0]), spg, aw, ad, d_decay, d_wet);
 }
 
 unsigned grid_for(int64_t n) {

@@ -26,8 +26,6 @@
 namespace ddsp {
 namespace {
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // grid (ceil(frames / (2 * 4096/N)), B), 256 threads
 template <int N>
 __global__ void __launch_bounds__(256) stft_mag_kernel(const float* __restrict__ x, int64_t T, int hop,

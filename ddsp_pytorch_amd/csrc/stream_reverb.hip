@@ -27,8 +27,6 @@
 namespace ddsp {
 namespace {
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 template <int N2>
 struct StreamShape {
   static constexpr int N = N2 / 2;                            // samples per call

@@ -402,8 +402,6 @@ inline unsigned grid1d(int64_t n, int nt) {
   return (unsigned)std::min<int64_t>(std::max<int64_t>(g, 1), 65536);
 }
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // One workgroup per (frame, item).  4 samples per thread when the block is long enough
 // (more independent sine chains per lane: measured 4% faster than 2 at block 512), else 2.
 template <bool RAW>

@@ -21,8 +21,6 @@
 namespace ddsp {
 namespace {
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // The oscillator bank over the (k+1, amplitude) table for 4 samples: acc[s] += A_k sin(fl32(w_s (k+1)))
 // in table order, which is descending k (frame_synth phase 2).  H4 % 4 == 0.  (A register double buffer of
 // the next 4 coefficients was re-rolled by the compiler into load-then-use; forced through inline assembly it

@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "impulse.h"
 #include "upols.h"
 #include "fft_radix.h"
 
@@ -60,6 +61,34 @@ __device__ __forceinline__ void fft4096(float2 (&v)[16], float2* lds, int j = th
   for (int r = 0; r < 16; ++r) v[r] = lds[lds_idx(j + 256 * r)];
   apply_tw(v, tw3);
   dft16<INV>(v);  // Ns = 256: output index == j + 256 r (coalesced)
+}
+
+// A transform's registers against one spectrum row: thread j holds elements j + 256 r
+__device__ __forceinline__ void row_load16(float2 (&v)[16], const float2* row, int j) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) v[r] = row[j + 256 * r];
+}
+__device__ __forceinline__ void row_store16(float2* row, const float2 (&v)[16], int j) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) row[j + 256 * r] = v[r];
+}
+
+// v = G_q = FFT(h[(q-1)P, (q+1)P) (zero outside [0, klen))) / N of one kernel window, h[s] = tap(s, r)
+// for the thread's r-th element: the one place a kernel spectrum is built (load, scale, transform).
+// The three callers store v with their own loop over out[j + 256 r], not row_store16: through the
+// helper the compiler splits that address another way and their register counts move.
+template <class Tap>
+__device__ __forceinline__ void window_spectrum(float2 (&v)[16], int q, int64_t klen, Tap tap, float2* lds) {
+  const int j = threadIdx.x;
+  const float inv_n = 1.0f / (float)kN;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t s = (int64_t)(q - 1) * kP + j + 256 * r;
+    float h = 0.0f;
+    if (s >= 0 && s < klen) h = tap(s, r);
+    v[r] = make_float2(h * inv_n, 0.0f);
+  }
+  fft4096<false>(v, lds);
 }
 
 // Complex multiply-accumulate as two packed FMAs (v_pk_fma_f32: two fp32 FMAs per lane per
@@ -112,9 +141,7 @@ __device__ __forceinline__ void forward_block(const float* __restrict__ x, int64
     v[r] = make_float2(ok ? xa[si] : 0.0f, (ok && xb) ? xb[si] : 0.0f);
   }
   fft4096<false>(v, lds);
-  float2* out = X + ((int64_t)pair * nb + b) * kN;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) out[j + 256 * r] = v[r];
+  row_store16(X + ((int64_t)pair * nb + b) * kN, v, j);
 }
 
 __global__ void __launch_bounds__(kNT) upols_forward_kernel(const float* __restrict__ x, int64_t ld,
@@ -130,8 +157,8 @@ __global__ void __launch_bounds__(kNT) upols_forward_kernel(const float* __restr
 // writes through .data).  Per kernel window q the cache keeps the spectrum G_q and a snapshot of the
 // exact inputs it was built from — the noise taps of the window [(q-1)P, (q+1)P) ∩ [0, klen) bit for
 // bit, decay, wet, the sample rate and klen + 1 (0 in a zero-filled cache: nothing valid yet).  The
-// window's workgroup compares them with the current parameters and rebuilds G_q (the arithmetic of
-// upols_impulse_spectrum_kernel, bit for bit) only when one differs or `force` is set.  Each
+// window's workgroup compares them with the current parameters and rebuilds G_q (as
+// upols_impulse_spectrum_kernel does, bit for bit) only when one differs or `force` is set.  Each
 // window's snapshot is its own (windows overlap by P taps), so no two workgroups write one word.
 constexpr int kSnapWords = 2 * kP + 4;
 
@@ -154,24 +181,9 @@ __device__ __forceinline__ void ir_window(const float* __restrict__ noise, const
     diff |= sq[2 * kP] != __float_as_uint(dec) || sq[2 * kP + 1] != __float_as_uint(wt) ||
             sq[2 * kP + 2] != __float_as_uint(sr) || sq[2 * kP + 3] != (uint32_t)(klen + 1);
   if (!__syncthreads_or(diff || force)) return;  // the cached G_q is this window's spectrum
-  const float d = -dec;
-  const float sp = d > 20.0f ? d : log1pf(expf(d));  // softplus(-decay), torch's threshold 20
-  const float neg = -sp;
-  const float w = 1.0f / (1.0f + expf(-wt));
-  const float inv_n = 1.0f / (float)kN;
+  const ImpulseParams ip = impulse_params(dec, wt);
   float2 v[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t s = (int64_t)(q - 1) * kP + j + 256 * r;
-    float h = 0.0f;
-    if (s >= 0 && s < klen) {
-      const float t = (float)s / sr;
-      const float env = expf((neg * t) * 500.0f);
-      h = s == 0 ? 1.0f : (nv[r] * env) * w;
-    }
-    v[r] = make_float2(h * inv_n, 0.0f);
-  }
-  fft4096<false>(v, lds);
+  window_spectrum(v, q, klen, [&](int64_t s, int r) { return impulse_tap(ip, s, impulse_env(ip, s, sr), nv[r]); }, lds);
   float2* out = Hs + (int64_t)q * kN;
 #pragma unroll
   for (int r = 0; r < 16; ++r) out[j + 256 * r] = v[r];
@@ -225,14 +237,8 @@ __global__ void __launch_bounds__(kNT) upols_kernel_spectrum_kernel(const float*
   __shared__ float2 lds[kPad];
   const int q = blockIdx.x, row = blockIdx.y, j = threadIdx.x;
   const float* hr = h + (int64_t)row * ld;
-  const float inv_n = 1.0f / (float)kN;
   float2 v[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t s = (int64_t)(q - 1) * kP + j + 256 * r;
-    v[r] = make_float2((s >= 0 && s < klen) ? hr[s] * inv_n : 0.0f, 0.0f);
-  }
-  fft4096<false>(v, lds);
+  window_spectrum(v, q, klen, [&](int64_t s, int) { return hr[s]; }, lds);
   float2* out = Hs + ((int64_t)row * QG + q) * kN;
 #pragma unroll
   for (int r = 0; r < 16; ++r) out[j + 256 * r] = v[r];
@@ -240,8 +246,8 @@ __global__ void __launch_bounds__(kNT) upols_kernel_spectrum_kernel(const float*
 
 // Reverb.build_impulse (modules.py:21-26) fused into the IR's partition spectra (modules.py:30-35):
 // G[q][:] = FFT(imp[(q-1)P, (q+1)P)) / N with imp[i] = noise[i] exp(-softplus(-decay) t 500) sigmoid(wet),
-// t = fl32(i / sr), imp[0] = 1, zero at or past klen — the arithmetic of reverb.hip's
-// build_impulse_kernel per tap, so the spectra are those of upols_spectrum(build_impulse(...)) bit for bit.
+// t = fl32(i / sr), imp[0] = 1, zero at or past klen — impulse.h's tap, the one reverb.hip's
+// build_impulse_kernel stores, so the spectra are those of upols_spectrum(build_impulse(...)) bit for bit.
 // One launch instead of two (the impulse never goes to HBM); grid (Q + 1)
 __global__ void __launch_bounds__(kNT) upols_impulse_spectrum_kernel(const float* __restrict__ noise,
                                                                      const float* __restrict__ decay,
@@ -249,59 +255,16 @@ __global__ void __launch_bounds__(kNT) upols_impulse_spectrum_kernel(const float
                                                                      float sr, int QG, float2* __restrict__ Hs) {
   __shared__ float2 lds[kPad];
   const int q = blockIdx.x, j = threadIdx.x;
-  const float d = -decay[0];
-  const float sp = d > 20.0f ? d : log1pf(expf(d));  // softplus(-decay), torch's threshold 20
-  const float neg = -sp;
-  const float w = 1.0f / (1.0f + expf(-wet[0]));
-  const float inv_n = 1.0f / (float)kN;
+  const ImpulseParams ip = impulse_params(decay[0], wet[0]);
   float2 v[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t s = (int64_t)(q - 1) * kP + j + 256 * r;
-    float h = 0.0f;
-    if (s >= 0 && s < klen) {
-      const float t = (float)s / sr;
-      const float env = expf((neg * t) * 500.0f);
-      h = s == 0 ? 1.0f : (noise[s] * env) * w;
-    }
-    v[r] = make_float2(h * inv_n, 0.0f);
-  }
-  fft4096<false>(v, lds);
+  window_spectrum(v, q, klen, [&](int64_t s, int) { return impulse_tap(ip, s, impulse_env(ip, s, sr), noise[s]); }, lds);
   float2* out = Hs + (int64_t)q * kN;
 #pragma unroll
   for (int r = 0; r < 16; ++r) out[j + 256 * r] = v[r];
 }
 
-// The same sums with the Z window as a register ring indexed statically.  The p loop is unrolled by
-// the ring size R = BLK + PF - 1, so the slot (m - b0) mod R of block m is a compile-time register
-// at every unrolled step and the window never shifts (no v_mov).  After step p's products, block
-// b0 - p - PF is loaded into the slot step p freed (block b0 + BLK - 1 - p), and G_{p+PF} into a
-// G ring of GR >= PF slots (GR | R): every operand is loaded PF steps before its first use.  The
-// unrolled rounds carry no per-step guards (guards made the compiler enter the round through a
-// jump table, whose joins forced a wait on every load at every step): steps past the last useful
-// one read the zero spectra of out-of-range descriptors (G_q, q >= Q; Z_m, m < 0) and add exact
-// zeros.  grid (N/256, ceil(nb/BLK), npairs)
-template <int BLK, int PF, int GR>
-__global__ void __launch_bounds__(kNT) upols_mac_ring_kernel(const float2* __restrict__ X,
-                                                             const float2* __restrict__ Hs,
-                                                             int64_t h_pair_stride, int nb, int Q,
-                                                             float2* __restrict__ Y) {
-  constexpr int R = BLK + PF - 1;
-  static_assert(PF >= 1 && R % GR == 0 && GR >= PF, "ring shapes");
-  constexpr int kRow = kN * (int)sizeof(float2);
-  const int f = blockIdx.x * kNT + threadIdx.x;
-  const int b0 = nb - (int)(gridDim.y - blockIdx.y) * BLK;
-  const int pair = blockIdx.z;
-  // Every spectrum row is read through a buffer descriptor built in SGPRs for that row (base =
-  // the row, lane offset = 8 f): no per-lane address arithmetic, and rows outside the signal or
-  // the kernel are descriptors with no records, whose loads return 0 without a select.
-  const float2* Xrow = X + (int64_t)pair * nb * kN;
-  const float2* Hrow = Hs + (int64_t)pair * h_pair_stride;
-  const int voff = f * (int)sizeof(float2);
-  float2 ring[R], g[GR];
-  v2f acc[BLK];
-// Cache policy of the input-spectra (Z) and kernel-spectra (G) loads: non-temporal (nt; G also
-// sc0).  With the default policy the fused synthesis kernel that follows the reverb in the next
+// Cache policy of the forward MAC's input-spectra (Z) and kernel-spectra (G) loads: non-temporal (nt; G
+// also sc0).  With the default policy the fused synthesis kernel that follows the reverb in the next
 // step runs at ~2.2 instead of ~2.38 GHz: the G loads' nt bit removes that, the Z
 // loads' adds a little (config-2 step 223.8-226.3 -> 208.3 us, tools/exp_timing.py, same box).
 // A/B builds override them (-DDDSP_MAC_ZAUX=0 -DDDSP_MAC_GAUX=0: the round-2 policy).
@@ -311,11 +274,91 @@ __global__ void __launch_bounds__(kNT) upols_mac_ring_kernel(const float2* __res
 #ifndef DDSP_MAC_GAUX
 #define DDSP_MAC_GAUX 3
 #endif
+
+// The two directions of the MAC, everything in which they differ:
+//   forward  Y_b = sum_q Z_{b-q} G_q                     (the lag-q operand of block b is block b - q)
+//   adjoint  V_k = (-1)^f sum_q conj(G_q) GZ_{k+q}       (block k + q; (-1)^f dZ_k, the form the
+//            forward's inverse kernel takes, see the backward below; one kernel for every pair)
+// The ring kernel's chunks of BLK output blocks are laid from the far end of the signal, so the
+// partial chunk sits at the end the operands run out at, and only blocks past that one end can lie
+// outside the signal: those are the descriptors with no records (zeros) and the outputs not stored.
+struct MacForward {
+  static constexpr int kStep = -1;  // block index of the operand per lag
+  static constexpr int kZAux = DDSP_MAC_ZAUX, kGAux = DDSP_MAC_GAUX;
+  // chunks end at the signal's end: the first one may start before block 0
+  static __device__ __forceinline__ int chunk_base(int nb, int blk) {
+    return nb - (int)(gridDim.y - blockIdx.y) * blk;
+  }
+  static __device__ __forceinline__ bool in_signal(int m, int) { return m >= 0; }
+  static __device__ __forceinline__ int clamped(int m, int) { return max(m, 0); }
+  static __device__ __forceinline__ int lags(int base, int, int blk) { return base + blk; }  // that reach block 0
+  static __device__ __forceinline__ void operand(float2 h, v2f& hb, v2f& hr) {
+    hb = (v2f){h.x, h.y};
+    hr = (v2f){-h.y, h.x};
+  }
+  static __device__ __forceinline__ const float2* kernel_rows(const float2* Hs, int pair, int64_t pair_stride) {
+    return Hs + (int64_t)pair * pair_stride;
+  }
+  static __device__ __forceinline__ float2 output(v2f acc, int) { return make_float2(acc.x, acc.y); }
+};
+struct MacAdjoint {
+  static constexpr int kStep = 1;
+  // default cache policy: the forward MAC's non-temporal bits slowed the train step here
+  // (0.556 -> 0.565-0.571 ms, DESIGN.md §3c)
+  static constexpr int kZAux = 0, kGAux = 0;
+  static __device__ __forceinline__ int chunk_base(int, int blk) { return blockIdx.y * blk; }
+  static __device__ __forceinline__ bool in_signal(int m, int nb) { return m < nb; }
+  static __device__ __forceinline__ int clamped(int m, int nb) { return min(m, nb - 1); }
+  static __device__ __forceinline__ int lags(int base, int nb, int) { return nb - base; }  // that stay below nb
+  static __device__ __forceinline__ void operand(float2 h, v2f& hb, v2f& hr) {  // conj(h) and its rotation
+    hb = (v2f){h.x, -h.y};
+    hr = (v2f){h.y, h.x};
+  }
+  static __device__ __forceinline__ const float2* kernel_rows(const float2* Hs, int, int64_t) { return Hs; }
+  static __device__ __forceinline__ float2 output(v2f acc, int f) {
+    const float sgn = (f & 1) ? -1.0f : 1.0f;
+    return make_float2(sgn * acc.x, sgn * acc.y);
+  }
+};
+
+// The same sums with the operand window as a register ring indexed statically.  A thread owns the
+// BLK output blocks b0 + d; at lag p it needs the blocks b0 + d + kStep p, a window that slides one
+// block per lag (backward in the forward MAC, forward in the adjoint).  The p loop is unrolled by
+// the ring size R = BLK + PF - 1, so the slot (m - b0) mod R of block m is a compile-time register
+// at every unrolled step and the window never shifts (no v_mov).  After step p's products, the
+// block the window reaches PF steps later is loaded into the slot step p freed, and G_{p+PF} into a
+// G ring of GR >= PF slots (GR | R): every operand is loaded PF steps before its first use.  The
+// unrolled rounds carry no per-step guards (guards made the compiler enter the round through a
+// jump table, whose joins forced a wait on every load at every step): steps past the last useful
+// one read the zero spectra of out-of-range descriptors (G_q, q >= Q; blocks outside the signal)
+// and add exact zeros.  grid (N/256, ceil(nb/BLK), npairs)
+template <class Dir, int BLK, int PF, int GR>
+__global__ void __launch_bounds__(kNT) upols_mac_ring_kernel(const float2* __restrict__ X,
+                                                             const float2* __restrict__ Hs,
+                                                             int64_t h_pair_stride, int nb, int Q,
+                                                             float2* __restrict__ Y) {
+  constexpr int R = BLK + PF - 1;
+  static_assert(PF >= 1 && R % GR == 0 && GR >= PF, "ring shapes");
+  constexpr int kRow = kN * (int)sizeof(float2);
+  constexpr int kStep = Dir::kStep;
+  constexpr int kLead = kStep > 0 ? BLK - 1 : 0;  // the window's leading block at lag 0, from b0
+  constexpr auto slot = [](int e) { return (e % R + R) % R; };
+  const int f = blockIdx.x * kNT + threadIdx.x;
+  const int b0 = Dir::chunk_base(nb, BLK);
+  const int pair = blockIdx.z;
+  // Every spectrum row is read through a buffer descriptor built in SGPRs for that row (base =
+  // the row, lane offset = 8 f): no per-lane address arithmetic, and rows outside the signal or
+  // the kernel are descriptors with no records, whose loads return 0 without a select.
+  const float2* Xrow = X + (int64_t)pair * nb * kN;
+  const float2* Hrow = Dir::kernel_rows(Hs, pair, h_pair_stride);
+  const int voff = f * (int)sizeof(float2);
+  float2 ring[R], g[GR];
+  v2f acc[BLK];
   auto zload = [&](int m, float2& dst) {
-    dst = row_load<DDSP_MAC_ZAUX>(Xrow + (int64_t)max(m, 0) * kN, m >= 0 ? kRow : 0, voff);
+    dst = row_load<Dir::kZAux>(Xrow + (int64_t)Dir::clamped(m, nb) * kN, Dir::in_signal(m, nb) ? kRow : 0, voff);
   };
   auto gload = [&](int q, float2& dst) {
-    dst = row_load<DDSP_MAC_GAUX>(Hrow + (int64_t)min(q, Q - 1) * kN, q < Q ? kRow : 0, voff);
+    dst = row_load<Dir::kGAux>(Hrow + (int64_t)min(q, Q - 1) * kN, q < Q ? kRow : 0, voff);
   };
 #pragma unroll
   for (int d = 0; d < BLK; ++d) {
@@ -323,20 +366,20 @@ __global__ void __launch_bounds__(kNT) upols_mac_ring_kernel(const float2* __res
     zload(b0 + d, ring[d]);
   }
 #pragma unroll
-  for (int j = 1; j < PF; ++j) zload(b0 - j, ring[R - j]);
+  for (int j = 1; j < PF; ++j) zload(b0 + kLead + kStep * j, ring[slot(kLead + kStep * j)]);
 #pragma unroll
   for (int j = 0; j < PF; ++j) gload(j, g[j]);
-  const int pmax = min(Q, b0 + BLK);
+  const int pmax = min(Q, Dir::lags(b0, nb, BLK));
   for (int pb = 0; pb < pmax; pb += R) {
 #pragma unroll
     for (int u = 0; u < R; ++u) {
       const int p = pb + u;
-      const float2 h = g[u % GR];
-      const v2f hb = {h.x, h.y}, hr = {-h.y, h.x};
+      v2f hb, hr;
+      Dir::operand(g[u % GR], hb, hr);
 #pragma unroll
-      for (int d = 0; d < BLK; ++d) cmac(acc[d], ring[(d - u + R) % R], hb, hr);
+      for (int d = 0; d < BLK; ++d) cmac(acc[d], ring[slot(d + kStep * u)], hb, hr);
       gload(p + PF, g[(u + PF) % GR]);
-      zload(b0 - p - PF, ring[(BLK - 1 - u + R) % R]);
+      zload(b0 + kStep * p + (kStep * PF + kLead), ring[slot(kLead + kStep * (u + PF))]);
       // keep the scheduler from sinking the loads toward their uses (it did, to cut register
       // live ranges, which turned the prefetch into a wait on every load)
       __builtin_amdgcn_sched_barrier(0);
@@ -345,59 +388,65 @@ __global__ void __launch_bounds__(kNT) upols_mac_ring_kernel(const float2* __res
   float2* Yp = Y + (int64_t)pair * nb * kN + f;
 #pragma unroll
   for (int d = 0; d < BLK; ++d)
-    if (b0 + d >= 0) Yp[(int64_t)(b0 + d) * kN] = make_float2(acc[d].x, acc[d].y);
+    if (Dir::in_signal(b0 + d, nb)) Yp[(int64_t)(b0 + d) * kN] = Dir::output(acc[d], f);
 }
 
-
-// The same sums for a whole pair row in one thread (nb == NBK, Q <= NQ): every Z_m and G_q of the bin is
-// loaded once and stays in registers (the ring kernel's two 25-block chunks re-read ~1.5x of Z: 122 vs
-// 104 MB at config 2), and the outputs stream — step b issues the loads of step b + PF (Z_{b+PF},
-// G_{b+PF}), then forms Y_b = sum_{q <= min(b, NQ-1)} Z_{b-q} G_q from operands already in registers and
-// stores it, so loads, products and stores overlap inside every wave (166 VGPRs; grid N/256 x npairs:
-// one round at 2 waves per SIMD).  Same-box A/Bs at config 2 (profiles/r05_ab_mac_vjp.log): 24.5-24.8 us
-// against 32.1-32.4 us for the ring kernel on boxes where the ring runs 32 us (step -3.8 / -6.4 us), equal
-// (25.0 vs 24.9-25.0 us) where the ring runs 25 us.  The ring kernel serves the other shapes.
-template <int NBK, int NQ, int PF>
+// The same sums for a whole pair row in one thread (nb == NBK, Q <= NQ): every operand block and G_q of
+// the bin is loaded once and stays in registers (the ring kernel's two 25-block chunks re-read ~1.5x of
+// them: 122 vs 104 MB of Z at config 2), and the outputs stream from the end the window starts at (the
+// forward from block 0 up, the adjoint from block NBK - 1 down) — step s issues the loads of step s + PF
+// (the next operand block, G_{s+PF}), then forms its output block from the s + 1 blocks and kernel
+// windows already in registers and stores it, so loads, products and stores overlap inside every wave
+// (166 VGPRs; grid N/256 x npairs: one round at 2 waves per SIMD).  Same-box A/Bs at config 2, forward
+// (profiles/r05_ab_mac_vjp.log): 24.5-24.8 us against 32.1-32.4 us for the ring kernel on boxes where the
+// ring runs 32 us (step -3.8 / -6.4 us), equal (25.0 vs 24.9-25.0 us) where the ring runs 25 us; adjoint:
+// 23.1-23.2 us against 29.8-29.9 for the ring kernel (tools/ab_prof.sh reverb_bwd).  The ring kernel
+// serves the other shapes.
+template <class Dir, int NBK, int NQ, int PF>
 __global__ void __launch_bounds__(kNT) upols_mac_stream_kernel(const float2* __restrict__ X,
                                                                const float2* __restrict__ Hs,
                                                                int64_t h_pair_stride, int nb, int Q,
                                                                float2* __restrict__ Y) {
   constexpr int kRow = kN * (int)sizeof(float2);
+  constexpr int kStep = Dir::kStep;
+  constexpr auto block = [](int s) { return kStep < 0 ? s : NBK - 1 - s; };  // output block of step s
   const int f = blockIdx.x * kNT + threadIdx.x;
   const int pair = blockIdx.y;
   const float2* Xrow = X + (int64_t)pair * nb * kN;
-  const float2* Hrow = Hs + (int64_t)pair * h_pair_stride;
+  const float2* Hrow = Dir::kernel_rows(Hs, pair, h_pair_stride);
   const int voff = f * (int)sizeof(float2);
   float2 z[NBK], g[NQ];
-  auto zload = [&](int m) { z[m] = row_load<DDSP_MAC_ZAUX>(Xrow + (int64_t)m * kN, kRow, voff); };
-  auto gload = [&](int q) { g[q] = row_load<DDSP_MAC_GAUX>(Hrow + (int64_t)min(q, Q - 1) * kN, q < Q ? kRow : 0, voff); };
+  auto zload = [&](int m) { z[m] = row_load<Dir::kZAux>(Xrow + (int64_t)m * kN, kRow, voff); };
+  auto gload = [&](int q) { g[q] = row_load<Dir::kGAux>(Hrow + (int64_t)min(q, Q - 1) * kN, q < Q ? kRow : 0, voff); };
 #pragma unroll
   for (int s = 0; s < PF; ++s) {
     if (s < NQ) gload(s);
-    zload(s);
+    zload(block(s));
   }
   float2* Yp = Y + (int64_t)pair * nb * kN + f;
 #pragma unroll
-  for (int b = 0; b < NBK; ++b) {
-    if (b + PF < NQ) gload(b + PF);
-    if (b + PF < NBK) zload(b + PF);
+  for (int s = 0; s < NBK; ++s) {
+    const int b = block(s);
+    if (s + PF < NQ) gload(s + PF);
+    if (s + PF < NBK) zload(block(s + PF));
     __builtin_amdgcn_sched_barrier(0);
     v2f acc = {0.f, 0.f}, acc2 = {0.f, 0.f};
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-      if (q <= b) {
-        const float2 h = g[q];
-        if (q & 1) cmac(acc2, z[b - q], (v2f){h.x, h.y}, (v2f){-h.y, h.x});
-        else cmac(acc, z[b - q], (v2f){h.x, h.y}, (v2f){-h.y, h.x});
+      if (q <= s) {
+        v2f hb, hr;
+        Dir::operand(g[q], hb, hr);
+        if (q & 1) cmac(acc2, z[b + kStep * q], hb, hr);
+        else cmac(acc, z[b + kStep * q], hb, hr);
       }
     }
-    Yp[(int64_t)b * kN] = make_float2(acc.x + acc2.x, acc.y + acc2.y);
+    Yp[(int64_t)b * kN] = Dir::output((v2f){acc.x + acc2.x, acc.y + acc2.y}, f);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
 
-// The whole-row MAC forms (upols_mac_stream_kernel, upols_mac_adj_stream_kernel) for the row length they
-// are built for: 50 blocks (config 2's 102400 samples), up to 25 kernel windows (a 1 s IR at 48 kHz)
+// The whole-row MAC form (upols_mac_stream_kernel, both directions) for the row length it
+// is built for: 50 blocks (config 2's 102400 samples), up to 25 kernel windows (a 1 s IR at 48 kHz)
 constexpr int kStreamNB = 50, kStreamNQ = 25, kStreamPF = 4;
 
 // y[row][bP + n] = IFFT(Y_b)[P + n]; grid (nb, npairs)
@@ -409,7 +458,7 @@ __global__ void __launch_bounds__(kNT) upols_inverse_kernel(const float2* __rest
   const float2* in = Y + ((int64_t)pair * nb + b) * kN;
   float2 v[16];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) v[r] = in[j + 256 * r];
+  for (int r = 0; r < 16; ++r) v[r] = in[j + 256 * r];  // not row_load16: it moves this hot kernel's schedule
   fft4096<true>(v, lds);
   int ra, rb;
   pair_rows(pair, rows, pairing, ra, rb);
@@ -431,7 +480,7 @@ __global__ void __launch_bounds__(kNT) upols_inverse_kernel(const float2* __rest
 // Backward of the partitioned convolution (Reverb.forward, modules.py:28-35), the adjoint of
 // each forward step (F = unnormalised FFT, its adjoint the unnormalised inverse):
 //   y_b = second half of F^-1(Y_b)           ->  dY_b = GZ_b = F([0, g_b])
-//   Y_b = sum_q Z_{b-q} G_q                   ->  dZ_k = sum_q conj(G_q) GZ_{k+q}   (upols_mac_adj_kernel)
+//   Y_b = sum_q Z_{b-q} G_q                   ->  dZ_k = sum_q conj(G_q) GZ_{k+q}   (the MAC kernels, MacAdjoint)
 //                                                 dG_q = sum_b conj(Z_{b-q}) GZ_b  (upols_corr_kernel)
 //   Z_b = F([x_b, 0])                         ->  dx_b = first half of F^-1(dZ_b) = second half of
 //                                                 F^-1((-1)^f dZ_b), so the forward's inverse kernel applies
@@ -493,108 +542,6 @@ __global__ void __launch_bounds__(64 * kCorrSlices) upols_corr_kernel(const floa
   }
 }
 
-// The adjoint MAC on the forward MAC's register ring: the window over GZ_{j0+d+q} (d < BLK) slides
-// forward, so block m sits in slot (m - j0) mod R (R = BLK + PF - 1), step u of a round reads slot
-// (d + u) mod R, and after its products block j0 + q + BLK + PF - 1 is loaded into the slot step q
-// freed (block j0 + q).  Blocks past the signal and windows past the kernel are descriptors with
-// no records (zeros), so the unrolled rounds carry no guards.  grid (N/256, ceil(nb/BLK), npairs)
-template <int BLK, int PF, int GR>
-__global__ void __launch_bounds__(kNT) upols_mac_adj_ring_kernel(const float2* __restrict__ G,
-                                                                 const float2* __restrict__ Hs, int nb, int Q,
-                                                                 float2* __restrict__ V) {
-  constexpr int R = BLK + PF - 1;
-  static_assert(PF >= 1 && R % GR == 0 && GR >= PF, "ring shapes");
-  constexpr int kRow = kN * (int)sizeof(float2);
-  const int f = blockIdx.x * kNT + threadIdx.x;
-  const int j0 = blockIdx.y * BLK;
-  const int pair = blockIdx.z;
-  const float2* Grow = G + (int64_t)pair * nb * kN;
-  const int voff = f * (int)sizeof(float2);
-  float2 ring[R], g[GR];
-  v2f acc[BLK];
-  // default cache policy: the forward MAC's non-temporal bits slowed the train step here
-  // (0.556 -> 0.565-0.571 ms, DESIGN.md §3c)
-  auto zload = [&](int m, float2& dst) {
-    dst = row_load<0>(Grow + (int64_t)min(m, nb - 1) * kN, m < nb ? kRow : 0, voff);
-  };
-  auto hload = [&](int q, float2& dst) {
-    dst = row_load<0>(Hs + (int64_t)min(q, Q - 1) * kN, q < Q ? kRow : 0, voff);
-  };
-#pragma unroll
-  for (int d = 0; d < BLK; ++d) {
-    acc[d] = (v2f){0.f, 0.f};
-    zload(j0 + d, ring[d]);
-  }
-#pragma unroll
-  for (int i = BLK; i < R; ++i) zload(j0 + i, ring[i]);
-#pragma unroll
-  for (int i = 0; i < PF; ++i) hload(i, g[i]);
-  const int qmax = min(Q, nb - j0);
-  for (int qb = 0; qb < qmax; qb += R) {
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-      const int q = qb + u;
-      const float2 h = g[u % GR];
-      const v2f hc = {h.x, -h.y}, hcr = {h.y, h.x};  // conj(h) and its rotation
-#pragma unroll
-      for (int d = 0; d < BLK; ++d) cmac(acc[d], ring[(d + u) % R], hc, hcr);
-      hload(q + PF, g[(u + PF) % GR]);
-      zload(j0 + q + R, ring[u]);
-      __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ahead of its use (see the forward MAC)
-    }
-  }
-  const float sgn = (f & 1) ? -1.0f : 1.0f;
-  float2* Vp = V + (int64_t)pair * nb * kN + f;
-#pragma unroll
-  for (int d = 0; d < BLK; ++d)
-    if (j0 + d < nb) Vp[(int64_t)(j0 + d) * kN] = make_float2(sgn * acc[d].x, sgn * acc[d].y);
-}
-
-// The adjoint sums for a whole pair row in one thread (nb == NBK, Q <= NQ): every GZ_m and H_q of the
-// bin is loaded once and stays in registers (the ring kernel's two chunks re-read ~1.5x of GZ), and the
-// outputs stream — step s issues the loads of step s + PF (GZ_{k-PF}, H_{s+PF}), then forms V_k,
-// k = NBK-1-s, from GZ_k..GZ_{k+s} and H_0..H_s already in registers and stores it, so loads, products
-// and stores overlap inside every wave (166 VGPRs; grid N/256 x npairs, one round at 2 waves/SIMD).
-// Config 2: 23.1-23.2 us against 29.8-29.9 for the ring kernel (same box, tools/ab_prof.sh reverb_bwd).
-template <int NBK, int NQ, int PF>
-__global__ void __launch_bounds__(kNT) upols_mac_adj_stream_kernel(const float2* __restrict__ G,
-                                                                   const float2* __restrict__ Hs, int nb, int Q,
-                                                                   float2* __restrict__ V) {
-  constexpr int kRow = kN * (int)sizeof(float2);
-  const int f = blockIdx.x * kNT + threadIdx.x;
-  const int pair = blockIdx.y;
-  const float2* Grow = G + (int64_t)pair * nb * kN;
-  const int voff = f * (int)sizeof(float2);
-  float2 z[NBK], h[NQ];
-  auto zload = [&](int m) { z[m] = row_load<0>(Grow + (int64_t)m * kN, kRow, voff); };
-  auto hload = [&](int q) { h[q] = row_load<0>(Hs + (int64_t)min(q, Q - 1) * kN, q < Q ? kRow : 0, voff); };
-#pragma unroll
-  for (int s = 0; s < PF; ++s) {
-    if (s < NQ) hload(s);
-    zload(NBK - 1 - s);
-  }
-  const float sgn = (f & 1) ? -1.0f : 1.0f;
-  float2* Vp = V + (int64_t)pair * nb * kN + f;
-#pragma unroll
-  for (int s = 0; s < NBK; ++s) {
-    const int k = NBK - 1 - s;
-    if (s + PF < NQ) hload(s + PF);
-    if (s + PF < NBK) zload(k - PF);
-    __builtin_amdgcn_sched_barrier(0);
-    v2f acc = {0.f, 0.f}, acc2 = {0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      if (q <= s) {
-        const float2 c = h[q];
-        if (q & 1) cmac(acc2, z[k + q], (v2f){c.x, -c.y}, (v2f){c.y, c.x});
-        else cmac(acc, z[k + q], (v2f){c.x, -c.y}, (v2f){c.y, c.x});
-      }
-    }
-    Vp[(int64_t)k * kN] = make_float2(sgn * (acc.x + acc2.x), sgn * (acc.y + acc2.y));
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
 // dimp[pP + n] = Re(IFFT(sum_groups part[grp][p] + (-1)^f part[grp][p+1])) [P + n] / N for n < P,
 // pP + n < klen (part holds Q + 1 lags; lag Q + 1 is zero), in two kernels:
 // sum[p][f] = sum_groups part[grp][p][f] + (-1)^f part[grp][p+1][f] (lag Q + 1 is zero): the group
@@ -623,10 +570,8 @@ __global__ void __launch_bounds__(kNT) upols_corr_finish_kernel(const float2* __
                                                                 float* __restrict__ dimp) {
   __shared__ float2 lds[kPad];
   const int p = blockIdx.x, j = threadIdx.x;
-  const float2* in = sum + (int64_t)p * kN;
   float2 v[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) v[r] = in[j + 256 * r];
+  row_load16(v, sum + (int64_t)p * kN, j);
   fft4096<true>(v, lds);
   const float inv_n = 1.0f / (float)kN;
 #pragma unroll
@@ -637,7 +582,7 @@ __global__ void __launch_bounds__(kNT) upols_corr_finish_kernel(const float2* __
 }
 
 // upols_corr_finish_kernel fused with Reverb.build_impulse's backward (modules.py:21-26; reverb.hip
-// impulse_backward_kernel, the same per-tap arithmetic, so d_noise is bit-identical): workgroup p turns its
+// impulse_backward_kernel calls the same impulse.h per tap, so d_noise is bit-identical): workgroup p turns its
 // 2048 taps of dimp straight into d_noise and fp64 partial sums of sum dimp*noise*env and sum
 // dimp*noise*env*t; the last workgroup to arrive (counter zeroed by upols_corr_sum_kernel) reduces the
 // partials in index order (deterministic) into d_wet and d_decay and leaves the counter at 0.  Two launches
@@ -649,21 +594,16 @@ __global__ void __launch_bounds__(kNT) upols_corr_finish_impulse_kernel(
   __shared__ double red[32];
   __shared__ bool last;
   const int p = blockIdx.x, j = threadIdx.x, Qp = gridDim.x;
-  const float2* in = sum + (int64_t)p * kN;
   float2 v[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) v[r] = in[j + 256 * r];
+  row_load16(v, sum + (int64_t)p * kN, j);
   // the taps' envelope and noise ahead of the transform (independent of dimp; their latency hides under it)
-  const float d = -ig.decay[0];
-  const float sp = d > 20.0f ? d : log1pf(expf(d));
-  const float neg = -sp;
-  const float w = 1.0f / (1.0f + expf(-ig.wet[0]));
+  const ImpulseParams ip = impulse_params(ig.decay[0], ig.wet[0]);
   float tt[8], env[8], nz[8];
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     const int64_t i = (int64_t)p * kP + j + 256 * r;
-    tt[r] = (float)i / ig.sr;
-    env[r] = expf((neg * tt[r]) * 500.0f);
+    tt[r] = impulse_time(i, ig.sr);
+    env[r] = impulse_env(ip, tt[r]);
     nz[r] = i < ig.L ? ig.noise[i] : 0.0f;
   }
   fft4096<true>(v, lds);
@@ -676,10 +616,7 @@ __global__ void __launch_bounds__(kNT) upols_corr_finish_impulse_kernel(
     if (dimp && i < kc) dimp[i] = di;
     if (i < ig.L) {
       const float gi = (i >= 1 && i < kc) ? di : 0.0f;
-      ig.d_noise[i] = gi * env[r] * w;
-      const float gne = gi * nz[r] * env[r];
-      aw += (double)gne;
-      ad += (double)gne * (double)tt[r];
+      ig.d_noise[i] = impulse_tap_grad(ip, gi, nz[r], env[r], tt[r], aw, ad);
     }
   }
   // taps past the partitions (an IR longer than the signal): no gradient
@@ -705,13 +642,9 @@ __global__ void __launch_bounds__(kNT) upols_corr_finish_impulse_kernel(
     sd += __shfl_down(sd, o, 64);
   }
   if (j != 0) return;
-  const float spg = d > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-d));  // softplus'(d)
-  ig.d_wet[0] = (float)(sw * (double)w * (1.0 - (double)w));
-  ig.d_decay[0] = (float)(sd * (double)w * 500.0 * (double)spg);
+  impulse_close(ip.w, impulse_slope(ip.d), sw, sd, ig.d_decay, ig.d_wet);
   *arrivals = 0u;
 }
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 }  // namespace
 
@@ -735,10 +668,18 @@ size_t upols_workspace_bytes(int64_t rows, int64_t n, bool pairing) {
   return 2 * (size_t)npairs * (size_t)upols_blocks(n) * kN * sizeof(float2);
 }
 
+// The grid limits of every launch here: nb signal blocks (x of the transforms; chunks of kRingBlk on
+// the ring MAC's y), rows pairs or kernel rows (y or z), wins kernel windows or lags (x or y: held to
+// the y limit wherever they sit).
+static int64_t ring_chunks(int64_t nb) { return (nb + kRingBlk - 1) / kRingBlk; }
+static bool grid_fits(int64_t nb, int64_t rows, int64_t wins) {
+  return nb <= INT32_MAX && ring_chunks(nb) <= 65535 && rows <= 65535 && wins <= 65535;
+}
+
 int upols_spectrum(const float* h, int64_t ld, int64_t klen, int64_t krows, float* spectrum,
                    void* stream) {
   const int64_t QG = upols_kernel_windows(klen);
-  if (QG > 65535 || krows > 65535) return DDSP_HIP_EINVAL;
+  if (!grid_fits(0, krows, QG)) return DDSP_HIP_EINVAL;
   hipLaunchKernelGGL(upols_kernel_spectrum_kernel, dim3((unsigned)QG, (unsigned)krows), dim3(kNT), 0,
                      S(stream), h, ld, klen, (int)QG, reinterpret_cast<float2*>(spectrum));
   return launch_status();
@@ -747,7 +688,7 @@ int upols_spectrum(const float* h, int64_t ld, int64_t klen, int64_t krows, floa
 int upols_impulse_spectrum(const float* noise, const float* decay, const float* wet, int64_t klen, float sr,
                            float* spectrum, void* stream) {
   const int64_t QG = upols_kernel_windows(klen);
-  if (QG > 65535) return DDSP_HIP_EINVAL;
+  if (!grid_fits(0, 0, QG)) return DDSP_HIP_EINVAL;
   hipLaunchKernelGGL(upols_impulse_spectrum_kernel, dim3((unsigned)QG), dim3(kNT), 0, S(stream), noise, decay, wet,
                      klen, sr, (int)QG, reinterpret_cast<float2*>(spectrum));
   return launch_status();
@@ -764,6 +705,27 @@ static int launch_forward(const float* x, int64_t n, int64_t rows, int pairing, 
   return launch_status();
 }
 
+// The MAC of one direction over the block spectra `in`: the whole-row form for the shape it is built
+// for, else the ring with kRingBlk (25) output blocks per thread: each operand row is re-read
+// (Q+BLK-1)/BLK times through L2 (A/B at config 2, forward: 25 blocks 26.6 us vs 16 blocks 28.3 us, 8
+// and 32 no better; measured slower: an LDS-tiled variant that reads Z once, 25%: lower occupancy,
+// exposed loads; every operand loaded up front from registers, 40%: 202 VGPRs, 2 waves/SIMD; one thread
+// per (pair, bin) streaming all blocks with a register ring, 8%)
+template <class Dir>
+static int launch_mac(const float2* in, const float* spectrum, int64_t h_stride, int64_t nb, int64_t Q,
+                      int64_t npairs, float2* out, void* stream) {
+  const float2* Hs = reinterpret_cast<const float2*>(spectrum);
+  if (nb == kStreamNB && Q <= kStreamNQ)
+    hipLaunchKernelGGL((upols_mac_stream_kernel<Dir, kStreamNB, kStreamNQ, kStreamPF>),
+                       dim3(kN / kNT, (unsigned)npairs), dim3(kNT), 0, S(stream), in, Hs, h_stride, (int)nb, (int)Q,
+                       out);
+  else
+    hipLaunchKernelGGL((upols_mac_ring_kernel<Dir, kRingBlk, kRingPF, kRingGR>),
+                       dim3(kN / kNT, (unsigned)ring_chunks(nb), (unsigned)npairs), dim3(kNT), 0, S(stream), in, Hs,
+                       h_stride, (int)nb, (int)Q, out);
+  return launch_status();
+}
+
 int upols_apply_spectra(const float2* Z, int64_t rows, int64_t n, const float* spectrum, int64_t klen,
                         bool per_row_kernel, float* y, float2* Y, void* stream, bool reverse) {
   const bool pairing = !per_row_kernel;
@@ -771,22 +733,8 @@ int upols_apply_spectra(const float2* Z, int64_t rows, int64_t n, const float* s
   const int64_t nb = upols_blocks(n);
   const int64_t Q = upols_kernel_windows(std::min(klen, n));
   const int64_t h_stride = per_row_kernel ? upols_kernel_windows(klen) * kN : 0;
-  constexpr int RB = kRingBlk;
-  if (nb > INT32_MAX || npairs > 65535 || (nb + RB - 1) / RB > 65535) return DDSP_HIP_EINVAL;
-  // kRingBlk (25) output blocks per thread: each Z row is re-read (Q+BLK-1)/BLK times through L2
-  // (A/B at config 2: 25 blocks 26.6 us vs 16 blocks 28.3 us, 8 and 32 no better; measured slower:
-  // an LDS-tiled variant that reads Z once, 25%: lower occupancy, exposed loads; every operand
-  // loaded up front from registers, 40%: 202 VGPRs, 2 waves/SIMD; one thread per (pair, bin)
-  // streaming all blocks with a register ring, 8%)
-  if (nb == kStreamNB && Q <= kStreamNQ)
-    hipLaunchKernelGGL((upols_mac_stream_kernel<kStreamNB, kStreamNQ, kStreamPF>), dim3(kN / kNT, (unsigned)npairs),
-                       dim3(kNT), 0, S(stream), Z, reinterpret_cast<const float2*>(spectrum), h_stride, (int)nb,
-                       (int)Q, Y);
-  else
-  hipLaunchKernelGGL((upols_mac_ring_kernel<RB, kRingPF, kRingGR>),
-                     dim3(kN / kNT, (unsigned)((nb + RB - 1) / RB), (unsigned)npairs), dim3(kNT), 0, S(stream), Z,
-                     reinterpret_cast<const float2*>(spectrum), h_stride, (int)nb, (int)Q, Y);
-  int st = launch_status();
+  if (!grid_fits(nb, npairs, 0)) return DDSP_HIP_EINVAL;
+  int st = launch_mac<MacForward>(Z, spectrum, h_stride, nb, Q, npairs, Y, stream);
   if (st) return st;
   hipLaunchKernelGGL(upols_inverse_kernel, dim3((unsigned)nb, (unsigned)npairs), dim3(kNT), 0, S(stream),
                      Y, (int)nb, n, (int)rows, (int)pairing, (int)reverse, y, n);
@@ -799,7 +747,7 @@ int upols_apply(const float* x, int64_t rows, int64_t n, const float* spectrum, 
   const int64_t npairs = pairing ? (rows + 1) / 2 : rows;
   const int64_t nb = upols_blocks(n);
   if (!ws || ws_bytes < upols_workspace_bytes(rows, n, pairing)) return DDSP_HIP_EWORKSPACE;
-  if (nb > INT32_MAX || npairs > 65535) return DDSP_HIP_EINVAL;
+  if (!grid_fits(nb, npairs, 0)) return DDSP_HIP_EINVAL;
   float2* X = reinterpret_cast<float2*>(ws);
   float2* Y = X + (size_t)npairs * nb * kN;
   // Z_b = FFT([x_b, 0])
@@ -819,7 +767,8 @@ int upols_reverb_cached(const float* x, int64_t rows, int64_t n, const float* no
   const int64_t QG = upols_kernel_windows(klen);
   const int64_t npairs = (rows + 1) / 2;
   const int64_t nb = rows > 0 ? upols_blocks(n) : 0;
-  if (QG > 65535 || nb > 65535 || npairs > 65534) return DDSP_HIP_EINVAL;
+  // one launch with blocks and windows on x (both held to the window limit) and a row more than the pairs
+  if (!grid_fits(nb, npairs + 1, std::max(nb, QG))) return DDSP_HIP_EINVAL;
   if (rows > 0 && (!ws || ws_bytes < upols_workspace_bytes(rows, n, true))) return DDSP_HIP_EWORKSPACE;
   float2* Hs = reinterpret_cast<float2*>(cache);
   uint32_t* snap = reinterpret_cast<uint32_t*>(Hs + (size_t)QG * kN);
@@ -857,7 +806,7 @@ int upols_backward(const float* x, const float* x_spectra, const float* spectrum
   const int64_t groups = corr_groups(npairs);
   const bool need_x = (dimp || ig) && !x_spectra;
   if (!ws || ws_bytes < upols_backward_workspace_bytes(rows, n, klen, !need_x)) return DDSP_HIP_EWORKSPACE;
-  if (nb > INT32_MAX || npairs > 65535 || Q > 65535 || (nb + kRingBlk - 1) / kRingBlk > 65535) return DDSP_HIP_EINVAL;
+  if (!grid_fits(nb, npairs, Q)) return DDSP_HIP_EINVAL;
   const size_t sb = upols_spectra_bytes(rows, n);
   char* w = reinterpret_cast<char*>(ws);
   float2* GZ = reinterpret_cast<float2*>(w);
@@ -873,16 +822,7 @@ int upols_backward(const float* x, const float* x_spectra, const float* spectrum
   int st = launch_forward(g, n, rows, 1, nb, npairs, -1, 1, 0, GZ, stream);
   if (st) return st;
   if (dx) {
-    constexpr int AB = kRingBlk;
-    if (nb == kStreamNB && Q <= kStreamNQ)
-      hipLaunchKernelGGL((upols_mac_adj_stream_kernel<kStreamNB, kStreamNQ, kStreamPF>),
-                         dim3(kN / kNT, (unsigned)npairs), dim3(kNT), 0, S(stream), GZ,
-                         reinterpret_cast<const float2*>(spectrum), (int)nb, (int)Q, V);
-    else
-      hipLaunchKernelGGL((upols_mac_adj_ring_kernel<AB, kRingPF, kRingGR>),
-                         dim3(kN / kNT, (unsigned)((nb + AB - 1) / AB), (unsigned)npairs), dim3(kNT), 0, S(stream), GZ,
-                         reinterpret_cast<const float2*>(spectrum), (int)nb, (int)Q, V);
-    if ((st = launch_status())) return st;
+    if ((st = launch_mac<MacAdjoint>(GZ, spectrum, 0, nb, Q, npairs, V, stream))) return st;
     hipLaunchKernelGGL(upols_inverse_kernel, dim3((unsigned)nb, (unsigned)npairs), dim3(kNT), 0, S(stream), V,
                        (int)nb, n, (int)rows, 1, 0, dx, n);
     if ((st = launch_status())) return st;

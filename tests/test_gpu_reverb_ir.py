@@ -1,6 +1,8 @@
 """The fused IR rebuild (ddsp_hip_reverb_impulse_spectrum: modules.py:21-26's build_impulse and the
 partition spectra of modules.py:30-35 in one launch) equals the two-launch form bit for bit, for crop
-and pad cases and non-default wet/decay; the module's uncached forward matches golden g4."""
+and pad cases and non-default wet/decay; the module's uncached forward matches golden g4.  The kernels that
+form the impulse's tap (three) and its gradient (two) call one definition (csrc/impulse.h): the tap's three
+spectra and the fused against the unfused gradient are held to each other bit for bit."""
 import numpy as np
 import pytest
 import torch
@@ -26,6 +28,56 @@ def test_impulse_spectrum_bitexact(dd, L, T, wet, decay):
         two = dd.core.reverb_spectrum(rv.build_impulse(), T)
         one = dd.core.reverb_impulse_spectrum(rv.noise, rv.decay, rv.wet, 48000, T)
     assert torch.equal(one, two)
+
+
+@pytest.mark.parametrize("L,T", [(5000, 6000), (5000, 3000)])
+def test_three_forward_taps_agree(dd, L, T):
+    """Reverb.build_impulse's tap is formed in three kernels (build_impulse_kernel, the one-launch
+    impulse spectrum, the device cache's window rebuild): their spectra are one, bit for bit, at an IR of
+    three partitions that the signal covers and at one it crops."""
+    torch.manual_seed(1)
+    rv = dd.Reverb(L, 48000, initial_wet=0.3, initial_decay=3.0).cuda()
+    x = torch.randn(3, T, 1, device="cuda")
+    with torch.no_grad():
+        two = dd.core.reverb_spectrum(rv.build_impulse(), T)
+        one = dd.core.reverb_impulse_spectrum(rv.noise, rv.decay, rv.wet, 48000, T)
+        rv(x)  # a fresh device cache, one ddsp_hip_reverb_forward
+        cached = rv._spectrum(T)
+    assert torch.equal(one, two)
+    assert torch.equal(cached, two)
+
+
+GRAD_REL = 1e-5  # the project's gradient bound (tests/test_gpu_grad.py)
+
+
+# (3, 6000, 5000): an odd row count (the last pair has one row), three blocks, four kernel windows, L no
+# multiple of the partition; (2, 3000, 5000): the IR cropped by the signal (kc = 3000 < L) and L past the
+# partitions — the fused kernel's zero-fill tail loop against the unfused one's grad_len guard
+@pytest.mark.parametrize("B,T,L", [(3, 6000, 5000), (2, 3000, 5000)])
+def test_fused_impulse_gradient_is_the_unfused_one(dd, B, T, L):
+    """grad.reverb_backward_params (the tap's gradient inside upols_corr_finish_impulse_kernel) against
+    grad.reverb_backward(want_dimp) + grad.impulse_backward from the same g, input spectra and parameters:
+    d_noise bit for bit; d_decay and d_wet, fp64 sums of the same fp32 terms grouped differently, within
+    GRAD_REL."""
+    from ddsp_pytorch_amd import core, grad
+    gen = torch.Generator().manual_seed(B * T + L)
+    x = (torch.randn(B, T, 1, generator=gen) * 0.3).cuda()
+    g = torch.randn(B, T, 1, generator=gen).cuda()
+    torch.manual_seed(1)
+    rv = dd.Reverb(L, 48000, initial_wet=0.3, initial_decay=4.0).cuda()
+    noise, decay, wet = (p.detach() for p in (rv.noise, rv.decay, rv.wet))
+    with torch.no_grad():
+        spec = core.reverb_impulse_spectrum(noise, decay, wet, 48000, T)
+        _, ws = core._reverb_apply_launch(x, spec, L)  # its head: the input spectra
+    dx_f, dn_f, dd_f, dw_f = grad.reverb_backward_params(ws, spec, g, noise, decay, wet, L, 48000, True)
+    dx_u, dimp = grad.reverb_backward(None, ws, spec, g, L, True, True)
+    dn_u, dd_u, dw_u = grad.impulse_backward(noise, decay, wet, dimp, min(L, T), 48000)
+    assert torch.equal(dx_f, dx_u)
+    assert float(dn_u.abs().max()) > 0 and torch.equal(dn_f, dn_u)
+    for name, a, b in (("decay", dd_f, dd_u), ("wet", dw_f, dw_u)):
+        a, b = float(a), float(b)
+        print(name, a, b, abs(a - b) / abs(b))
+        assert b != 0.0 and abs(a - b) / abs(b) < GRAD_REL, (name, a, b)
 
 
 @pytest.mark.parametrize("tag", ["small", "1s", "crop", "wet"])

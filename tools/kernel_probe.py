@@ -1,6 +1,10 @@
 """Run one kernel of the synthesis path repeatedly at configuration 2 (for rocprofv3 PMC passes).
 
-    python tools/kernel_probe.py {fused,bwd,reverb_bwd,gru,gru_train,harmonic,harmonic_frames,noise,reverb,op} [reps]
+    python tools/kernel_probe.py {fused,bwd,reverb_bwd,reverb_ir,gru,gru_train,harmonic,harmonic_frames,noise,reverb,op}
+                                 [reps] [frames]
+
+frames (default 200, configuration 2's): another signal length, e.g. 250 for the reverb's ring MAC kernels
+(200 frames are the 50 blocks of the whole-row MAC form).
 """
 import os
 import sys
@@ -17,6 +21,8 @@ def main():
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
     dev = torch.device("cuda", 0)
     B, F, H, NB, bs, sr = 64, 200, 100, 65, 512, 48000
+    if len(sys.argv) > 3:
+        F = int(sys.argv[3])
     inp = make_inputs(B, F, H, NB, bs, seed=0, device=dev, with_noise=False)
     syn = SynthPath(bs, sr, reverb_length=48000).to(dev)
     if which == "bwd":  # the fused synthesis backward (frame_backward_kernel<2, 2, true>)
@@ -64,6 +70,18 @@ def main():
         g = torch.randn(B, F * bs, 1, device=dev)
         for _ in range(reps):  # forward each time: the backward releases the kept input spectra
             syn.reverb(x).backward(g)
+        torch.cuda.synchronize()
+        return
+    if which == "reverb_ir":  # the IR's cold kernels: build_impulse, both spectrum kernels, the unfused impulse backward
+        from ddsp_pytorch_amd import grad
+        rv = syn.reverb
+        noise, decay, wet = (p.detach() for p in (rv.noise, rv.decay, rv.wet))
+        dimp = torch.randn(rv.length, device=dev)
+        with torch.no_grad():
+            for _ in range(reps):
+                core.reverb_spectrum(rv.build_impulse(), F * bs)
+                core.reverb_impulse_spectrum(noise, decay, wet, sr, F * bs)
+                grad.impulse_backward(noise, decay, wet, dimp, rv.length, sr)
         torch.cuda.synchronize()
         return
     with torch.no_grad():

@@ -14,6 +14,7 @@ correction is applied only where that access shape holds (listed in WIDE_READS).
 import csv
 import json
 import os
+import re
 import shutil
 import sys
 from collections import defaultdict
@@ -41,7 +42,8 @@ REPORT = {  # bench.py roofline key -> kernels whose bytes add up to one launch 
 def short(name):
     """kernel name with its template arguments, without namespace, return type and parameters"""
     base = name.replace("(anonymous namespace)", "anon").split("(")[0]
-    return base.replace("void ", "").split("::")[-1]
+    # every qualifier goes, those inside the template arguments too (upols_mac_ring_kernel<ddsp::anon::MacForward, ...>)
+    return re.sub(r"\w+::", "", base.replace("void ", ""))
 
 
 def base(name):

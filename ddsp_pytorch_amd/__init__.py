@@ -10,6 +10,9 @@ Drop-in for hugofloresgarcia/ddsp_pytorch's synthesis hot path:
 * analysis — ``core.extract_loudness``, ``core.mfcc`` and ``features.analyze``: the loudness and MFCC
   features the models consume, from raw audio on the device (ddsp/core.py:81-97, ddsp/preprocess.py:28-32);
   ``features.StreamAnalyzer`` / ``core.stream_loudness`` / ``core.stream_mfcc``: the same per call of a stream;
+  ``core.extract_pitch`` / ``core.stream_pitch``: f0 from the audio by the YIN estimator (the reference's
+  ``extract_pitch`` is the CREPE network, which this package does not carry), so ``analyze(signal, None, ...)``
+  runs from audio alone;
 * ``DDSPDecoder`` and ``DDSPAutoencoder`` — the reference's two models (same state_dicts) running
   on these kernels.
 

@@ -29,6 +29,7 @@ __all__ = [
     "harmonic_synth_frames", "harmonic_synth_params", "synth_frames", "synth_signal", "filtered_noise", "reverb_build_impulse", "reverb_spectrum_floats",
     "reverb_spectrum", "reverb_impulse_spectrum", "reverb_apply", "reverb_forward", "reverb_cache_bytes", "set_noise_seed", "safe_log", "stft_magnitude", "multiscale_fft",
     "extract_loudness", "mfcc", "FeatureStreamState", "stream_loudness", "stream_mfcc", "stream_feature_delay",
+    "extract_pitch", "stream_pitch", "pitch_lags",
 ]
 
 
@@ -992,6 +993,52 @@ def extract_loudness(signal, sample_rate, block_size, n_fft=2048):
     return out[0] if one_d else out
 
 
+def pitch_lags(sample_rate, fmin, fmax, frame_length):
+    """(tau_min, tau_max) of include/ddsp_hip.h ("pitch"): the lag range in samples for a frequency range, in
+    double precision, once: max(floor(sr / fmax), 1) and min(ceil(sr / fmin), L - W - 1), W = L / 2."""
+    sr, L = float(sample_rate), int(frame_length)
+    if not (sr > 0.0 and float(fmin) > 0.0 and float(fmax) > 0.0):
+        raise RuntimeError(f"pitch: sample_rate, fmin and fmax must be positive, got {sample_rate}, {fmin}, {fmax}")
+    tau_min = max(int(math.floor(sr / float(fmax))), 1)
+    tau_max = min(int(math.ceil(sr / float(fmin))), L - L // 2 - 1)
+    if tau_min > tau_max:
+        raise RuntimeError(f"pitch: no lag lies in [{fmin}, {fmax}] Hz at sample_rate {sample_rate} with "
+                           f"frame_length {L} (lags {tau_min} .. {tau_max})")
+    return tau_min, tau_max
+
+
+def _pitch_outputs(B, F, device, return_confidence, return_period):
+    f0 = torch.empty(B, F, dtype=torch.float32, device=device)
+    conf = torch.empty(B, F, dtype=torch.float32, device=device) if return_confidence else None
+    period = torch.empty(B, F, dtype=torch.int32, device=device) if return_period else None
+    return f0, conf, period
+
+
+def _pitch_result(f0, conf, period, one_d):
+    out = tuple(t[0] if one_d else t for t in (f0, conf, period) if t is not None)
+    return out[0] if len(out) == 1 else out
+
+
+def extract_pitch(signal, sample_rate, block_size, fmin=50.0, fmax=2000.0, frame_length=2048, threshold=0.1,
+                  return_confidence=False, return_period=False):
+    """f0 from raw audio on the device: signal [T] or [B, T] (HIP, fp32) -> f0 in Hz, [T // block_size] or
+    [B, T // block_size], by the YIN estimator of include/ddsp_hip.h ("pitch": frames of ``frame_length`` samples
+    centred at f * block_size with reflect padding, the loudness's frames; the fp64 difference function through
+    the FFT, cumulative-mean normalisation, the first dip under ``threshold``, parabolic refinement).  One launch,
+    no host synchronisation.  This is NOT the reference's ``extract_pitch`` (ddsp/core.py:100-119: the CREPE
+    network on host numpy), whose weights are not part of this package; it stands where that stood so that
+    ``features.analyze`` can run from audio alone.  ``return_confidence``: also 1 - d'(tau*) in [0, 1] (what a
+    caller thresholds for voicing); ``return_period``: also the integer lag tau* (int32).  No autograd."""
+    x, one_d = _signal_rows(signal, block_size, "extract_pitch")
+    L = int(frame_length)
+    tau_min, tau_max = pitch_lags(sample_rate, fmin, fmax, L)
+    B, T = x.shape
+    f0, conf, period = _pitch_outputs(B, T // int(block_size), x.device, return_confidence, return_period)
+    _lib.call("pitch", _lib.ptr(x), _lib.ptr(f0), _lib.ptr(conf), _lib.ptr(period), B, T, L, int(block_size),
+              tau_min, tau_max, float(sample_rate), float(threshold), _lib.stream_of(x))
+    return _pitch_result(f0, conf, period, one_d)
+
+
 def mfcc_tables(sample_rate, n_mfcc, n_fft, n_mels, fmin, fmax, device):
     """(band_start, band_count, band_weights, dct) of ``mfcc`` on ``device``, cached per parameters."""
     params = (float(sample_rate), int(n_mfcc), int(n_fft), int(n_mels), float(fmin), float(fmax))
@@ -1152,9 +1199,9 @@ def stream_advance(state, f0=None, block_size=1, sample_rate=1.0, wrap=True):
 
 
 # ------------------------------------------------------------------------------------
-# streaming analysis (ddsp_hip_stream_loudness / ddsp_hip_stream_mfcc): the features of a stream call by
-# call, the history a window needs carried on the device.  With d = ceil((n_fft / 2) / hop), call k of N = R hop
-# samples emits the frames f = k R - d + 1 + j, j < R, of the stream (frame f: the n_fft samples from
+# streaming analysis (ddsp_hip_stream_loudness / ddsp_hip_stream_mfcc / ddsp_hip_stream_pitch): the features of a
+# stream call by call, the history a window needs carried on the device.  With d = ceil((n_fft / 2) / hop), call k
+# of N = R hop samples emits the frames f = k R - d + 1 + j, j < R, of the stream (frame f: the n_fft samples from
 # f hop - n_fft / 2, zeros before the stream's start — no reflect padding), i.e. the features lag the offline
 # alignment by d - 1 frames.
 # ------------------------------------------------------------------------------------
@@ -1165,7 +1212,7 @@ def stream_feature_delay(n_fft, hop):
 
 
 class FeatureStreamState:
-    """The device state of one streamed feature (loudness or MFCC): ``buf`` (uint8,
+    """The device state of one streamed feature (loudness, MFCC or pitch): ``buf`` (uint8,
     ddsp_hip_stream_features_state_bytes: per item a ring of the carried samples plus one call, then the
     MFCC's running maximum per item) and ``counter`` (int64[1], the call index).  Zero-filled is a fresh
     stream.  ``counter``: another state's counter tensor to share (a ``StreamState``'s, so that one
@@ -1242,6 +1289,23 @@ def stream_mfcc(x, sample_rate, block_size, state, n_mfcc=30, n_fft=1024, n_mels
               state.buf.numel(), B, N, int(n_fft), int(block_size), int(n_mels), int(n_mfcc), float(top_db),
               _lib.stream_of(xc))
     return out
+
+
+def stream_pitch(x, sample_rate, block_size, state, fmin=50.0, fmax=2000.0, frame_length=2048, threshold=0.1,
+                 return_confidence=False, return_period=False):
+    """``extract_pitch`` for one call of a stream: x [B, N] or [B, N, 1] -> f0 [B, N // block_size] (and the
+    confidence, the period) of the frames the call completes, the stream's own frames (zeros before its start;
+    delayed by ``state.delay_frames``).  ``state``: a ``FeatureStreamState(B, device, N, frame_length, block_size)``
+    of its own; the call reads its counter and writes its ring, ``stream_advance`` ends the call.  One launch."""
+    L = int(frame_length)
+    xc = _stream_call_rows(x, state, block_size, L, "stream_pitch")
+    tau_min, tau_max = pitch_lags(sample_rate, fmin, fmax, L)
+    B, N = xc.shape
+    f0, conf, period = _pitch_outputs(B, state.frames, xc.device, return_confidence, return_period)
+    _lib.call("stream_pitch", _lib.ptr(xc), _lib.ptr(f0), _lib.ptr(conf), _lib.ptr(period), _lib.ptr(state.counter),
+              _lib.ptr(state.buf), state.buf.numel(), B, N, L, int(block_size), tau_min, tau_max, float(sample_rate),
+              float(threshold), _lib.stream_of(xc))
+    return _pitch_result(f0, conf, period, False)
 
 
 from . import grad as _grad  # noqa: E402  (autograd Functions over the backward kernels)

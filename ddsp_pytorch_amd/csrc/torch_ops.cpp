@@ -501,6 +501,42 @@ at::Tensor mfcc_stream(const at::Tensor& x, const at::Tensor& band_start, const 
   return out;
 }
 
+// ---------------- pitch: YIN f0 (ddsp_hip_pitch / ddsp_hip_stream_pitch) -> (f0, confidence, period) ----------------
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch(const at::Tensor& x, int64_t frame_length, int64_t hop,
+                                                     int64_t tau_min, int64_t tau_max, double sample_rate,
+                                                     double threshold) {
+  at::Tensor xc = audio_rows(x, "pitch");
+  TORCH_CHECK(hop >= 1, "pitch: hop must be positive");
+  const int64_t B = xc.size(0), T = xc.size(1);
+  at::Tensor f0 = at::empty({B, T / hop}, xc.options());
+  at::Tensor conf = at::empty_like(f0);
+  at::Tensor period = at::empty({B, T / hop}, xc.options().dtype(at::kInt));
+  ok(ddsp_hip_pitch(xc.data_ptr<float>(), f0.data_ptr<float>(), conf.data_ptr<float>(), period.data_ptr<int32_t>(), B,
+                    T, frame_length, hop, tau_min, tau_max, (float)sample_rate, (float)threshold, stream_of(xc)),
+     "pitch");
+  if (x.dim() == 1) return {f0.select(0, 0), conf.select(0, 0), period.select(0, 0)};
+  return {f0, conf, period};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_stream(const at::Tensor& x, int64_t frame_length, int64_t hop,
+                                                            int64_t tau_min, int64_t tau_max, double sample_rate,
+                                                            double threshold, const at::Tensor& counter,
+                                                            at::Tensor& state) {
+  at::Tensor xc = call_rows(x, "pitch_stream");
+  check_stream(counter, state, xc);
+  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "pitch_stream: call_samples must be a multiple of hop");
+  const int64_t B = xc.size(0), N = xc.size(1);
+  at::Tensor f0 = at::empty({B, N / hop}, xc.options());
+  at::Tensor conf = at::empty_like(f0);
+  at::Tensor period = at::empty({B, N / hop}, xc.options().dtype(at::kInt));
+  ok(ddsp_hip_stream_pitch(xc.data_ptr<float>(), f0.data_ptr<float>(), conf.data_ptr<float>(),
+                           period.data_ptr<int32_t>(), reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()),
+                           state.data_ptr(), (size_t)state.numel(), B, N, frame_length, hop, tau_min, tau_max,
+                           (float)sample_rate, (float)threshold, stream_of(xc)),
+     "stream_pitch");
+  return {f0, conf, period};
+}
+
 }  // namespace
 
 // ---------------- decoder.py:33-68: the GRU recurrence ----------------
@@ -562,6 +598,10 @@ TORCH_LIBRARY(ddsp_hip, m) {
   m.def("loudness_stream(Tensor x, Tensor? weights, int n_fft, int hop, Tensor counter, Tensor(a!) state) -> Tensor");
   m.def("mfcc_stream(Tensor x, Tensor band_start, Tensor band_count, Tensor band_weights, Tensor dct, int n_fft,"
         " int hop, float top_db, Tensor counter, Tensor(a!) state) -> Tensor");
+  m.def("pitch(Tensor x, int frame_length, int hop, int tau_min, int tau_max, float sample_rate, float threshold)"
+        " -> (Tensor, Tensor, Tensor)");
+  m.def("pitch_stream(Tensor x, int frame_length, int hop, int tau_min, int tau_max, float sample_rate,"
+        " float threshold, Tensor counter, Tensor(a!) state) -> (Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA key on ROCm
@@ -589,4 +629,6 @@ TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA 
   m.impl("mfcc", &mfcc);
   m.impl("loudness_stream", &loudness_stream);
   m.impl("mfcc_stream", &mfcc_stream);
+  m.impl("pitch", &pitch);
+  m.impl("pitch_stream", &pitch_stream);
 }

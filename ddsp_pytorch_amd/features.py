@@ -3,11 +3,14 @@
 The reference computes ``batch['loudness']`` and ``batch['mfcc']`` on the host, file by file, with librosa
 (``ddsp/core.py:81-97``, ``ddsp/preprocess.py:28-32``) and stores them; ``ddsp/data.py:22-32`` hands them to the
 model as [frames, 1], [frames, 1] and [frames, 30].  ``analyze`` produces the same dict from audio that is
-already on the HIP device (``core.extract_loudness``, ``core.mfcc``: csrc/features.hip).  Pitch (the reference's
-CREPE network, ``extract_pitch``) is not computed here: ``f0`` stays an input.
+already on the HIP device (``core.extract_loudness``, ``core.mfcc``: csrc/features.hip).  The reference's pitch
+is the CREPE network (``extract_pitch``), whose weights are not part of this package: a pitch track from elsewhere
+can be passed in as before, and without one ``analyze`` computes f0 on the device with the YIN estimator
+(``core.extract_pitch``: csrc/pitch.hip) — a classical tracker, not CREPE.
 
 ``StreamAnalyzer`` is the same front end for a realtime stream: audio comes in call by call and each call returns
-the frames it completes (``core.stream_loudness``, ``core.stream_mfcc``), the history carried on the device.
+the frames it completes (``core.stream_loudness``, ``core.stream_mfcc`` and, on request, ``core.stream_pitch``),
+the history carried on the device.
 """
 import torch
 
@@ -16,12 +19,17 @@ from . import core
 __all__ = ["analyze", "StreamAnalyzer"]
 
 
-def analyze(signal, pitch, sample_rate, block_size, mean_loudness=None, std_loudness=None):
+def analyze(signal, pitch=None, sample_rate=None, block_size=None, mean_loudness=None, std_loudness=None, fmin=50.0,
+            fmax=2000.0):
     """signal [T] or [B, T] (HIP, fp32) and pitch (F = T // block_size values per item, [B, F] or [B, F, 1]) ->
     ``{'pitch': [B, F, 1], 'loudness': [B, F, 1], 'mfcc': [B, F, 30]}``, the shapes of ``ddsp/data.py:22-32``
     (the MFCC's last frame is dropped there, ``data.py:25``; the loudness's inside ``extract_loudness``).
-    With ``mean_loudness`` and ``std_loudness`` the loudness is normalised as ``train.py:87`` does,
-    ``(l - mean) / std``.  No autograd, no host synchronisation after the first call (see ``core.mfcc``)."""
+    ``pitch=None``: f0 is computed from the audio (``core.extract_pitch`` over ``fmin`` .. ``fmax`` Hz, YIN).
+    ``sample_rate`` and ``block_size`` are required.  With ``mean_loudness`` and ``std_loudness`` the loudness is
+    normalised as ``train.py:87`` does, ``(l - mean) / std``.  No autograd, no host synchronisation after the first
+    call (see ``core.mfcc``)."""
+    if sample_rate is None or block_size is None:
+        raise TypeError("analyze: sample_rate and block_size are required")
     if (mean_loudness is None) != (std_loudness is None):
         raise ValueError("analyze: mean_loudness and std_loudness go together")
     x = signal.unsqueeze(0) if signal.dim() == 1 else signal
@@ -30,6 +38,8 @@ def analyze(signal, pitch, sample_rate, block_size, mean_loudness=None, std_loud
     if mean_loudness is not None:
         loudness = (loudness - mean_loudness) / std_loudness
     mfcc = core.mfcc(x, sample_rate, block_size)[:, :F]
+    if pitch is None:
+        pitch = core.extract_pitch(x, sample_rate, block_size, fmin=fmin, fmax=fmax)
     pitch = torch.as_tensor(pitch, dtype=torch.float32, device=x.device)
     if pitch.numel() != B * F:
         raise RuntimeError(f"analyze: pitch must hold {B} x {F} values (T // block_size per item), got "
@@ -41,18 +51,21 @@ class StreamAnalyzer:
     """Loudness and MFCC of a stream, call by call: ``analyzer(audio)`` takes the stream's next ``call_samples``
     samples, audio [B, N] or [B, N, 1] on the device, and returns ``{'loudness': [B, R, 1], 'mfcc': [B, R, 30]}``
     for the R = N // block_size frames the call completes, then advances the stream (one launch per feature and one
-    for the advance).  The frames are the stream's own (zeros before its start, no reflect padding); call k holds
-    frames ``k R + first_frame[name] + j`` of the offline alignment (frame f centred at sample f * block_size), so
-    each feature lags by ``delay_frames[name]`` frames (loudness: n_fft 2048, MFCC: n_fft 1024 as in
-    ``analyze``).  The MFCC's top_db clamp is causal (``core.stream_mfcc``).  ``mean_loudness`` / ``std_loudness``
-    as in ``analyze``.  After one warm-up call (the tables) nothing synchronises with the host: a call can be
-    captured in a HIP graph over a static input buffer.  ``counter``: a stream counter to share (e.g. a
-    ``core.StreamState``'s), with ``advance=False`` when that stream's own advance ends the call."""
+    for the advance).  ``pitch=True`` adds ``'pitch'`` and ``'confidence'`` ([B, R, 1] each: ``core.stream_pitch``
+    over ``fmin`` .. ``fmax`` Hz with frames of 2048 samples, a third state on the shared counter).  The frames are
+    the stream's own (zeros before its start, no reflect padding); call k holds frames
+    ``k R + first_frame[name] + j`` of the offline alignment (frame f centred at sample f * block_size), so each
+    feature lags by ``delay_frames[name]`` frames (loudness: n_fft 2048, MFCC: n_fft 1024 as in ``analyze``; pitch:
+    2048, so it lags exactly as the loudness does).  The MFCC's top_db clamp is causal (``core.stream_mfcc``).
+    ``mean_loudness`` / ``std_loudness`` as in ``analyze``.  After one warm-up call (the tables) nothing
+    synchronises with the host: a call can be captured in a HIP graph over a static input buffer.  ``counter``: a
+    stream counter to share (e.g. a ``core.StreamState``'s), with ``advance=False`` when that stream's own advance
+    ends the call."""
 
-    N_FFT = {"loudness": 2048, "mfcc": 1024}
+    N_FFT = {"loudness": 2048, "mfcc": 1024, "pitch": 2048}
 
     def __init__(self, sample_rate, block_size, call_samples, batch=1, device="cuda", mean_loudness=None,
-                 std_loudness=None, counter=None, advance=True):
+                 std_loudness=None, counter=None, advance=True, pitch=False, fmin=50.0, fmax=2000.0):
         if (mean_loudness is None) != (std_loudness is None):
             raise ValueError("StreamAnalyzer: mean_loudness and std_loudness go together")
         self.sample_rate, self.block_size, self.call_samples = float(sample_rate), int(block_size), int(call_samples)
@@ -64,11 +77,20 @@ class StreamAnalyzer:
         self.mfcc_state = core.FeatureStreamState(batch, device, call_samples, self.N_FFT["mfcc"], block_size,
                                                   counter=self.counter)
         self.delay_frames = {"loudness": self.loudness_state.delay_frames, "mfcc": self.mfcc_state.delay_frames}
+        self.pitch, self.fmin, self.fmax = bool(pitch), float(fmin), float(fmax)
+        self.pitch_state = None
+        if self.pitch:
+            core.pitch_lags(sample_rate, fmin, fmax, self.N_FFT["pitch"])  # a bad range is refused here
+            self.pitch_state = core.FeatureStreamState(batch, device, call_samples, self.N_FFT["pitch"], block_size,
+                                                       counter=self.counter)
+            self.delay_frames["pitch"] = self.pitch_state.delay_frames
         self.first_frame = {k: -v for k, v in self.delay_frames.items()}
 
     def reset(self):
         self.loudness_state.reset()
         self.mfcc_state.reset()
+        if self.pitch_state is not None:
+            self.pitch_state.reset()
 
     @torch.no_grad()
     def __call__(self, audio):
@@ -77,6 +99,11 @@ class StreamAnalyzer:
         if self.mean_loudness is not None:
             loudness = (loudness - self.mean_loudness) / self.std_loudness
         mfcc = core.stream_mfcc(audio, self.sample_rate, self.block_size, self.mfcc_state, n_fft=self.N_FFT["mfcc"])
+        out = {"loudness": loudness.unsqueeze(-1), "mfcc": mfcc}
+        if self.pitch:
+            f0, conf = core.stream_pitch(audio, self.sample_rate, self.block_size, self.pitch_state, fmin=self.fmin,
+                                         fmax=self.fmax, frame_length=self.N_FFT["pitch"], return_confidence=True)
+            out["pitch"], out["confidence"] = f0.unsqueeze(-1), conf.unsqueeze(-1)
         if self.advance:
             core.stream_advance(self.loudness_state)
-        return {"loudness": loudness.unsqueeze(-1), "mfcc": mfcc}
+        return out

@@ -4,7 +4,9 @@ Function level: ``ddsp/__init__.py:1`` re-exports ``ddsp.core`` and the synth mo
 ``ddsp.<fn>`` at call time (modules.py:33,53-56,74-78,113,117,125), so rebinding the six
 package attributes redirects every caller.  Module level: the reference classes'
 forwards are replaced by the fused ones (same instance attributes and parameters).
-``uninstall()`` restores everything.
+``uninstall()`` restores everything.  The analysis functions are not rebound: the reference's
+``extract_loudness`` and ``extract_pitch`` (the CREPE network) take and return host numpy, and
+``core.extract_pitch`` is a different estimator (YIN), not a faster CREPE.
 """
 from . import core, decoder, encoder, modules
 

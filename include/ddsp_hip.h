@@ -660,6 +660,58 @@ int ddsp_hip_stream_mfcc(const float* x, const int32_t* band_start, const int32_
                          int64_t call_samples, int64_t n_fft, int64_t hop, int64_t n_mels, int64_t n_mfcc, float top_db,
                          void* stream);
 
+/* ---------------- pitch: YIN f0 from raw audio, offline and per call of a stream ----------------
+ * The reference's extract_pitch (ddsp/core.py:100-119) is the CREPE network; this is not it but the classical YIN
+ * estimator (de Cheveigne & Kawahara, JASA 2002), so that the third input of the models can come from audio too.
+ *
+ * Parameters.  frame_length L, a power of two in [64, 4096]; W = L/2; hop; sample_rate sr; threshold (0.1 is usual);
+ * the lag range tau_min .. tau_max in samples, which the caller derives from its frequency range once, in double
+ * precision: tau_min = max(floor(sr / fmax), 1), tau_max = min(ceil(sr / fmin), L - W - 1).  The entry points take
+ * the integers, so that caller and kernel cannot disagree about a rounding; 1 <= tau_min <= tau_max <= W - 1.
+ *
+ * Frames, no window applied.  Offline, frame f is y[i] = x[reflect(f * hop - L/2 + i)], i < L, for
+ * f = 0 .. n_samples/hop - 1: ddsp_hip_loudness's frames.  Streamed, the frames of "streaming analysis" above with
+ * n_fft := L: frame f starts at f * hop - L/2, samples before the stream are zero, call k emits f = k R - d + 1 + j.
+ *
+ * Per frame, for tau = 0 .. tau_max + 1, in fp64 on the fp32 samples:
+ *   1. E(tau) = sum_{j<W} y[j + tau]^2
+ *   2. r(tau) = sum_{j<W} y[j] y[j + tau]
+ *   3. d(tau) = E(0) + E(tau) - 2 r(tau)
+ *   4. d(tau) := 0 wherever d(tau) < 2^-40 (E(0) + E(tau)): silent, onset and exactly periodic frames come out the
+ *      same whether r is a direct sum (exactly 0 or exactly cancelling there) or taken through a transform
+ *      (~1e-16 E); 2^-40 is far below what an fp32 input with audible content produces and far above the fp64
+ *      transform's error.  (r(tau) is exactly 0 where y[0..W) or y[tau..tau+W) is all zeros; the kernels return
+ *      exactly that.)
+ *   5. d'(0) = 1; with S(tau) = sum_{k=1..tau} d(k), d'(tau) = d(tau) tau / S(tau) if S(tau) > 0, else 1
+ *   6. candidates: tau in [tau_min, tau_max] with d'(tau) < d'(tau-1) and d'(tau) <= d'(tau+1).  tau* = the smallest
+ *      candidate with d' < threshold; if there is none, the smallest tau in [tau_min, tau_max] attaining the minimum
+ *      of d' over that range
+ *   7. with a = d'(tau*-1), b = d'(tau*), c = d'(tau*+1): if b <= a, b <= c and a - 2b + c > 0 the shift is
+ *      s = (a - c) / (2 (a - 2b + c)), otherwise s = 0
+ *   8. f0 = sr / (tau* + s), confidence = 1 - min(1, b - (a - c) s / 4), period = tau*.
+ * An all-zero frame therefore gives period tau_min, f0 = sr / tau_min and confidence 0, never a NaN.  The threshold
+ * is the fp32 value passed, widened.  Outputs: f0 and confidence fp32, period int32, each [batch, frames]; confidence
+ * and period may be NULL.  r goes through the fp64 transform of features (d cancels to zero at the pitch), E and S
+ * through fp64 scans, tau* through fixed-order reductions: no atomics, bit-reproducible, independent of the batch
+ * around an item.  One launch.
+ * Checked before any HIP call: null x / f0 (streamed: counter, state too), sizes < 1, tau bounds, sr <= 0 (NaN
+ * included), frame_length/2 >= n_samples (reflect padding, as ddsp_hip_loudness): DDSP_HIP_EINVAL; frame_length not
+ * a power of two in [64, 4096], batch > 65535 and the streaming envelope's caps: DDSP_HIP_ERANGE; a short state:
+ * DDSP_HIP_EWORKSPACE; batch == 0: a no-op success. */
+int ddsp_hip_pitch(const float* x, float* f0, float* confidence, int32_t* period, int64_t batch, int64_t n_samples,
+                   int64_t frame_length, int64_t hop, int64_t tau_min, int64_t tau_max, float sample_rate,
+                   float threshold, void* stream);
+
+/* The same per call of a stream: x [batch, call_samples], outputs [batch, R].  State: a buffer of
+ * ddsp_hip_stream_features_state_bytes(batch, call_samples, frame_length, hop) bytes of its own, zero-filled for a
+ * fresh stream (the trailing float per item is unused); the counter is read and never written, and may be shared
+ * with the other features and with a synthesis stream.  The call copies x into the ring under the argument given
+ * above, so a call run twice before the advance gives the same bits. */
+int ddsp_hip_stream_pitch(const float* x, float* f0, float* confidence, int32_t* period, const uint64_t* counter,
+                          void* state, size_t state_bytes, int64_t batch, int64_t call_samples, int64_t frame_length,
+                          int64_t hop, int64_t tau_min, int64_t tau_max, float sample_rate, float threshold,
+                          void* stream);
+
 /* Two-stage serving pipeline (ddsp_pytorch_amd.synth.PipelinedSynthPath; no reference counterpart:
  * the reference synthesises one batch at a time, decoder.py:101-136).  A HIP stream restricted to
  * the CUs whose bits are set in cu_mask (mask_words 32-bit words, bit c = CU index c; HIP deals

@@ -11,6 +11,11 @@ JSON line per (shape, leg); DESIGN.md 3f records a run.  Needs a HIP device: the
 item, calls of 1024 samples, block 256, 48 kHz), each leg captured in a HIP graph and replayed: the stream
 kernels, beside the route open without them — the offline kernels over a rolling window of Hs + N samples (the
 history a call's frames need plus the call), the window's shift included.  DESIGN.md 3g records a run.
+
+``--leg pitch`` times the pitch tracker (core.extract_pitch: csrc/pitch.hip) at the two offline shapes beside the
+same definition (include/ddsp_hip.h, "pitch") composed from torch.fft and ATen ops in fp64 — what a user would
+write today; the package had no pitch path before — and core.stream_pitch at the realtime shape, captured in a HIP
+graph.  DESIGN.md 3f-pitch records a run.
 """
 import argparse
 import json
@@ -41,6 +46,81 @@ def torch_mfcc(x, fb, dct, n_fft, hop, top_db=80.0):
     D = 10.0 * torch.log10(torch.clamp(fb @ P, min=1e-10))
     D = torch.maximum(D, D.amax(dim=(1, 2), keepdim=True) - top_db)
     return (dct @ D).transpose(1, 2)
+
+
+def torch_pitch(x, sr, hop, L, tau_min, tau_max, threshold=0.1):
+    """include/ddsp_hip.h "pitch" as torch ops in fp64: the frames, their transforms, d, d' and the candidates all
+    go through memory.  -> (f0 [B, F] fp32, period [B, F])."""
+    W, F = L // 2, x.shape[1] // hop
+    xp = torch.nn.functional.pad(x[:, None], (W, W), mode="reflect")[:, 0]
+    Y = xp.unfold(1, L, hop)[:, :F].double()
+    r = torch.fft.irfft(torch.fft.rfft(Y[..., :W], n=L).conj() * torch.fft.rfft(Y, n=L), n=L)[..., :tau_max + 2]
+    c = torch.nn.functional.pad(torch.cumsum(Y * Y, -1), (1, 0))
+    E = c[..., W:W + tau_max + 2] - c[..., :tau_max + 2]
+    tot = E[..., :1] + E
+    d = tot - 2.0 * r
+    d = torch.where(d < 2.0 ** -40 * tot, torch.zeros_like(d), d)
+    d[..., 0] = 0.0
+    S = torch.cumsum(d, -1)
+    tau = torch.arange(tau_max + 2, device=x.device, dtype=torch.float64)
+    dn = torch.where(S > 0, d * tau / torch.where(S > 0, S, torch.ones_like(S)), torch.ones_like(S))
+    dn[..., 0] = 1.0
+    b, a, cn = dn[..., tau_min:tau_max + 1], dn[..., tau_min - 1:tau_max], dn[..., tau_min + 1:tau_max + 2]
+    cand = (b < a) & (b <= cn) & (b < float(torch.tensor(threshold, dtype=torch.float32)))
+    first = (torch.cumsum(cand, -1) == 0).sum(-1)
+    ts = torch.where(cand.any(-1), first, b.argmin(-1)) + tau_min
+    a, b, cn = (dn.gather(-1, (ts + o)[..., None])[..., 0] for o in (-1, 0, 1))
+    curv = a - 2.0 * b + cn
+    ok = (b <= a) & (b <= cn) & (curv > 0)
+    s = torch.where(ok, 0.5 * (a - cn) / torch.where(ok, curv, torch.ones_like(curv)), torch.zeros_like(curv))
+    return (sr / (ts + s)).float(), ts
+
+
+def pitch_leg(dev, reps, windows):
+    L, fmin, fmax = 2048, 50.0, 2000.0
+    for name, B, T, hop, sr in SHAPES:
+        g = torch.Generator().manual_seed(B + T)
+        t = torch.arange(T) / sr
+        f = 110.0 * 2.0 ** (torch.arange(B)[:, None] / 8.0) * (1.0 + 0.005 * torch.sin(2 * torch.pi * 5.5 * t))[None, :]
+        phase = 2 * torch.pi * torch.cumsum(f.double(), 1) / sr
+        x = 0.2 * sum(torch.sin(h * phase) / h for h in range(1, 7)).float() + 0.003 * torch.randn(B, T, generator=g)
+        x = x.to(dev)
+        F = T // hop
+        tau_min, tau_max = core.pitch_lags(sr, fmin, fmax, L)
+        nbytes = 4 * (B * T + 3 * B * F)
+        f_hip, _, p_hip = core.extract_pitch(x, sr, hop, return_confidence=True, return_period=True)
+        f_t, p_t = torch_pitch(x, sr, hop, L, tau_min, tau_max)
+        same = p_hip == p_t
+        rel = float(((f_hip - f_t).abs() / f_t)[same].max())
+        print(json.dumps({"shape": name, "frames": B * F, "periods_that_differ": int((~same).sum()),
+                          "max_rel_diff_f0": rel}), flush=True)
+        legs = [
+            ("pitch hip", lambda: core.extract_pitch(x, sr, hop, return_confidence=True, return_period=True), nbytes),
+            ("pitch torch.fft (fp64)", lambda: torch_pitch(x, sr, hop, L, tau_min, tau_max), None),
+        ]
+        for leg, fn, nb in legs:
+            med, lo, hi = timed(fn, reps if nb is not None else max(reps // 20, 5), windows)
+            row = {"shape": name, "leg": leg, "ms": round(med, 4), "ms_min": round(lo, 4), "ms_max": round(hi, 4)}
+            if nb is not None:
+                row["algorithmic_bytes"] = nb
+                row["GB_per_s"] = round(nb / (med * 1e-3) / 1e9, 1)
+            print(json.dumps(row), flush=True)
+    sr, hop, N = 48000, 256, 1024
+    x = 0.1 * torch.randn(1, N, device=dev)
+    st = core.FeatureStreamState(1, dev, N, L, hop)
+
+    def stream_and_advance():
+        out = core.stream_pitch(x, sr, hop, st, return_confidence=True, return_period=True)
+        core.stream_advance(st)
+        return out
+
+    for leg, fn, launches in (("stream pitch", lambda: core.stream_pitch(x, sr, hop, st, return_confidence=True,
+                                                                       return_period=True), 1),
+                              ("stream pitch + advance", stream_and_advance, 2)):
+        med, lo, hi = timed(graphed(fn), reps, windows)
+        print(json.dumps({"shape": "stream 1x1024 block 256", "leg": leg, "graph_nodes": launches,
+                          "us": round(1e3 * med, 2), "us_min": round(1e3 * lo, 2), "us_max": round(1e3 * hi, 2)}),
+              flush=True)
 
 
 def timed(fn, reps, windows):
@@ -124,11 +204,15 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=1000)
     ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--leg", choices=("offline", "stream", "all"), default="all")
+    ap.add_argument("--leg", choices=("offline", "stream", "pitch", "all"), default="all",
+                    help="all: offline and stream (the pitch leg runs on request)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_features: needs a HIP device (there is no CPU path)")
     dev = torch.device("cuda", 0)
+    if args.leg == "pitch":
+        pitch_leg(dev, args.reps, args.windows)
+        return
     if args.leg in ("stream", "all"):
         stream_leg(dev, args.reps, args.windows)
     if args.leg == "stream":

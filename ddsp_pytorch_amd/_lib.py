@@ -119,6 +119,9 @@ SIGNATURES = {
     # pitch (YIN f0), offline and per call of a stream
     "ddsp_hip_pitch": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _F, _F, _P]),
     "ddsp_hip_stream_pitch": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64, _I64, _I64, _F, _F, _P]),
+    # streamed loudness + pitch of one call in one launch over one state
+    "ddsp_hip_stream_analysis": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64, _I64, _I64, _F, _F,
+                                      _P]),
     # backward
     "ddsp_hip_scale_function_backward": (_I, [_P, _P, _P, _I64, _F, _P]),
     "ddsp_hip_upsample_backward": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P]),

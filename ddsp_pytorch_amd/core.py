@@ -29,7 +29,7 @@ __all__ = [
     "harmonic_synth_frames", "harmonic_synth_params", "synth_frames", "synth_signal", "filtered_noise", "reverb_build_impulse", "reverb_spectrum_floats",
     "reverb_spectrum", "reverb_impulse_spectrum", "reverb_apply", "reverb_forward", "reverb_cache_bytes", "set_noise_seed", "safe_log", "stft_magnitude", "multiscale_fft",
     "extract_loudness", "mfcc", "FeatureStreamState", "stream_loudness", "stream_mfcc", "stream_feature_delay",
-    "extract_pitch", "stream_pitch", "pitch_lags",
+    "extract_pitch", "stream_pitch", "pitch_lags", "stream_analysis",
 ]
 
 
@@ -1203,7 +1203,7 @@ def stream_advance(state, f0=None, block_size=1, sample_rate=1.0, wrap=True):
 # stream call by call, the history a window needs carried on the device.  With d = ceil((n_fft / 2) / hop), call k
 # of N = R hop samples emits the frames f = k R - d + 1 + j, j < R, of the stream (frame f: the n_fft samples from
 # f hop - n_fft / 2, zeros before the stream's start — no reflect padding), i.e. the features lag the offline
-# alignment by d - 1 frames.
+# alignment by d - 1 frames.  ddsp_hip_stream_analysis: the loudness and the pitch of one frame length in one launch.
 # ------------------------------------------------------------------------------------
 def stream_feature_delay(n_fft, hop):
     """d - 1, the frames by which a streamed feature lags the offline alignment (frame f at sample f * hop):
@@ -1306,6 +1306,29 @@ def stream_pitch(x, sample_rate, block_size, state, fmin=50.0, fmax=2000.0, fram
               _lib.ptr(state.buf), state.buf.numel(), B, N, L, int(block_size), tau_min, tau_max, float(sample_rate),
               float(threshold), _lib.stream_of(xc))
     return _pitch_result(f0, conf, period, False)
+
+
+def stream_analysis(x, sample_rate, block_size, state, fmin=50.0, fmax=2000.0, frame_length=2048, threshold=0.1,
+                    return_confidence=False, return_period=False):
+    """``stream_loudness(n_fft=frame_length)`` and ``stream_pitch(frame_length=frame_length)`` of one call in ONE
+    launch over ONE state (ddsp_hip_stream_analysis): x [B, N] or [B, N, 1] -> (loudness [B, R], f0 [B, R]
+    [, confidence] [, period]), R = N // block_size, bit for bit what the two separate calls return (the pitch and
+    the loudness frames run side by side in different workgroups of one grid over one shared ring).  ``state``: a
+    ``FeatureStreamState(B, device, N, frame_length, block_size)``; the call reads its counter and writes its ring,
+    ``stream_advance`` ends the call.  Tables cached as ``stream_loudness``'s, lags as ``pitch_lags``; no host
+    synchronisation after the first call."""
+    L = int(frame_length)
+    xc = _stream_call_rows(x, state, block_size, L, "stream_analysis")
+    tau_min, tau_max = pitch_lags(sample_rate, fmin, fmax, L)
+    (w,) = _feature_tables("a_weighting", (float(sample_rate), L), xc.device,
+                           lambda: (a_weighting_table(sample_rate, L),))
+    B, N = xc.shape
+    loud = torch.empty(B, state.frames, dtype=torch.float32, device=xc.device)
+    f0, conf, period = _pitch_outputs(B, state.frames, xc.device, return_confidence, return_period)
+    _lib.call("stream_analysis", _lib.ptr(xc), _lib.ptr(w), _lib.ptr(loud), _lib.ptr(f0), _lib.ptr(conf),
+              _lib.ptr(period), _lib.ptr(state.counter), _lib.ptr(state.buf), state.buf.numel(), B, N, L,
+              int(block_size), tau_min, tau_max, float(sample_rate), float(threshold), _lib.stream_of(xc))
+    return (loud,) + tuple(t for t in (f0, conf, period) if t is not None)
 
 
 from . import grad as _grad  # noqa: E402  (autograd Functions over the backward kernels)

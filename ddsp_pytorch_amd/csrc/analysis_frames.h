@@ -1,7 +1,7 @@
 // What the analysis kernels share (features.hip: loudness, MFCC; pitch.hip: YIN f0): where a frame's samples come
 // from, offline (reflect padding) and per call of a stream (the carried ring), the call arithmetic of a stream, and
 // the identities by which two real sequences ride one complex fp64 transform.  Written once, so that the features
-// cannot disagree about a frame.
+// cannot disagree about a frame.  (analysis_bodies.h holds what is computed per frame.)
 #pragma once
 
 #include <hip/hip_runtime.h>

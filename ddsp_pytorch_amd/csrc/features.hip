@@ -22,12 +22,14 @@
 //
 // A workgroup transforms kPoints<N> points: 2048 (128 threads, 34 KB of LDS, 2048/N transforms) or, for
 // N = 4096, one transform of 4096 (256 threads, 68 KB: gfx950's LDS is 160 KB per CU).
+// The loudness's reduction over a packed spectrum (loudness_sums) is in analysis_bodies.h, shared with
+// stream_analysis.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 
-#include "analysis_frames.h"
+#include "analysis_bodies.h"
 
 namespace ddsp {
 namespace {
@@ -35,39 +37,6 @@ namespace {
 constexpr int kMaxMels = 256;  // n_mels cap (the band tables live in LDS)
 constexpr int kDctFrames = 8;  // frames per workgroup of the DCT launch
 constexpr int kDctChunk = 32;  // mel columns of the DCT table staged per pass
-
-// Sums of a and b over the Q threads of one transform, valid in its thread t == 0; fixed order.
-// Q < 64: a shuffle tree inside the wave.  Q >= 64: whole waves (group_sum_double2, one barrier — every
-// thread of the workgroup calls this either way).
-template <int Q>
-__device__ __forceinline__ void transform_sum2(double& a, double& b, double* scratch, int tr) {
-  if constexpr (Q >= 64) {
-    group_sum_double2(a, b, scratch, tr * (Q / 64), Q / 64);
-  } else {
-#pragma unroll
-    for (int o = Q / 2; o > 0; o >>= 1) {
-      a += __shfl_down(a, o, Q);
-      b += __shfl_down(b, o, Q);
-    }
-  }
-}
-
-// The two packed frames' sums over the bins of ln(|X[k]| + 1e-7) + w[k] (fp32 log, fp64 sum in a fixed order), valid
-// in the transform's thread t == 0; every thread of the workgroup calls this.
-template <int N>
-__device__ __forceinline__ void loudness_sums(const double2* lds, const float* __restrict__ w, int t, int tr,
-                                              double* red, double& sa, double& sb) {
-  constexpr int Q = N / 16, BINS = N / 2 + 1;
-  sa = 0.0;
-  sb = 0.0;
-  for (int k = t; k < BINS; k += Q) {
-    const double2 p = packed_power<N>(lds, k);
-    const float wk = w ? w[k] : 0.0f;
-    sa += (double)(logf((float)sqrt(p.x) + 1e-7f) + wk);
-    sb += (double)(logf((float)sqrt(p.y) + 1e-7f) + wk);
-  }
-  transform_sum2<Q>(sa, sb, red, tr);
-}
 
 // grid (ceil(frames / (2 * kPoints/N)), B), kPoints/16 threads; out[B, frames]
 template <int N>
@@ -420,11 +389,6 @@ int check_mfcc(int64_t B, int64_t T, int64_t n_fft, int64_t hop, int64_t n_mels,
   const int st = check_features(B, T, n_fft, hop);
   if (st) return st;
   return n_mels > kMaxMels ? DDSP_HIP_ERANGE : DDSP_HIP_OK;
-}
-
-unsigned frame_blocks(int64_t n_fft, int64_t frames) {
-  const int64_t per = 2 * ((n_fft == 4096 ? 4096 : 2048) / n_fft);  // two frames per transform, kPoints/N transforms
-  return (unsigned)((frames + per - 1) / per);
 }
 
 template <int N>

@@ -537,6 +537,36 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_stream(const at::Tensor& x,
   return {f0, conf, period};
 }
 
+// loudness_stream + pitch_stream in one launch over one state (ddsp_hip_stream_analysis)
+// -> (loudness, f0, confidence, period)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> analysis_stream(
+    const at::Tensor& x, const std::optional<at::Tensor>& weights, int64_t frame_length, int64_t hop, int64_t tau_min,
+    int64_t tau_max, double sample_rate, double threshold, const at::Tensor& counter, at::Tensor& state) {
+  at::Tensor xc = call_rows(x, "analysis_stream");
+  check_stream(counter, state, xc);
+  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "analysis_stream: call_samples must be a multiple of hop");
+  const int64_t B = xc.size(0), N = xc.size(1);
+  at::Tensor w;
+  if (weights.has_value() && weights->defined()) {
+    check_dev(*weights, "weights");
+    TORCH_CHECK(weights->numel() == frame_length / 2 + 1,
+                "analysis_stream: weights must hold frame_length/2+1 values");
+    w = weights->contiguous();
+  }
+  at::Tensor loud = at::empty({B, N / hop}, xc.options());
+  at::Tensor f0 = at::empty_like(loud);
+  at::Tensor conf = at::empty_like(loud);
+  at::Tensor period = at::empty({B, N / hop}, xc.options().dtype(at::kInt));
+  ok(ddsp_hip_stream_analysis(xc.data_ptr<float>(), w.defined() ? w.data_ptr<float>() : nullptr,
+                              loud.data_ptr<float>(), f0.data_ptr<float>(), conf.data_ptr<float>(),
+                              period.data_ptr<int32_t>(),
+                              reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
+                              (size_t)state.numel(), B, N, frame_length, hop, tau_min, tau_max, (float)sample_rate,
+                              (float)threshold, stream_of(xc)),
+     "stream_analysis");
+  return {loud, f0, conf, period};
+}
+
 }  // namespace
 
 // ---------------- decoder.py:33-68: the GRU recurrence ----------------
@@ -602,6 +632,8 @@ TORCH_LIBRARY(ddsp_hip, m) {
         " -> (Tensor, Tensor, Tensor)");
   m.def("pitch_stream(Tensor x, int frame_length, int hop, int tau_min, int tau_max, float sample_rate,"
         " float threshold, Tensor counter, Tensor(a!) state) -> (Tensor, Tensor, Tensor)");
+  m.def("analysis_stream(Tensor x, Tensor? weights, int frame_length, int hop, int tau_min, int tau_max,"
+        " float sample_rate, float threshold, Tensor counter, Tensor(a!) state) -> (Tensor, Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA key on ROCm
@@ -631,4 +663,5 @@ TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA 
   m.impl("mfcc_stream", &mfcc_stream);
   m.impl("pitch", &pitch);
   m.impl("pitch_stream", &pitch_stream);
+  m.impl("analysis_stream", &analysis_stream);
 }

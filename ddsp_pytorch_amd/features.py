@@ -56,7 +56,9 @@ class StreamAnalyzer:
     the stream's own (zeros before its start, no reflect padding); call k holds frames
     ``k R + first_frame[name] + j`` of the offline alignment (frame f centred at sample f * block_size), so each
     feature lags by ``delay_frames[name]`` frames (loudness: n_fft 2048, MFCC: n_fft 1024 as in ``analyze``; pitch:
-    2048, so it lags exactly as the loudness does).  The MFCC's top_db clamp is causal (``core.stream_mfcc``).
+    2048, so it lags exactly as the loudness does).  ``fused=True`` (needs ``pitch=True``): the loudness and the
+    pitch come from ONE launch over ONE state (``core.stream_analysis``; ``pitch_state is loudness_state``), the
+    same bits with one launch and one ring less.  The MFCC's top_db clamp is causal (``core.stream_mfcc``).
     ``mean_loudness`` / ``std_loudness`` as in ``analyze``.  After one warm-up call (the tables) nothing
     synchronises with the host: a call can be captured in a HIP graph over a static input buffer.  ``counter``: a
     stream counter to share (e.g. a ``core.StreamState``'s), with ``advance=False`` when that stream's own advance
@@ -65,9 +67,12 @@ class StreamAnalyzer:
     N_FFT = {"loudness": 2048, "mfcc": 1024, "pitch": 2048}
 
     def __init__(self, sample_rate, block_size, call_samples, batch=1, device="cuda", mean_loudness=None,
-                 std_loudness=None, counter=None, advance=True, pitch=False, fmin=50.0, fmax=2000.0):
+                 std_loudness=None, counter=None, advance=True, pitch=False, fmin=50.0, fmax=2000.0, fused=False):
         if (mean_loudness is None) != (std_loudness is None):
             raise ValueError("StreamAnalyzer: mean_loudness and std_loudness go together")
+        if fused and not pitch:
+            raise ValueError("StreamAnalyzer: fused=True is the loudness and the pitch in one launch; it needs "
+                             "pitch=True")
         self.sample_rate, self.block_size, self.call_samples = float(sample_rate), int(block_size), int(call_samples)
         self.mean_loudness, self.std_loudness = mean_loudness, std_loudness
         self.advance = bool(advance)
@@ -78,31 +83,45 @@ class StreamAnalyzer:
                                                   counter=self.counter)
         self.delay_frames = {"loudness": self.loudness_state.delay_frames, "mfcc": self.mfcc_state.delay_frames}
         self.pitch, self.fmin, self.fmax = bool(pitch), float(fmin), float(fmax)
+        self.fused = bool(fused)
         self.pitch_state = None
         if self.pitch:
             core.pitch_lags(sample_rate, fmin, fmax, self.N_FFT["pitch"])  # a bad range is refused here
-            self.pitch_state = core.FeatureStreamState(batch, device, call_samples, self.N_FFT["pitch"], block_size,
-                                                       counter=self.counter)
+            if self.fused:  # one ring for both: the same frames of the same samples
+                if self.N_FFT["pitch"] != self.N_FFT["loudness"]:
+                    raise RuntimeError("StreamAnalyzer: fused=True needs one frame length for loudness and pitch")
+                self.pitch_state = self.loudness_state
+            else:
+                self.pitch_state = core.FeatureStreamState(batch, device, call_samples, self.N_FFT["pitch"],
+                                                           block_size, counter=self.counter)
             self.delay_frames["pitch"] = self.pitch_state.delay_frames
         self.first_frame = {k: -v for k, v in self.delay_frames.items()}
 
     def reset(self):
         self.loudness_state.reset()
         self.mfcc_state.reset()
-        if self.pitch_state is not None:
+        if self.pitch_state is not None and self.pitch_state is not self.loudness_state:
             self.pitch_state.reset()
 
     @torch.no_grad()
     def __call__(self, audio):
-        loudness = core.stream_loudness(audio, self.sample_rate, self.block_size, self.loudness_state,
-                                        n_fft=self.N_FFT["loudness"])
+        f0 = conf = None
+        if self.fused:
+            loudness, f0, conf = core.stream_analysis(audio, self.sample_rate, self.block_size, self.loudness_state,
+                                                      fmin=self.fmin, fmax=self.fmax,
+                                                      frame_length=self.N_FFT["loudness"], return_confidence=True)
+        else:
+            loudness = core.stream_loudness(audio, self.sample_rate, self.block_size, self.loudness_state,
+                                            n_fft=self.N_FFT["loudness"])
         if self.mean_loudness is not None:
             loudness = (loudness - self.mean_loudness) / self.std_loudness
         mfcc = core.stream_mfcc(audio, self.sample_rate, self.block_size, self.mfcc_state, n_fft=self.N_FFT["mfcc"])
         out = {"loudness": loudness.unsqueeze(-1), "mfcc": mfcc}
         if self.pitch:
-            f0, conf = core.stream_pitch(audio, self.sample_rate, self.block_size, self.pitch_state, fmin=self.fmin,
-                                         fmax=self.fmax, frame_length=self.N_FFT["pitch"], return_confidence=True)
+            if not self.fused:
+                f0, conf = core.stream_pitch(audio, self.sample_rate, self.block_size, self.pitch_state,
+                                             fmin=self.fmin, fmax=self.fmax, frame_length=self.N_FFT["pitch"],
+                                             return_confidence=True)
             out["pitch"], out["confidence"] = f0.unsqueeze(-1), conf.unsqueeze(-1)
         if self.advance:
             core.stream_advance(self.loudness_state)

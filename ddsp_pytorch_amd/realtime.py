@@ -30,7 +30,9 @@ calls of N samples are the K N samples the offline model renders.
 ``loudness_from_audio=True`` makes the input side seamless too: the second input of a call is the stream's
 audio, and the graph computes the loudness from it (`ddsp_hip_stream_loudness`, one more launch: the reference's
 `extract_loudness`, core.py:81-97, with the history a 2048-sample window needs carried on the device) before
-the normalisation and the control network.
+the normalisation and the control network.  ``pitch_from_audio=True`` on top of it makes the audio the only input:
+that launch becomes `ddsp_hip_stream_analysis`, which computes the loudness and the YIN f0 of the same frames side by
+side over the same ring, and the f0 drives the control network and the synthesis — audio in, audio out.
 """
 from collections import namedtuple
 
@@ -63,11 +65,22 @@ class RealtimeGraph:
     block 256) after its centre, so the loudness that drives a call's frames is that much older than the call's
     samples.  The pitch is NOT delayed to match: pitch trackers bring a latency of their own, and aligning the
     two is the caller's.  The analysis shares the stream's call counter (with ``continuous`` the `StreamState`'s),
-    its state is `self.analysis` (core.FeatureStreamState), and `reset()` zeroes it too."""
+    its state is `self.analysis` (core.FeatureStreamState), and `reset()` zeroes it too.
+
+    ``pitch_from_audio=True`` (needs ``loudness_from_audio=True``; with or without ``continuous`` / ``reverb``):
+    ``__call__(audio)`` — the call's audio [1, N, 1] is the only input (a host call copies N floats in, not 2 N),
+    and the graph runs `core.stream_analysis` on it: the loudness and the YIN f0 (``pitch_fmin`` .. ``pitch_fmax``
+    Hz, ``pitch_threshold``) of the same 2048-sample frames in one launch over the one analysis state, so the graph
+    holds as many launches as with ``loudness_from_audio`` alone.  The per-frame f0 drives the control network and
+    the synthesis; it lags as the loudness does (`pitch_delay_samples == loudness_delay_samples`).  `self.f0` and
+    `self.confidence` are static [1, R] device buffers holding the last call's values, for the host to monitor or
+    gate on.  Nothing holds or smooths f0: an unvoiced or silent frame carries YIN's value as it is (a silent frame
+    gives sample_rate / tau_min with confidence 0), and the instrument is then as quiet as its loudness says."""
 
     def __init__(self, model, call_samples=1024, mean_loudness=0.0, std_loudness=1.0,
                  seed=0x5EEDDD5B, device=None, warmup=3, fused=True, gru_route="steps",
-                 continuous=False, reverb=False, wrap=None, loudness_from_audio=False):
+                 continuous=False, reverb=False, wrap=None, loudness_from_audio=False, pitch_from_audio=False,
+                 pitch_fmin=50.0, pitch_fmax=2000.0, pitch_threshold=0.1):
         device = torch.device(device) if device is not None else next(model.parameters()).device
         if device.type != "cuda":
             raise RuntimeError("RealtimeGraph: the model must be on a HIP device")
@@ -112,6 +125,17 @@ class RealtimeGraph:
         if self.loudness_from_audio:  # raises on a call size or block the streamed analysis cannot take
             self.analysis = core.FeatureStreamState(1, device, N, 2048, bs, counter=self.counter)
             self.loudness_delay_samples = self.analysis.delay_frames * bs
+        self.pitch_from_audio = bool(pitch_from_audio)
+        self.pitch_fmin, self.pitch_fmax = float(pitch_fmin), float(pitch_fmax)
+        self.pitch_threshold = float(pitch_threshold)
+        self.pitch_delay_samples = 0
+        self.f0 = self.confidence = None
+        if self.pitch_from_audio:
+            if not self.loudness_from_audio:
+                raise RuntimeError("RealtimeGraph: pitch_from_audio=True needs loudness_from_audio=True (one launch "
+                                   "computes both from the same frames of the same ring)")
+            core.pitch_lags(self.sample_rate, self.pitch_fmin, self.pitch_fmax, self.analysis.n_fft)  # a bad range
+            self.pitch_delay_samples = self.loudness_delay_samples
         self._inp_h = torch.zeros(2, N, 1).pin_memory()
         self._out_h = torch.zeros(1, N, 1).pin_memory()
         self.fused = bool(fused)
@@ -162,12 +186,21 @@ class RealtimeGraph:
         core.stream_advance(self.stream, f0, bs, self.sample_rate, wrap=self.wrap)
         return out
 
-    def _loudness_frames(self):
-        """The call's loudness, one value per frame: (tensor, its stride) — the input decimated by block_size,
-        or with ``loudness_from_audio`` the streamed analysis of the audio in the loudness buffer."""
+    def _control_frames(self):
+        """The call's pitch and loudness, one value per frame: (pitch, its stride, loudness, its stride) — the
+        inputs decimated by block_size; with ``loudness_from_audio`` the loudness is the streamed analysis of the
+        audio in the loudness buffer (stride 1); with ``pitch_from_audio`` both come from that audio in one launch,
+        and the call's f0 and confidence stay in ``self.f0`` / ``self.confidence``."""
         if not self.loudness_from_audio:
-            return self.loudness, self.block_size
-        return core.stream_loudness(self.loudness, self.sample_rate, self.block_size, self.analysis), 1
+            return self.pitch, self.block_size, self.loudness, self.block_size
+        if not self.pitch_from_audio:
+            loud = core.stream_loudness(self.loudness, self.sample_rate, self.block_size, self.analysis)
+            return self.pitch, self.block_size, loud, 1
+        loud, self.f0, self.confidence = core.stream_analysis(
+            self.loudness, self.sample_rate, self.block_size, self.analysis, fmin=self.pitch_fmin,
+            fmax=self.pitch_fmax, frame_length=self.analysis.n_fft, threshold=self.pitch_threshold,
+            return_confidence=True)
+        return self.f0, 1, loud, 1
 
     def _setup_fused(self):
         m, dev = self.model, self.device
@@ -200,9 +233,9 @@ class RealtimeGraph:
         di = core.dense_input
         inv = 1.0 / self.std_loudness
         f0m, lm, om = d.f0_mlp, d.loudness_mlp, d.out_mlp
-        loud, loud_ld = self._loudness_frames()
+        pitch, pitch_ld, loud, loud_ld = self._control_frames()
         core.dense_rows([  # mlp layers 1-2 (core.py:122-129), f0 and loudness
-            ([di(self.pitch, ld=bs, first=f0m[0], norm=f0m[1], x_copy=b["f0"])], f0m[3], b["y2f"]),
+            ([di(pitch, ld=pitch_ld, first=f0m[0], norm=f0m[1], x_copy=b["f0"])], f0m[3], b["y2f"]),
             ([di(loud, ld=loud_ld, scale=inv, shift=-self.mean_loudness * inv, first=lm[0], norm=lm[1],
                  x_copy=b["loud"])], lm[3], b["y2l"])], R, dev)
         core.dense_rows([([di(b["y2f"], norm=f0m[4])], f0m[6], b["y3f"]),
@@ -232,8 +265,8 @@ class RealtimeGraph:
         if self.fused:
             return self._forward_fused()
         m, bs = self.model, self.block_size
-        pitch = self.pitch[:, ::bs]
-        loud, loud_ld = self._loudness_frames()
+        pitch, pitch_ld, loud, loud_ld = self._control_frames()
+        pitch = pitch.view(1, -1, 1)[:, ::pitch_ld]
         loudness = (loud.view(1, -1, 1)[:, ::loud_ld] - self.mean_loudness) / self.std_loudness
         hidden = gru_decoder_forward(m.decoder, pitch, loudness, None, realtime=True)
         param = m.harmonic_proj(hidden)
@@ -249,9 +282,15 @@ class RealtimeGraph:
             self.analysis.reset()
 
     @torch.no_grad()
-    def __call__(self, pitch, loudness):
+    def __call__(self, pitch, loudness=None):
         """pitch, loudness [1, N, 1] on the host (returns a host tensor) or on the device (returns
-        the device output buffer).  With ``loudness_from_audio`` the second input is the call's audio."""
+        the device output buffer).  With ``loudness_from_audio`` the second input is the call's audio; with
+        ``pitch_from_audio`` the call's audio is the only input."""
+        if self.pitch_from_audio:
+            return self._call_audio(pitch, loudness)
+        if loudness is None:
+            raise RuntimeError("RealtimeGraph: two inputs expected, pitch and loudness (one, the audio, only with "
+                               "pitch_from_audio=True)")
         if tuple(pitch.shape) != (1, self.call_samples, 1) or tuple(loudness.shape) != tuple(pitch.shape):
             raise RuntimeError(f"RealtimeGraph: pitch and loudness must be [1, {self.call_samples}, 1]")
         stream = torch.cuda.current_stream(self.device)
@@ -263,6 +302,25 @@ class RealtimeGraph:
         self._inp_h[0:1].copy_(pitch)
         self._inp_h[1:2].copy_(loudness)
         self._inp.copy_(self._inp_h, non_blocking=True)
+        self.graph.replay()
+        self._out_h.copy_(self.out, non_blocking=True)
+        stream.synchronize()
+        return self._out_h
+
+    def _call_audio(self, audio, extra):
+        """``pitch_from_audio``: the call's audio [1, N, 1] in (N floats, not 2 N), audio out."""
+        if extra is not None:
+            raise RuntimeError("RealtimeGraph(pitch_from_audio=True) takes one input, the call's audio; the pitch "
+                               "is computed from it")
+        if tuple(audio.shape) != (1, self.call_samples, 1):
+            raise RuntimeError(f"RealtimeGraph: audio must be [1, {self.call_samples}, 1]")
+        if audio.is_cuda:
+            self.loudness.copy_(audio)
+            self.graph.replay()
+            return self.out
+        stream = torch.cuda.current_stream(self.device)
+        self._inp_h[1:2].copy_(audio)
+        self.loudness.copy_(self._inp_h[1:2], non_blocking=True)
         self.graph.replay()
         self._out_h.copy_(self.out, non_blocking=True)
         stream.synchronize()

@@ -712,6 +712,25 @@ int ddsp_hip_stream_pitch(const float* x, float* f0, float* confidence, int32_t*
                           int64_t hop, int64_t tau_min, int64_t tau_max, float sample_rate, float threshold,
                           void* stream);
 
+/* ddsp_hip_stream_loudness and ddsp_hip_stream_pitch of one call in ONE launch over ONE state, for a stream whose
+ * loudness and pitch use the same frame length L (n_fft == frame_length == L: the same frames of the same samples).
+ * loudness_out [batch, R] holds ddsp_hip_stream_loudness(n_fft = L)'s bits and f0 / confidence / period [batch, R]
+ * hold ddsp_hip_stream_pitch(frame_length = L)'s bits: the per-frame code is the same and every reduction order is
+ * fixed, so only the grid differs — the first workgroups of an item take the pitch frames (one per transform), the
+ * rest the loudness frames (two per transform), side by side.  weights as ddsp_hip_loudness (NULL = zeros);
+ * confidence and period may be NULL.  State: one buffer of ddsp_hip_stream_features_state_bytes(batch, call_samples,
+ * L, hop) bytes, zero-filled for a fresh stream, with the ring layout of "streaming analysis" above — a state either
+ * separate entry point has filled can be continued by this one and back.  The counter is read and never written; the
+ * call copies x into the ring under the argument given there (no workgroup reads what another writes, whatever its
+ * role), so a call run twice before the advance gives the same bits.
+ * Checked before any HIP call, in this order: the streaming envelope (as ddsp_hip_stream_loudness), the pitch
+ * parameters (as ddsp_hip_stream_pitch, so L in [64, 4096]), batch == 0: a no-op success, null x / loudness_out / f0 /
+ * counter / state: DDSP_HIP_EINVAL, a short state: DDSP_HIP_EWORKSPACE. */
+int ddsp_hip_stream_analysis(const float* x, const float* weights, float* loudness_out, float* f0, float* confidence,
+                             int32_t* period, const uint64_t* counter, void* state, size_t state_bytes, int64_t batch,
+                             int64_t call_samples, int64_t frame_length, int64_t hop, int64_t tau_min, int64_t tau_max,
+                             float sample_rate, float threshold, void* stream);
+
 /* Two-stage serving pipeline (ddsp_pytorch_amd.synth.PipelinedSynthPath; no reference counterpart:
  * the reference synthesises one batch at a time, decoder.py:101-136).  A HIP stream restricted to
  * the CUs whose bits are set in cu_mask (mask_words 32-bit words, bit c = CU index c; HIP deals

@@ -16,6 +16,10 @@ history a call's frames need plus the call), the window's shift included.  DESIG
 same definition (include/ddsp_hip.h, "pitch") composed from torch.fft and ATen ops in fp64 — what a user would
 write today; the package had no pitch path before — and core.stream_pitch at the realtime shape, captured in a HIP
 graph.  DESIGN.md 3f-pitch records a run.
+
+``--leg fused`` times core.stream_analysis (the streamed loudness and pitch in one launch over one state) against
+core.stream_loudness + core.stream_pitch (two launches, two states) at the realtime shape, each captured in a HIP
+graph, the legs' windows alternating.  DESIGN.md 3f-fused records a run.
 """
 import argparse
 import json
@@ -200,16 +204,47 @@ def stream_leg(dev, reps, windows):
               flush=True)
 
 
+def fused_leg(dev, reps, windows):
+    """The fused launch (core.stream_analysis, one state) against the route without it (core.stream_loudness +
+    core.stream_pitch, two launches on two states), each captured in a HIP graph; the legs' windows alternate, so
+    that a drift of the box lands on all of them alike."""
+    sr, hop, N, L = 48000, 256, 1024, 2048
+    x = 0.1 * torch.randn(1, N, device=dev)
+    sf = core.FeatureStreamState(1, dev, N, L, hop)
+    sl = core.FeatureStreamState(1, dev, N, L, hop, counter=sf.counter)
+    sp = core.FeatureStreamState(1, dev, N, L, hop, counter=sf.counter)
+    kw = dict(return_confidence=True, return_period=True)
+    legs = [
+        ("stream loudness + stream pitch (two launches, two states)",
+         graphed(lambda: (core.stream_loudness(x, sr, hop, sl, n_fft=L), core.stream_pitch(x, sr, hop, sp, **kw))), 2),
+        ("stream analysis (one launch, one state)", graphed(lambda: core.stream_analysis(x, sr, hop, sf, **kw)), 1),
+        ("stream pitch", graphed(lambda: core.stream_pitch(x, sr, hop, sp, **kw)), 1),
+        ("stream loudness", graphed(lambda: core.stream_loudness(x, sr, hop, sl, n_fft=L)), 1),
+    ]
+    ms = [[] for _ in legs]
+    for _ in range(windows):
+        for i, (_, fn, _) in enumerate(legs):
+            ms[i].append(timed(fn, reps, 1)[0])
+    for (leg, _, launches), m in zip(legs, ms):
+        print(json.dumps({"shape": "stream 1x1024 block 256 L 2048", "leg": leg, "graph_nodes": launches,
+                          "us": round(1e3 * statistics.median(m), 2), "us_min": round(1e3 * min(m), 2),
+                          "us_max": round(1e3 * max(m), 2), "windows_us": [round(1e3 * v, 2) for v in m]}),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=1000)
     ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--leg", choices=("offline", "stream", "pitch", "all"), default="all",
-                    help="all: offline and stream (the pitch leg runs on request)")
+    ap.add_argument("--leg", choices=("offline", "stream", "pitch", "fused", "all"), default="all",
+                    help="all: offline and stream (the pitch and fused legs run on request)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_features: needs a HIP device (there is no CPU path)")
     dev = torch.device("cuda", 0)
+    if args.leg == "fused":
+        fused_leg(dev, args.reps, args.windows)
+        return
     if args.leg == "pitch":
         pitch_leg(dev, args.reps, args.windows)
         return

@@ -14,7 +14,9 @@ Drop-in for hugofloresgarcia/ddsp_pytorch's synthesis hot path:
   ``extract_pitch`` is the CREPE network, which this package does not carry), so ``analyze(signal, None, ...)``
   runs from audio alone; ``core.stream_analysis``: the streamed loudness and pitch in one launch over one state,
   which ``realtime.RealtimeGraph(loudness_from_audio=True, pitch_from_audio=True)`` runs per call (audio in,
-  audio out);
+  audio out); ``core.stream_analysis_mfcc`` / ``StreamAnalyzer(aligned=True)``: the streamed loudness, MFCC and pitch
+  of the same frames in one launch on one time axis, which ``RealtimeGraph`` runs for a ``DDSPAutoencoder`` (the
+  encoder's GRU state carried between calls): realtime timbre transfer from audio alone;
 * ``DDSPDecoder`` and ``DDSPAutoencoder`` — the reference's two models (same state_dicts) running
   on these kernels.
 

@@ -26,11 +26,11 @@ _SZ = ctypes.c_size_t
 class DenseInput(ctypes.Structure):
     """ddsp_hip_dense_input (include/ddsp_hip.h)."""
     _fields_ = [("x", _P), ("ld", _I64), ("width", _I64), ("scale", _F), ("shift", _F), ("w1", _P),
-                ("b1", _P), ("gamma", _P), ("beta", _P), ("x_copy", _P)]
+                ("b1", _P), ("gamma", _P), ("beta", _P), ("x_copy", _P), ("plain_norm", _I)]
 
 
 DENSE_MAX_INPUTS = 3
-DENSE_MAX_PROBLEMS = 2
+DENSE_MAX_PROBLEMS = 3
 
 
 class DenseProblem(ctypes.Structure):
@@ -122,6 +122,9 @@ SIGNATURES = {
     # streamed loudness + pitch of one call in one launch over one state
     "ddsp_hip_stream_analysis": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64, _I64, _I64, _F, _F,
                                       _P]),
+    # streamed loudness + MFCC (+ pitch) of one call in one launch over one state, on one time axis
+    "ddsp_hip_stream_analysis_mfcc": (_I, [_P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _SZ, _I64, _I64,
+                                           _I64, _I64, _I64, _I64, _I64, _F, _I64, _I64, _F, _F, _P]),
     # backward
     "ddsp_hip_scale_function_backward": (_I, [_P, _P, _P, _I64, _F, _P]),
     "ddsp_hip_upsample_backward": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P]),

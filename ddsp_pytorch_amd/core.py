@@ -29,7 +29,7 @@ __all__ = [
     "harmonic_synth_frames", "harmonic_synth_params", "synth_frames", "synth_signal", "filtered_noise", "reverb_build_impulse", "reverb_spectrum_floats",
     "reverb_spectrum", "reverb_impulse_spectrum", "reverb_apply", "reverb_forward", "reverb_cache_bytes", "set_noise_seed", "safe_log", "stft_magnitude", "multiscale_fft",
     "extract_loudness", "mfcc", "FeatureStreamState", "stream_loudness", "stream_mfcc", "stream_feature_delay",
-    "extract_pitch", "stream_pitch", "pitch_lags", "stream_analysis",
+    "extract_pitch", "stream_pitch", "pitch_lags", "stream_analysis", "stream_analysis_mfcc",
 ]
 
 
@@ -814,9 +814,10 @@ def ln_leaky_launch(h, gamma, beta, eps, slope, out=None, w1=None, b1=None):
     return None if st == ERANGE else out
 
 
-def dense_input(x, width=None, ld=None, scale=1.0, shift=0.0, first=None, norm=None, x_copy=None):
+def dense_input(x, width=None, ld=None, scale=1.0, shift=0.0, first=None, norm=None, x_copy=None, activation=True):
     """One input segment of dense_rows: x [rows, ld] (or, with `first` = a K=1 nn.Linear, one value
-    per row at x[r * ld]); `norm` = an nn.LayerNorm applied with LeakyReLU(0.01) after it."""
+    per row at x[r * ld]); `norm` = an nn.LayerNorm applied with LeakyReLU(0.01) after it, or with
+    ``activation=False`` alone (the MFCC encoder's ``norm``)."""
     inp = _lib.DenseInput()
     inp.x = x.data_ptr()
     inp.scale, inp.shift = float(scale), float(shift)
@@ -830,15 +831,20 @@ def dense_input(x, width=None, ld=None, scale=1.0, shift=0.0, first=None, norm=N
         if norm.eps != 1e-5 or norm.weight is None:
             raise RuntimeError("dense_input: LayerNorm(eps=1e-5, elementwise_affine) expected")
         inp.gamma, inp.beta = norm.weight.data_ptr(), norm.bias.data_ptr()
+        inp.plain_norm = 0 if activation else 1
+    elif not activation:
+        raise RuntimeError("dense_input: activation=False goes with a norm")
     if x_copy is not None:
         inp.x_copy = x_copy.data_ptr()
     return inp
 
 
 def dense_rows(problems, rows, device):
-    """ddsp_hip_dense_rows: up to two Linears (each `(inputs, linear, y)`, inputs from dense_input,
+    """ddsp_hip_dense_rows: up to three Linears (each `(inputs, linear, y)`, inputs from dense_input,
     y [rows, out_features] contiguous) over `rows` <= 8 rows in one launch (core.py:122-129 blocks
     with the LayerNorm/LeakyReLU of the previous block folded into the input)."""
+    if not 1 <= len(problems) <= _lib.DENSE_MAX_PROBLEMS:
+        raise RuntimeError(f"dense_rows: 1 to {_lib.DENSE_MAX_PROBLEMS} problems per launch")
     arr = (_lib.DenseProblem * len(problems))()
     for i, (inputs, lin, y) in enumerate(problems):
         P = arr[i]
@@ -1329,6 +1335,42 @@ def stream_analysis(x, sample_rate, block_size, state, fmin=50.0, fmax=2000.0, f
               _lib.ptr(period), _lib.ptr(state.counter), _lib.ptr(state.buf), state.buf.numel(), B, N, L,
               int(block_size), tau_min, tau_max, float(sample_rate), float(threshold), _lib.stream_of(xc))
     return (loud,) + tuple(t for t in (f0, conf, period) if t is not None)
+
+
+def stream_analysis_mfcc(x, sample_rate, block_size, state, pitch=True, fmin=50.0, fmax=2000.0, frame_length=2048,
+                         threshold=0.1, return_confidence=False, return_period=False, n_mfcc=30, mfcc_n_fft=1024,
+                         n_mels=128, mel_fmin=20.0, mel_fmax=8000.0, top_db=80.0):
+    """The streamed loudness, MFCC and (``pitch=True``) YIN pitch of one call in ONE launch over ONE state, on ONE
+    time axis (ddsp_hip_stream_analysis_mfcc): x [B, N] or [B, N, 1] -> (loudness [B, R], mfcc [B, R, n_mfcc]
+    [, f0 [B, R]] [, confidence] [, period]), R = N // block_size.  Loudness and pitch are ``stream_analysis``'s
+    bits (frame length ``frame_length`` = L).  MFCC slot j is the ``mfcc_n_fft`` = M-sample window (M = L or L/2)
+    centred in frame j's L-sample window, so all three describe stream frame k R - state.delay_frames + j: the
+    bits of ``stream_mfcc(n_fft=M)`` fed the same stream delayed by
+    (stream_feature_delay(L) - stream_feature_delay(M)) * block_size samples.  ``fmin`` / ``fmax`` / ``threshold``
+    are the pitch's, ``mel_fmin`` / ``mel_fmax`` / ``n_mels`` / ``top_db`` the MFCC's (its clamp causal, its running
+    maximum in ``state``).  ``state``: a ``FeatureStreamState(B, device, N, frame_length, block_size)``, the same
+    as ``stream_analysis``'s; ``stream_advance`` ends the call.  Tables cached as the neighbours'; no host
+    synchronisation after the first call."""
+    L, M = int(frame_length), int(mfcc_n_fft)
+    xc = _stream_call_rows(x, state, block_size, L, "stream_analysis_mfcc")
+    if not pitch and (return_confidence or return_period):
+        raise RuntimeError("stream_analysis_mfcc: confidence and period come with pitch=True")
+    tau_min, tau_max = pitch_lags(sample_rate, fmin, fmax, L) if pitch else (0, 0)
+    (w,) = _feature_tables("a_weighting", (float(sample_rate), L), xc.device,
+                           lambda: (a_weighting_table(sample_rate, L),))
+    band_start, band_count, band_weights, dct = mfcc_tables(sample_rate, n_mfcc, M, n_mels, mel_fmin, mel_fmax,
+                                                            xc.device)
+    B, N = xc.shape
+    loud = torch.empty(B, state.frames, dtype=torch.float32, device=xc.device)
+    out = torch.empty(B, state.frames, int(n_mfcc), dtype=torch.float32, device=xc.device)
+    f0, conf, period = _pitch_outputs(B, state.frames, xc.device, return_confidence, return_period) if pitch \
+        else (None, None, None)
+    _lib.call("stream_analysis_mfcc", _lib.ptr(xc), _lib.ptr(w), _lib.ptr(loud), _lib.ptr(band_start),
+              _lib.ptr(band_count), _lib.ptr(band_weights), band_weights.numel(), _lib.ptr(dct), _lib.ptr(out),
+              _lib.ptr(f0), _lib.ptr(conf), _lib.ptr(period), _lib.ptr(state.counter), _lib.ptr(state.buf),
+              state.buf.numel(), B, N, L, M, int(block_size), int(n_mels), int(n_mfcc), float(top_db), tau_min,
+              tau_max, float(sample_rate), float(threshold), _lib.stream_of(xc))
+    return (loud, out) + tuple(t for t in (f0, conf, period) if t is not None)
 
 
 from . import grad as _grad  # noqa: E402  (autograd Functions over the backward kernels)

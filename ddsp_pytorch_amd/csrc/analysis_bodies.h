@@ -1,7 +1,8 @@
 // The per-frame bodies of the analysis kernels, written once: the loudness's reduction over a packed spectrum
-// (features.hip's loudness kernels) and the YIN estimator of one frame (pitch.hip's kernels), with the envelope and
-// the grid arithmetic that go with them.  stream_analysis.hip runs both side by side in one launch, in different
-// workgroups; since the bodies are these, its bits are those of the separate launches.
+// (features.hip's loudness kernels), the YIN estimator of one frame (pitch.hip's kernels) and the streamed MFCC of
+// one call (features.hip's stream_mfcc_kernel), with the envelope and the grid arithmetic that go with them.
+// stream_analysis.hip and stream_analysis_mfcc.hip run them side by side in one launch, in different workgroups;
+// since the bodies are these, their bits are those of the separate launches.
 #pragma once
 
 #include <climits>
@@ -256,6 +257,199 @@ inline int check_pitch_params(int64_t L, int64_t tau_min, int64_t tau_max, float
 inline unsigned pitch_blocks(int64_t L, int64_t frames) {
   const int64_t per = (L == 4096 ? 4096 : 2048) / L;
   return (unsigned)((frames + per - 1) / per);
+}
+
+// ---------------- MFCC: mel dB of packed frames, the causal clamp, the DCT ----------------
+constexpr int kMaxMels = 256;  // n_mels cap (the band tables live in LDS)
+constexpr int kDctFrames = 8;  // frames per workgroup of the DCT launch
+constexpr int kDctChunk = 32;  // mel columns of the DCT table staged per pass
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
+  return v;
+}
+
+// The mel rows' band tables into LDS for a workgroup of THREADS threads: s_start / s_count, cut to the spectrum's
+// BINS bins, and s_off, the rows' offsets into band_w (an exclusive scan of the counts; thread tid holds rows
+// RPT tid ..).  The caller's next barrier publishes them.
+template <int THREADS, int BINS>
+__device__ __forceinline__ void stage_bands(const int* __restrict__ band_start, const int* __restrict__ band_count,
+                                            int n_mels, int* s_start, int* s_count, int* s_off, int* s_wave) {
+  constexpr int RPT = kMaxMels / THREADS;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int st[RPT], cnt[RPT], sum = 0;
+#pragma unroll
+  for (int j = 0; j < RPT; ++j) {
+    const int m = RPT * tid + j;
+    st[j] = m < n_mels ? min(max(band_start[m], 0), BINS) : 0;
+    cnt[j] = m < n_mels ? min(max(band_count[m], 0), 1 << 20) : 0;
+    sum += cnt[j];
+  }
+  int v = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  if (lane == 63) s_wave[wid] = v;
+  __syncthreads();
+  int off = v - sum;
+  for (int i = 0; i < wid; ++i) off += s_wave[i];
+#pragma unroll
+  for (int j = 0; j < RPT; ++j) {
+    const int m = RPT * tid + j;
+    s_off[m] = off;
+    s_start[m] = st[j];
+    s_count[m] = min(cnt[j], BINS - st[j]);
+    off += cnt[j];
+  }
+}
+
+// Mel row m of the two packed frames whose powers are in lds: (10 log10(max(1e-10, energy_a)), the same of b).
+__device__ __forceinline__ float2 mel_db_pair(const double2* lds, const float* __restrict__ band_w, int n_w, int s0,
+                                              int c, int off) {
+  double ea = 0.0, eb = 0.0;
+  for (int j = 0; j < c; ++j) {
+    const double wj = off + j < n_w ? (double)band_w[off + j] : 0.0;
+    const double2 p = lds[lds_idx(s0 + j)];
+    ea = fma(wj, p.x, ea);
+    eb = fma(wj, p.y, eb);
+  }
+  return make_float2(10.0f * log10f(fmaxf(1e-10f, (float)ea)), 10.0f * log10f(fmaxf(1e-10f, (float)eb)));
+}
+
+// One pass of the MFCC's loop: frames fa and fa + 1 of the call through the packed transform, then both frames'
+// power over the spectrum in place (the thread that owns the pair {k, N-k} writes slot k; no other thread reads k
+// or N-k), published by the closing barrier.  Kept out of line on purpose: inlined into the caller's loop over
+// passes, this code came out of the compiler wrong on gfx950 for every n_fft whose last FFT stage is not radix-2
+// (bin 0 exact, every other bin off by decibels; the same source as a function, or with the loop removed, is
+// exact).  The cause in the compiler was not found; tests/test_gpu_stream_features.py covers every size.
+// The fetch comes by value, in registers: by reference the caller had to keep it in 48 B of scratch per thread.
+template <int N>
+__device__ __noinline__ void spectrum_power_pass(const StreamFetch fetch, int fa, int t, double2* lds) {
+  constexpr int Q = N / 16, BINS = N / 2 + 1;
+  packed_spectrum<N>(fetch, fa, t, lds);
+  for (int k = t; k < BINS; k += Q) lds[lds_idx(k)] = packed_power<N>(lds, k);
+  __syncthreads();
+}
+
+struct MfccTables {
+  const int *start, *count;
+  const float* w;
+  int n_w;
+  const float* dct;
+  int n_mels, n_mfcc;
+  float top_db;
+};
+
+// The LDS the streamed MFCC keeps beside the transforms' lds_all.
+struct MfccLds {
+  float* sD;  // [kStreamMaxFrames * kMaxMels]: the call's D
+  int *s_start, *s_count, *s_off;  // [kMaxMels] each
+  int* s_wave;   // [waves of the workgroup]
+  float* s_max;  // [waves of the workgroup]
+  float* s_floor;
+};
+
+// The streamed MFCC of one item's call by one workgroup of kPoints<N>/16 threads (features.hip's stream_mfcc_kernel;
+// stream_analysis_mfcc.hip's MFCC workgroup): it loops over the call's frame pairs (kPoints/N transforms per pass) as
+// mel_db_kernel does, keeping D[frames, n_mels] in LDS; folds the call's largest D with the item's carried maximum
+// *runmax (taken as absent when `carried` is false, whatever the stored bits) and stores the result; clamps D at
+// that maximum - top_db; and applies the DCT out of LDS as mfcc_dct_kernel does (kDctFrames frames per round, the
+// table staged kDctChunk columns at a time in the transforms' LDS, m ascending, fp64 accumulator) into
+// out[frames, n_mfcc].  A second run before the advance folds the same call into a maximum that already holds it:
+// the same bits.  Every thread of the workgroup calls this.
+template <int N>
+__device__ __forceinline__ void stream_mfcc_body(const StreamFetch& fetch, bool carried, double2* lds_all,
+                                                 const MfccLds& s, const MfccTables& m,
+                                                 float* runmax, float* __restrict__ out) {
+  constexpr int Q = N / 16, THREADS = kPoints<N> / 16, TPW = kPoints<N> / N, BINS = N / 2 + 1;
+  constexpr int WAVES = THREADS / 64, FR = kDctFrames, MC = kDctChunk;
+  constexpr int TASKS = FR * kMaxMels / THREADS;  // DCT outputs per thread and round
+  static_assert(sizeof(double2) * TPW * (N + N / 16) >= sizeof(float) * kMaxMels * (MC + 1), "the DCT table's LDS");
+  float* sT = reinterpret_cast<float*>(lds_all);
+  float* sD = s.sD;
+  const int frames = fetch.frames, n_mels = m.n_mels, n_mfcc = m.n_mfcc;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  stage_bands<THREADS, BINS>(m.start, m.count, n_mels, s.s_start, s.s_count, s.s_off, s.s_wave);
+  const int tr = tid / Q, t = tid - tr * Q;
+  double2* lds = lds_all + tr * (N + N / 16);
+  float mx = -INFINITY;
+  for (int f0 = 0; f0 < frames; f0 += 2 * TPW) {
+    const int fa = f0 + 2 * tr;
+    spectrum_power_pass<N>(fetch, fa, t, lds);  // (its barriers publish s_*)
+    const bool va = fa < frames, vb = fa + 1 < frames;
+    float* Da = sD + (va ? fa : 0) * n_mels;
+    for (int mm = t; mm < n_mels; mm += Q) {
+      const float2 d = mel_db_pair(lds, m.w, m.n_w, s.s_start[mm], s.s_count[mm], s.s_off[mm]);
+      if (va) {
+        Da[mm] = d.x;
+        mx = fmaxf(mx, d.x);
+      }
+      if (vb) {
+        Da[n_mels + mm] = d.y;
+        mx = fmaxf(mx, d.y);
+      }
+    }
+    __syncthreads();  // the powers consumed before the next pass (or the DCT table) overwrites them
+  }
+  mx = wave_max(mx);
+  if (lane == 0) s.s_max[wid] = mx;
+  __syncthreads();
+  if (tid == 0) {
+    float r = s.s_max[0];
+#pragma unroll
+    for (int i = 1; i < WAVES; ++i) r = fmaxf(r, s.s_max[i]);
+    if (carried) r = fmaxf(r, *runmax);
+    *runmax = r;
+    *s.s_floor = r - m.top_db;
+  }
+  __syncthreads();
+  const float floor_db = *s.s_floor;
+  for (int i = tid; i < frames * n_mels; i += THREADS) sD[i] = fmaxf(sD[i], floor_db);
+  for (int f0 = 0; f0 < frames; f0 += FR) {
+    const int nf = min(FR, frames - f0);
+    const int tasks = nf * n_mfcc;  // task o = f * n_mfcc + i, <= THREADS * TASKS
+    double acc[TASKS];
+#pragma unroll
+    for (int j = 0; j < TASKS; ++j) acc[j] = 0.0;
+    for (int m0 = 0; m0 < n_mels; m0 += MC) {
+      const int mc = min(MC, n_mels - m0);
+      __syncthreads();  // the clamp complete (first pass); the previous chunk consumed (later ones)
+      for (int idx = tid; idx < n_mfcc * MC; idx += THREADS) {
+        const int i = idx / MC, mm = idx - i * MC;
+        sT[i * (MC + 1) + mm] = mm < mc ? m.dct[(int64_t)i * n_mels + m0 + mm] : 0.0f;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < TASKS; ++j) {
+        const int o = tid + THREADS * j;
+        if (o < tasks) {
+          const int f = o / n_mfcc, i = o - f * n_mfcc;
+          const float* trow = sT + i * (MC + 1);
+          const float* dr = sD + (f0 + f) * n_mels + m0;
+          double a = acc[j];
+          for (int mm = 0; mm < mc; ++mm) a = fma((double)trow[mm], (double)dr[mm], a);
+          acc[j] = a;
+        }
+      }
+    }
+    float* ot = out + (int64_t)f0 * n_mfcc;
+#pragma unroll
+    for (int j = 0; j < TASKS; ++j) {
+      const int o = tid + THREADS * j;
+      if (o < tasks) ot[o] = (float)acc[j];
+    }
+  }
+}
+
+// The streamed MFCC's parameters (include/ddsp_hip.h, ddsp_hip_stream_mfcc's limits), checked before any HIP call;
+// the streaming envelope is the caller's.
+inline int check_stream_mfcc_params(int64_t n_band_weights, int64_t n_mels, int64_t n_mfcc, float top_db) {
+  if (n_band_weights < 0 || n_band_weights > INT32_MAX || !(top_db >= 0.0f)) return DDSP_HIP_EINVAL;
+  if (n_mels < 1 || n_mfcc < 1 || n_mfcc > n_mels) return DDSP_HIP_EINVAL;
+  return n_mels > kMaxMels ? DDSP_HIP_ERANGE : DDSP_HIP_OK;
 }
 
 #define DDSP_FOR_FRAME_LENGTH(L, CALL) \

@@ -11,9 +11,12 @@
 //   y[r, n] = sum_k W[n, k] a[r, k] + b[n]                   (one wave per output row of W)
 // act_s: x' = x * scale + shift; if w1: x'' = w1[c] * x' + b1[c] (c < width; x' is one value per
 // row); if gamma: leaky_relu(layer_norm(x'') * gamma + beta, 0.01) with torch's eps 1e-5 and
-// biased variance.  W rows are streamed once per launch with coalesced loads; each workgroup
-// recomputes the (tiny) activations.  Up to kMaxProblems independent Linears share a launch
-// (blockIdx.y), e.g. the f0 and loudness MLPs, or the harmonic and noise projections.
+// biased variance (plain_norm: the LayerNorm alone, as the encoder's `norm`).  W rows are streamed
+// once per launch with coalesced loads; each workgroup recomputes the (tiny) activations.  Up to
+// kMaxProblems independent Linears share a launch (blockIdx.y), e.g. the f0, loudness and z MLPs,
+// or the harmonic and noise projections.  The W row lives in registers as KL chunks of 64 columns:
+// the kernel is instantiated for 17 (K <= 1088, every decoder shape) and 24 (K <= 1536, the
+// z-conditioned GRU input's 3 x 512) and dispatched on the launch's largest K.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +32,7 @@ constexpr int kOutPerWave = 1;     // output features per wave
 constexpr int kOutPerWG = (kDenseNT / 64) * kOutPerWave;
 constexpr int kMaxRows = 8;
 constexpr int kKL = 17;            // K <= 64 * kKL per lane-strided row (1088: the GRU input's 1024)
+constexpr int kKLWide = 24;        // the wide instantiation (1536: the z-conditioned GRU input's 3 x 512)
 
 struct DenseArgs {
   ddsp_hip_dense_problem p[DDSP_HIP_DENSE_MAX_PROBLEMS];
@@ -49,9 +53,27 @@ __device__ __forceinline__ float wave_sum(float v) {
          __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
 }
 
+// Rows n .. n + kOutPerWave - 1 of P's W, lane-strided, into w (zeros past K; a row past the last repeats it).
+template <int KL>
+__device__ __forceinline__ void load_w_rows(float (&w)[kOutPerWave][KL], const ddsp_hip_dense_problem& P, int n0w,
+                                            int K, int lane) {
+#pragma unroll
+  for (int i = 0; i < kOutPerWave; ++i) {
+    const int n = min(n0w + i, (int)P.out_features - 1);
+    const float* wr = P.weight + (int64_t)n * K;
+#pragma unroll
+    for (int j = 0; j < KL; ++j) {
+      const unsigned k = lane + 64 * j;
+      const float v = wr[min(k, (unsigned)K - 1u)];  // unconditional: every address is valid
+      w[i][j] = k < (unsigned)K ? v : 0.0f;
+    }
+  }
+}
+
 // At 4 rows everything here is latency: every global load a wave needs is issued before the
 // first use (W rows straight into registers at kernel entry, under the activation prologue),
-// and the cross-lane sums avoid ds_bpermute.
+// and the cross-lane sums avoid ds_bpermute.  KL: the 64-column chunks of a W row a lane holds (K <= 64 KL).
+template <int KL>
 __global__ void __launch_bounds__(kDenseNT) dense_rows_kernel(DenseArgs args) {
   extern __shared__ float act[];  // [rows][K]
   const ddsp_hip_dense_problem& P = args.p[blockIdx.y];
@@ -63,22 +85,14 @@ __global__ void __launch_bounds__(kDenseNT) dense_rows_kernel(DenseArgs args) {
   for (int s = 0; s < P.n_inputs; ++s) K += (int)P.inputs[s].width;
 
   // ---- W rows of this wave's outputs into registers ----
-  float wreg[kOutPerWave][kKL];
+  float wreg[kOutPerWave][KL];
   // (loads branch-free: a clamped address and a select; chunk guards j < nK are wave-uniform)
   const int nK = (K + 63) >> 6;
-#pragma unroll
-  for (int i = 0; i < kOutPerWave; ++i) {
-    const int n = min(n0 + wave * kOutPerWave + i, (int)P.out_features - 1);
-    const float* wr = P.weight + (int64_t)n * K;
-#pragma unroll
-    for (int j = 0; j < kKL; ++j) {
-      const unsigned k = lane + 64 * j;
-      const float w = wr[min(k, (unsigned)K - 1u)];  // unconditional: every address is valid
-      wreg[i][j] = k < (unsigned)K ? w : 0.0f;
-    }
-  }
+  // The wide instantiation issues them after the activation prologue instead: its 24 chunks held across the
+  // prologue's v / gamma / beta do not fit the register file.
+  if constexpr (KL <= kKL) load_w_rows<KL>(wreg, P, n0 + wave * kOutPerWave, K, lane);
 
-  // ---- activations: wave w builds (segment, row) pairs w, w+4, ... ----
+  // ---- activations: wave w builds (segment, row) pairs w, w+4, ... (a segment is at most 64 kKL wide) ----
   int col0 = 0;
   for (int s = 0; s < P.n_inputs; ++s) {
     const ddsp_hip_dense_input& in = P.inputs[s];
@@ -128,7 +142,7 @@ __global__ void __launch_bounds__(kDenseNT) dense_rows_kernel(DenseArgs args) {
 #pragma unroll
         for (int j = 0; j < kKL; ++j) {
           const float t = (v[j] - mean) * rstd * gm[j] + bt[j];
-          v[j] = t >= 0.0f ? t : 0.01f * t;
+          v[j] = t >= 0.0f || in.plain_norm ? t : 0.01f * t;
         }
       }
 #pragma unroll
@@ -137,6 +151,7 @@ __global__ void __launch_bounds__(kDenseNT) dense_rows_kernel(DenseArgs args) {
     }
     col0 += width;
   }
+  if constexpr (KL > kKL) load_w_rows<KL>(wreg, P, n0 + wave * kOutPerWave, K, lane);
   __syncthreads();
 
   // ---- GEMV from registers x LDS, then step-major wave sums ----
@@ -146,7 +161,7 @@ __global__ void __launch_bounds__(kDenseNT) dense_rows_kernel(DenseArgs args) {
 #pragma unroll
     for (int r = 0; r < kMaxRows; ++r) acc[i][r] = 0.0f;
 #pragma unroll
-  for (int j = 0; j < kKL; ++j) {
+  for (int j = 0; j < KL; ++j) {
     if (j < nK) {  // wave-uniform; past K the weights are 0 and the activation index is clamped
       const int k = min(lane + 64 * j, K - 1);
 #pragma unroll
@@ -1064,9 +1079,10 @@ int ddsp_hip_dense_rows(const ddsp_hip_dense_problem* problems, int n_problems, 
     args.p[i] = P;
   }
   const size_t shm = sizeof(float) * (size_t)rows * (size_t)max_k;
-  if (max_k > 64 * kKL || max_n > (int64_t)65535 * kOutPerWG) return DDSP_HIP_ERANGE;
+  if (max_k > 64 * kKLWide || max_n > (int64_t)65535 * kOutPerWG) return DDSP_HIP_ERANGE;
   const dim3 grid((unsigned)((max_n + kOutPerWG - 1) / kOutPerWG), (unsigned)n_problems);
-  hipLaunchKernelGGL(dense_rows_kernel, grid, dim3(kDenseNT), shm, reinterpret_cast<hipStream_t>(stream), args);
+  const auto kern = max_k > 64 * kKL ? dense_rows_kernel<kKLWide> : dense_rows_kernel<kKL>;
+  hipLaunchKernelGGL(kern, grid, dim3(kDenseNT), shm, reinterpret_cast<hipStream_t>(stream), args);
   return launch_status();
 }
 

@@ -22,8 +22,8 @@
 //
 // A workgroup transforms kPoints<N> points: 2048 (128 threads, 34 KB of LDS, 2048/N transforms) or, for
 // N = 4096, one transform of 4096 (256 threads, 68 KB: gfx950's LDS is 160 KB per CU).
-// The loudness's reduction over a packed spectrum (loudness_sums) is in analysis_bodies.h, shared with
-// stream_analysis.hip.
+// The loudness's reduction over a packed spectrum (loudness_sums) and the MFCC's pieces (the band tables, the mel
+// rows, the streamed call's body) are in analysis_bodies.h, shared with stream_analysis.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,10 +33,6 @@
 
 namespace ddsp {
 namespace {
-
-constexpr int kMaxMels = 256;  // n_mels cap (the band tables live in LDS)
-constexpr int kDctFrames = 8;  // frames per workgroup of the DCT launch
-constexpr int kDctChunk = 32;  // mel columns of the DCT table staged per pass
 
 // grid (ceil(frames / (2 * kPoints/N)), B), kPoints/16 threads; out[B, frames]
 template <int N>
@@ -57,61 +53,6 @@ __global__ void __launch_bounds__(kPoints<N> / 16) loudness_kernel(const float* 
   float* o = out + (int64_t)b * frames + fa;
   o[0] = (float)(sa / (double)BINS);
   if (fa + 1 < frames) o[1] = (float)(sb / (double)BINS);
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
-  return v;
-}
-
-// The mel rows' band tables into LDS for a workgroup of THREADS threads: s_start / s_count, cut to the spectrum's
-// BINS bins, and s_off, the rows' offsets into band_w (an exclusive scan of the counts; thread tid holds rows
-// RPT tid ..).  The caller's next barrier publishes them.
-template <int THREADS, int BINS>
-__device__ __forceinline__ void stage_bands(const int* __restrict__ band_start, const int* __restrict__ band_count,
-                                            int n_mels, int* s_start, int* s_count, int* s_off, int* s_wave) {
-  constexpr int RPT = kMaxMels / THREADS;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int st[RPT], cnt[RPT], sum = 0;
-#pragma unroll
-  for (int j = 0; j < RPT; ++j) {
-    const int m = RPT * tid + j;
-    st[j] = m < n_mels ? min(max(band_start[m], 0), BINS) : 0;
-    cnt[j] = m < n_mels ? min(max(band_count[m], 0), 1 << 20) : 0;
-    sum += cnt[j];
-  }
-  int v = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  if (lane == 63) s_wave[wid] = v;
-  __syncthreads();
-  int off = v - sum;
-  for (int i = 0; i < wid; ++i) off += s_wave[i];
-#pragma unroll
-  for (int j = 0; j < RPT; ++j) {
-    const int m = RPT * tid + j;
-    s_off[m] = off;
-    s_start[m] = st[j];
-    s_count[m] = min(cnt[j], BINS - st[j]);
-    off += cnt[j];
-  }
-}
-
-// Mel row m of the two packed frames whose powers are in lds: (10 log10(max(1e-10, energy_a)), the same of b).
-__device__ __forceinline__ float2 mel_db_pair(const double2* lds, const float* __restrict__ band_w, int n_w, int s0,
-                                              int c, int off) {
-  double ea = 0.0, eb = 0.0;
-  for (int j = 0; j < c; ++j) {
-    const double wj = off + j < n_w ? (double)band_w[off + j] : 0.0;
-    const double2 p = lds[lds_idx(s0 + j)];
-    ea = fma(wj, p.x, ea);
-    eb = fma(wj, p.y, eb);
-  }
-  return make_float2(10.0f * log10f(fmaxf(1e-10f, (float)ea)), 10.0f * log10f(fmaxf(1e-10f, (float)eb)));
 }
 
 // MFCC launch (a).  grid (ceil(frames / (2 * kPoints/N)), B), kPoints/16 threads.  Mel row m is the band
@@ -257,122 +198,31 @@ __global__ void __launch_bounds__(kPoints<N> / 16) stream_loudness_kernel(const 
   if (fa + 1 < frames) o[1] = (float)(sb / (double)BINS);
 }
 
-// One pass of the MFCC's loop: frames fa and fa + 1 of the call through the packed transform, then both frames'
-// power over the spectrum in place (the thread that owns the pair {k, N-k} writes slot k; no other thread reads k
-// or N-k), published by the closing barrier.  Kept out of line on purpose: inlined into the caller's loop over
-// passes, this code came out of the compiler wrong on gfx950 for every n_fft whose last FFT stage is not radix-2
-// (bin 0 exact, every other bin off by decibels; the same source as a function, or with the loop removed, is
-// exact).  The cause in the compiler was not found; tests/test_gpu_stream_features.py covers every size.
-template <int N>
-__device__ __noinline__ void spectrum_power_pass(const StreamFetch& fetch, int fa, int t, double2* lds) {
-  constexpr int Q = N / 16, BINS = N / 2 + 1;
-  packed_spectrum<N>(fetch, fa, t, lds);
-  for (int k = t; k < BINS; k += Q) lds[lds_idx(k)] = packed_power<N>(lds, k);
-  __syncthreads();
-}
-
-// The MFCC of one call in one launch: grid (B), kPoints/16 threads, one workgroup per item.  It loops over the
-// call's frame pairs (kPoints/N transforms per pass) as mel_db_kernel does, keeping D[frames, n_mels] in LDS; folds
-// the call's largest D with the item's carried maximum runmax[b] (taken as absent when the counter is 0, whatever
-// the stored bits) and stores the result; clamps D at that maximum - top_db; and applies the DCT out of LDS as
-// mfcc_dct_kernel does (kDctFrames frames per round, the table staged kDctChunk columns at a time in the
-// transforms' LDS, m ascending, fp64 accumulator).  A second run before the advance folds the same call into a
-// maximum that already holds it: the same bits.
+// The MFCC of one call in one launch: grid (B), kPoints/16 threads, one workgroup per item running
+// stream_mfcc_body (analysis_bodies.h) with the item's carried maximum runmax[b], taken as absent when the counter
+// is 0.
 template <int N>
 __global__ void __launch_bounds__(kPoints<N> / 16) stream_mfcc_kernel(
     const float* __restrict__ x, const int* __restrict__ band_start, const int* __restrict__ band_count,
     const float* __restrict__ band_w, int n_w, const float* __restrict__ dct, float* __restrict__ out,
     const uint64_t* __restrict__ counter, float* ring, float* runmax, int n, int len, int hs, int hop, int frames,
     int n_mels, int n_mfcc, float top_db) {
-  constexpr int Q = N / 16, THREADS = kPoints<N> / 16, TPW = kPoints<N> / N, BINS = N / 2 + 1;
-  constexpr int WAVES = THREADS / 64, FR = kDctFrames, MC = kDctChunk;
-  constexpr int TASKS = FR * kMaxMels / THREADS;  // DCT outputs per thread and round
+  constexpr int THREADS = kPoints<N> / 16, TPW = kPoints<N> / N, WAVES = THREADS / 64;
   __shared__ double2 lds_all[TPW * (N + N / 16)];
   __shared__ float sD[kStreamMaxFrames * kMaxMels];
   __shared__ int s_start[kMaxMels], s_count[kMaxMels], s_off[kMaxMels];
   __shared__ int s_wave[WAVES];
   __shared__ float s_max[WAVES];
   __shared__ float s_floor;
-  static_assert(sizeof(double2) * TPW * (N + N / 16) >= sizeof(float) * kMaxMels * (MC + 1), "the DCT table's LDS");
-  float* sT = reinterpret_cast<float*>(lds_all);
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  stage_bands<THREADS, BINS>(band_start, band_count, n_mels, s_start, s_count, s_off, s_wave);
-  const int tr = tid / Q, t = tid - tr * Q;
-  double2* lds = lds_all + tr * (N + N / 16);
   const int b = blockIdx.x;
   const uint64_t k = *counter;
   const StreamCall call{k, n, len, hs, hop, frames};
   float* rb = ring + (int64_t)b * len;
   const float* xb = x + (int64_t)b * n;
-  call.store(rb, xb, tid, THREADS);
-  const StreamFetch fetch = call.fetch(rb, xb);
-  float mx = -INFINITY;
-  for (int f0 = 0; f0 < frames; f0 += 2 * TPW) {
-    const int fa = f0 + 2 * tr;
-    spectrum_power_pass<N>(fetch, fa, t, lds);  // (its barriers publish s_*)
-    const bool va = fa < frames, vb = fa + 1 < frames;
-    float* Da = sD + (va ? fa : 0) * n_mels;
-    for (int m = t; m < n_mels; m += Q) {
-      const float2 d = mel_db_pair(lds, band_w, n_w, s_start[m], s_count[m], s_off[m]);
-      if (va) {
-        Da[m] = d.x;
-        mx = fmaxf(mx, d.x);
-      }
-      if (vb) {
-        Da[n_mels + m] = d.y;
-        mx = fmaxf(mx, d.y);
-      }
-    }
-    __syncthreads();  // the powers consumed before the next pass (or the DCT table) overwrites them
-  }
-  mx = wave_max(mx);
-  if (lane == 0) s_max[wid] = mx;
-  __syncthreads();
-  if (tid == 0) {
-    float r = s_max[0];
-#pragma unroll
-    for (int i = 1; i < WAVES; ++i) r = fmaxf(r, s_max[i]);
-    if (k != 0) r = fmaxf(r, runmax[b]);
-    runmax[b] = r;
-    s_floor = r - top_db;
-  }
-  __syncthreads();
-  const float floor_db = s_floor;
-  for (int i = tid; i < frames * n_mels; i += THREADS) sD[i] = fmaxf(sD[i], floor_db);
-  for (int f0 = 0; f0 < frames; f0 += FR) {
-    const int nf = min(FR, frames - f0);
-    const int tasks = nf * n_mfcc;  // task o = f * n_mfcc + i, <= THREADS * TASKS
-    double acc[TASKS];
-#pragma unroll
-    for (int j = 0; j < TASKS; ++j) acc[j] = 0.0;
-    for (int m0 = 0; m0 < n_mels; m0 += MC) {
-      const int mc = min(MC, n_mels - m0);
-      __syncthreads();  // the clamp complete (first pass); the previous chunk consumed (later ones)
-      for (int idx = tid; idx < n_mfcc * MC; idx += THREADS) {
-        const int i = idx / MC, mm = idx - i * MC;
-        sT[i * (MC + 1) + mm] = mm < mc ? dct[(int64_t)i * n_mels + m0 + mm] : 0.0f;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int j = 0; j < TASKS; ++j) {
-        const int o = tid + THREADS * j;
-        if (o < tasks) {
-          const int f = o / n_mfcc, i = o - f * n_mfcc;
-          const float* trow = sT + i * (MC + 1);
-          const float* dr = sD + (f0 + f) * n_mels + m0;
-          double a = acc[j];
-          for (int mm = 0; mm < mc; ++mm) a = fma((double)trow[mm], (double)dr[mm], a);
-          acc[j] = a;
-        }
-      }
-    }
-    float* ot = out + ((int64_t)b * frames + f0) * n_mfcc;
-#pragma unroll
-    for (int j = 0; j < TASKS; ++j) {
-      const int o = tid + THREADS * j;
-      if (o < tasks) ot[o] = (float)acc[j];
-    }
-  }
+  call.store(rb, xb, threadIdx.x, THREADS);
+  stream_mfcc_body<N>(call.fetch(rb, xb), k != 0, lds_all, MfccLds{sD, s_start, s_count, s_off, s_wave, s_max, &s_floor},
+                      MfccTables{band_start, band_count, band_w, n_w, dct, n_mels, n_mfcc, top_db}, runmax + b,
+                      out + (int64_t)b * frames * n_mfcc);
 }
 
 // The envelope both features share (include/ddsp_hip.h), checked before any HIP call.
@@ -440,15 +290,6 @@ int stream_loudness_launch(const StreamArgs& a, const float* w, float* out) {
                      0, S(a.stream), a.x, w, out, a.counter, a.ring, a.n, a.len, a.hs, a.hop, a.frames);
   return launch_status();
 }
-
-struct MfccTables {
-  const int *start, *count;
-  const float* w;
-  int n_w;
-  const float* dct;
-  int n_mels, n_mfcc;
-  float top_db;
-};
 
 template <int N>
 int stream_mfcc_launch(const StreamArgs& a, const MfccTables& m, float* runmax, float* out) {

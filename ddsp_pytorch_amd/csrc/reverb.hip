@@ -279,6 +279,6 @@ const char* ddsp_hip_status_string(int status) {
   }
 }
 
-int ddsp_hip_version(void) { return 107; }
+int ddsp_hip_version(void) { return 108; }
 
 }  // extern "C"

@@ -10,7 +10,7 @@
 // pitch.hip's and features.hip's kernels (analysis_bodies.h), so the bits are the separate launches'.  The role branch
 // is uniform per workgroup and there is no loop over passes.  Every workgroup copies its strided share of the call
 // into the ring; no workgroup reads what another writes (analysis_frames.h), whatever its role.  One lds_all serves
-// both roles.
+// both roles.  (stream_analysis_mfcc.hip adds the streamed MFCC of the same frames as a third role.)
 #include <hip/hip_runtime.h>
 
 #include "analysis_bodies.h"

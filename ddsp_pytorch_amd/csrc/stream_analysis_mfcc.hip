@@ -1,0 +1,146 @@
+// The streamed loudness, the streamed MFCC and (on request) the streamed YIN pitch of one call in ONE launch over ONE
+// state, on ONE time axis (include/ddsp_hip.h, ddsp_hip_stream_analysis_mfcc): what a z-conditioned model (the
+// reference's ddsp/models/encoder.py autoencoder) needs per call of a realtime stream.  stream_analysis.hip's grid with
+// one more workgroup per item, which runs the streamed MFCC's per-call code (analysis_bodies.h: features.hip's
+// stream_mfcc_kernel is the same body) over the same ring.  A translation unit of its own, so that
+// stream_analysis.hip's object stays what it was.
+#include <hip/hip_runtime.h>
+
+#include "analysis_bodies.h"
+
+namespace ddsp {
+namespace {
+
+// grid (pitch_blocks + frame_blocks + 1, B), kPoints<N>/16 threads.  Per item the pitch and the loudness workgroups are
+// stream_analysis_kernel's (the same bodies, so the same bits); the item's last workgroup runs
+// stream_mfcc_body<M> over the same ring with each frame's M-sample window centred in the frame's L-sample window
+// (the fetch's rel0 moved by (L - M)/2, still inside [-hs, n)), so slot j of all three features is the same stream
+// frame.  pblocks == 0: no pitch role.  kPoints<L> == kPoints<M> == 2048: one workgroup shape and one lds_all for
+// the three roles; the MFCC's D and band tables come on top of it (nothing is aliased).
+template <int N, int M>
+__global__ void __launch_bounds__(kPoints<N> / 16) stream_analysis_mfcc_kernel(
+    const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ loud,
+    const uint64_t* __restrict__ counter, float* ring, float* runmax, int n, int len, int hs, int hop, int frames,
+    int pblocks, PitchParams p, float* __restrict__ f0, float* __restrict__ conf, int32_t* __restrict__ period,
+    MfccTables m, float* __restrict__ mfcc) {
+  constexpr int Q = N / 16, TPW = kPoints<N> / N, BINS = N / 2 + 1, WAVES = kPoints<N> / 1024;
+  static_assert(kPoints<N> == 2048 && kPoints<M> == 2048 && (M == N || 2 * M == N), "one workgroup shape");
+  __shared__ double2 lds_all[TPW * (N + N / 16)];
+  __shared__ double red[8];
+  __shared__ int rint[8];
+  __shared__ float sD[kStreamMaxFrames * kMaxMels];
+  __shared__ int s_start[kMaxMels], s_count[kMaxMels], s_off[kMaxMels];
+  __shared__ int s_wave[WAVES];
+  __shared__ float s_max[WAVES];
+  __shared__ float s_floor;
+  const int b = blockIdx.y;
+  const uint64_t k = *counter;
+  const StreamCall call{k, n, len, hs, hop, frames};
+  float* rb = ring + (int64_t)b * len;
+  const float* xb = x + (int64_t)b * n;
+  call.store(rb, xb, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  if (blockIdx.x == gridDim.x - 1) {
+    StreamFetch fetch = call.fetch(rb, xb);
+    fetch.rel0 += (N - M) / 2;
+    stream_mfcc_body<M>(fetch, k != 0, lds_all, MfccLds{sD, s_start, s_count, s_off, s_wave, s_max, &s_floor}, m,
+                        runmax + b, mfcc + (int64_t)b * frames * m.n_mfcc);
+    return;
+  }
+  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;
+  double2* lds = lds_all + tr * (N + N / 16);
+  if ((int)blockIdx.x < pblocks) {
+    const int j = blockIdx.x * TPW + tr;
+    yin_frame<N>(call.fetch(rb, xb), j, t, lds, red, rint, p, j < frames, (int64_t)b * frames + j, f0, conf, period);
+    return;
+  }
+  const int fa = 2 * ((blockIdx.x - pblocks) * TPW + tr);
+  packed_spectrum<N>(call.fetch(rb, xb), fa, t, lds);
+  double sa, sb;
+  loudness_sums<N>(lds, w, t, tr, red, sa, sb);
+  if (t != 0 || fa >= frames) return;
+  float* o = loud + (int64_t)b * frames + fa;
+  o[0] = (float)(sa / (double)BINS);
+  if (fa + 1 < frames) o[1] = (float)(sb / (double)BINS);
+}
+
+struct AnalysisMfccArgs {
+  const float* w;
+  float* loud;
+  PitchParams p;
+  float *f0, *conf;
+  int32_t* period;
+  MfccTables m;
+  float *runmax, *mfcc;
+};
+
+template <int N, int M>
+int stream_analysis_mfcc_launch(const StreamArgs& a, const AnalysisMfccArgs& g) {
+  const unsigned pb = g.f0 ? pitch_blocks(N, a.frames) : 0u;
+  hipLaunchKernelGGL((stream_analysis_mfcc_kernel<N, M>), dim3(pb + frame_blocks(N, a.frames) + 1, (unsigned)a.B),
+                     dim3(kPoints<N> / 16), 0, S(a.stream), a.x, g.w, g.loud, a.counter, a.ring, g.runmax, a.n, a.len,
+                     a.hs, a.hop, a.frames, (int)pb, g.p, g.f0, g.conf, g.period, g.m, g.mfcc);
+  return launch_status();
+}
+
+int stream_analysis_mfcc_dispatch(const StreamArgs& a, int64_t L, bool half, const AnalysisMfccArgs& g) {
+#define DDSP_CALL(N) \
+  (half ? stream_analysis_mfcc_launch<N, N / 2>(a, g) : stream_analysis_mfcc_launch<N, N>(a, g))
+  switch (L) {
+    case 64: return DDSP_CALL(64);
+    case 128: return DDSP_CALL(128);
+    case 256: return DDSP_CALL(256);
+    case 512: return DDSP_CALL(512);
+    case 1024: return DDSP_CALL(1024);
+    default: return DDSP_CALL(2048);
+  }
+#undef DDSP_CALL
+}
+
+}  // namespace
+}  // namespace ddsp
+
+using namespace ddsp;
+
+extern "C" {
+
+int ddsp_hip_stream_analysis_mfcc(const float* x, const float* weights, float* loudness_out, const int32_t* band_start,
+                                  const int32_t* band_count, const float* band_weights, int64_t n_band_weights,
+                                  const float* dct, float* mfcc_out, float* f0, float* confidence, int32_t* period,
+                                  const uint64_t* counter, void* state, size_t state_bytes, int64_t batch,
+                                  int64_t call_samples, int64_t frame_length, int64_t mfcc_n_fft, int64_t hop,
+                                  int64_t n_mels, int64_t n_mfcc, float top_db, int64_t tau_min, int64_t tau_max,
+                                  float sample_rate, float threshold, void* stream) {
+  StreamSizes sz;
+  int st = check_stream_features(batch, call_samples, frame_length, hop, &sz);
+  if (st) return st;
+  if (frame_length < kPitchMinFrame || frame_length > 2048) return DDSP_HIP_ERANGE;
+  if (f0) {
+    st = check_pitch_params(frame_length, tau_min, tau_max, sample_rate);
+    if (st) return st;
+  } else if (confidence || period) {
+    return DDSP_HIP_EINVAL;
+  }
+  if (mfcc_n_fft != frame_length && 2 * mfcc_n_fft != frame_length) return DDSP_HIP_ERANGE;
+  st = check_stream_mfcc_params(n_band_weights, n_mels, n_mfcc, top_db);
+  if (st) return st;
+  if (batch == 0) return DDSP_HIP_OK;
+  if (!x || !loudness_out || !band_start || !band_count || !band_weights || !dct || !mfcc_out || !counter || !state)
+    return DDSP_HIP_EINVAL;
+  if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
+  float* ring = reinterpret_cast<float*>(state);
+  const StreamArgs a{x, counter, ring, batch, (int)call_samples, (int)sz.len, (int)sz.hs, (int)hop, (int)sz.frames,
+                     stream};
+  const AnalysisMfccArgs g{weights,
+                           loudness_out,
+                           PitchParams{(int)tau_min, (int)tau_max, sample_rate, threshold},
+                           f0,
+                           confidence,
+                           period,
+                           MfccTables{band_start, band_count, band_weights, (int)n_band_weights, dct, (int)n_mels,
+                                      (int)n_mfcc, top_db},
+                           ring + (size_t)batch * (size_t)sz.len,
+                           mfcc_out};
+  return stream_analysis_mfcc_dispatch(a, frame_length, mfcc_n_fft != frame_length, g);
+}
+
+}  // extern "C"

@@ -567,6 +567,49 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> analysis_stream(
   return {loud, f0, conf, period};
 }
 
+// loudness_stream + mfcc_stream (+ pitch_stream) in one launch over one state, on one time axis
+// (ddsp_hip_stream_analysis_mfcc) -> (loudness, mfcc, f0, confidence, period); pitch == false: the last three empty
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> analysis_mfcc_stream(
+    const at::Tensor& x, const std::optional<at::Tensor>& weights, const at::Tensor& band_start,
+    const at::Tensor& band_count, const at::Tensor& band_weights, const at::Tensor& dct, int64_t frame_length,
+    int64_t mfcc_n_fft, int64_t hop, double top_db, bool pitch, int64_t tau_min, int64_t tau_max, double sample_rate,
+    double threshold, const at::Tensor& counter, at::Tensor& state) {
+  at::Tensor xc = call_rows(x, "analysis_mfcc_stream");
+  check_stream(counter, state, xc);
+  check_dev(band_weights, "band_weights");
+  check_dev(dct, "dct");
+  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "analysis_mfcc_stream: call_samples must be a multiple of hop");
+  TORCH_CHECK(dct.dim() == 2, "analysis_mfcc_stream: dct [n_mfcc, n_mels] expected");
+  const int64_t B = xc.size(0), N = xc.size(1), n_mfcc = dct.size(0), n_mels = dct.size(1);
+  for (const at::Tensor* t : {&band_start, &band_count})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->numel() == n_mels,
+                "analysis_mfcc_stream: band_start and band_count must be int32 HIP tensors of n_mels values");
+  at::Tensor w;
+  if (weights.has_value() && weights->defined()) {
+    check_dev(*weights, "weights");
+    TORCH_CHECK(weights->numel() == frame_length / 2 + 1,
+                "analysis_mfcc_stream: weights must hold frame_length/2+1 values");
+    w = weights->contiguous();
+  }
+  at::Tensor bs = band_start.contiguous(), bc = band_count.contiguous(), bw = band_weights.contiguous(),
+             d = dct.contiguous();
+  const int64_t R = N / hop, Rp = pitch ? R : 0;
+  at::Tensor loud = at::empty({B, R}, xc.options());
+  at::Tensor out = at::empty({B, R, n_mfcc}, xc.options());
+  at::Tensor f0 = at::empty({B, Rp}, xc.options());
+  at::Tensor conf = at::empty_like(f0);
+  at::Tensor period = at::empty({B, Rp}, xc.options().dtype(at::kInt));
+  ok(ddsp_hip_stream_analysis_mfcc(
+         xc.data_ptr<float>(), w.defined() ? w.data_ptr<float>() : nullptr, loud.data_ptr<float>(),
+         bs.data_ptr<int32_t>(), bc.data_ptr<int32_t>(), bw.data_ptr<float>(), bw.numel(), d.data_ptr<float>(),
+         out.data_ptr<float>(), pitch ? f0.data_ptr<float>() : nullptr, pitch ? conf.data_ptr<float>() : nullptr,
+         pitch ? period.data_ptr<int32_t>() : nullptr, reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()),
+         state.data_ptr(), (size_t)state.numel(), B, N, frame_length, mfcc_n_fft, hop, n_mels, n_mfcc, (float)top_db,
+         tau_min, tau_max, (float)sample_rate, (float)threshold, stream_of(xc)),
+     "stream_analysis_mfcc");
+  return {loud, out, f0, conf, period};
+}
+
 }  // namespace
 
 // ---------------- decoder.py:33-68: the GRU recurrence ----------------
@@ -634,6 +677,10 @@ TORCH_LIBRARY(ddsp_hip, m) {
         " float threshold, Tensor counter, Tensor(a!) state) -> (Tensor, Tensor, Tensor)");
   m.def("analysis_stream(Tensor x, Tensor? weights, int frame_length, int hop, int tau_min, int tau_max,"
         " float sample_rate, float threshold, Tensor counter, Tensor(a!) state) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("analysis_mfcc_stream(Tensor x, Tensor? weights, Tensor band_start, Tensor band_count, Tensor band_weights,"
+        " Tensor dct, int frame_length, int mfcc_n_fft, int hop, float top_db, bool pitch, int tau_min, int tau_max,"
+        " float sample_rate, float threshold, Tensor counter, Tensor(a!) state)"
+        " -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA key on ROCm
@@ -664,4 +711,5 @@ TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA 
   m.impl("pitch", &pitch);
   m.impl("pitch_stream", &pitch_stream);
   m.impl("analysis_stream", &analysis_stream);
+  m.impl("analysis_mfcc_stream", &analysis_mfcc_stream);
 }

@@ -9,8 +9,9 @@ can be passed in as before, and without one ``analyze`` computes f0 on the devic
 (``core.extract_pitch``: csrc/pitch.hip) — a classical tracker, not CREPE.
 
 ``StreamAnalyzer`` is the same front end for a realtime stream: audio comes in call by call and each call returns
-the frames it completes (``core.stream_loudness``, ``core.stream_mfcc`` and, on request, ``core.stream_pitch``),
-the history carried on the device.
+the frames it completes (``core.stream_loudness``, ``core.stream_mfcc`` and, on request, ``core.stream_pitch``;
+``aligned=True``: all of them from one launch on one time axis, ``core.stream_analysis_mfcc``), the history
+carried on the device.
 """
 import torch
 
@@ -58,7 +59,11 @@ class StreamAnalyzer:
     feature lags by ``delay_frames[name]`` frames (loudness: n_fft 2048, MFCC: n_fft 1024 as in ``analyze``; pitch:
     2048, so it lags exactly as the loudness does).  ``fused=True`` (needs ``pitch=True``): the loudness and the
     pitch come from ONE launch over ONE state (``core.stream_analysis``; ``pitch_state is loudness_state``), the
-    same bits with one launch and one ring less.  The MFCC's top_db clamp is causal (``core.stream_mfcc``).
+    same bits with one launch and one ring less.  ``aligned=True`` (with or without ``pitch``): every feature comes
+    from ONE launch over ONE state (``core.stream_analysis_mfcc``; ``mfcc_state is loudness_state``, and
+    ``pitch_state`` too), the MFCC window centred in the loudness's, so that ``delay_frames['mfcc'] ==
+    delay_frames['loudness']`` — what a model that consumes all three per frame needs.  The MFCC's top_db clamp is
+    causal (``core.stream_mfcc``).
     ``mean_loudness`` / ``std_loudness`` as in ``analyze``.  After one warm-up call (the tables) nothing
     synchronises with the host: a call can be captured in a HIP graph over a static input buffer.  ``counter``: a
     stream counter to share (e.g. a ``core.StreamState``'s), with ``advance=False`` when that stream's own advance
@@ -67,7 +72,8 @@ class StreamAnalyzer:
     N_FFT = {"loudness": 2048, "mfcc": 1024, "pitch": 2048}
 
     def __init__(self, sample_rate, block_size, call_samples, batch=1, device="cuda", mean_loudness=None,
-                 std_loudness=None, counter=None, advance=True, pitch=False, fmin=50.0, fmax=2000.0, fused=False):
+                 std_loudness=None, counter=None, advance=True, pitch=False, fmin=50.0, fmax=2000.0, fused=False,
+                 aligned=False):
         if (mean_loudness is None) != (std_loudness is None):
             raise ValueError("StreamAnalyzer: mean_loudness and std_loudness go together")
         if fused and not pitch:
@@ -79,17 +85,22 @@ class StreamAnalyzer:
         self.loudness_state = core.FeatureStreamState(batch, device, call_samples, self.N_FFT["loudness"], block_size,
                                                       counter=counter)
         self.counter = self.loudness_state.counter
-        self.mfcc_state = core.FeatureStreamState(batch, device, call_samples, self.N_FFT["mfcc"], block_size,
-                                                  counter=self.counter)
+        self.aligned = bool(aligned)
+        if self.aligned:  # one ring for every feature, the MFCC's window centred in the loudness's
+            self.mfcc_state = self.loudness_state
+        else:
+            self.mfcc_state = core.FeatureStreamState(batch, device, call_samples, self.N_FFT["mfcc"], block_size,
+                                                      counter=self.counter)
         self.delay_frames = {"loudness": self.loudness_state.delay_frames, "mfcc": self.mfcc_state.delay_frames}
         self.pitch, self.fmin, self.fmax = bool(pitch), float(fmin), float(fmax)
-        self.fused = bool(fused)
+        self.fused = bool(fused) or (self.aligned and self.pitch)
         self.pitch_state = None
         if self.pitch:
             core.pitch_lags(sample_rate, fmin, fmax, self.N_FFT["pitch"])  # a bad range is refused here
             if self.fused:  # one ring for both: the same frames of the same samples
                 if self.N_FFT["pitch"] != self.N_FFT["loudness"]:
-                    raise RuntimeError("StreamAnalyzer: fused=True needs one frame length for loudness and pitch")
+                    raise RuntimeError("StreamAnalyzer: fused=True and aligned=True need one frame length for "
+                                       "loudness and pitch")
                 self.pitch_state = self.loudness_state
             else:
                 self.pitch_state = core.FeatureStreamState(batch, device, call_samples, self.N_FFT["pitch"],
@@ -99,14 +110,23 @@ class StreamAnalyzer:
 
     def reset(self):
         self.loudness_state.reset()
-        self.mfcc_state.reset()
+        if self.mfcc_state is not self.loudness_state:
+            self.mfcc_state.reset()
         if self.pitch_state is not None and self.pitch_state is not self.loudness_state:
             self.pitch_state.reset()
 
     @torch.no_grad()
     def __call__(self, audio):
-        f0 = conf = None
-        if self.fused:
+        f0 = conf = mfcc = None
+        if self.aligned:
+            got = core.stream_analysis_mfcc(audio, self.sample_rate, self.block_size, self.loudness_state,
+                                            pitch=self.pitch, fmin=self.fmin, fmax=self.fmax,
+                                            frame_length=self.N_FFT["loudness"], return_confidence=self.pitch,
+                                            mfcc_n_fft=self.N_FFT["mfcc"])
+            loudness, mfcc = got[:2]
+            if self.pitch:
+                f0, conf = got[2:]
+        elif self.fused:
             loudness, f0, conf = core.stream_analysis(audio, self.sample_rate, self.block_size, self.loudness_state,
                                                       fmin=self.fmin, fmax=self.fmax,
                                                       frame_length=self.N_FFT["loudness"], return_confidence=True)
@@ -115,7 +135,9 @@ class StreamAnalyzer:
                                             n_fft=self.N_FFT["loudness"])
         if self.mean_loudness is not None:
             loudness = (loudness - self.mean_loudness) / self.std_loudness
-        mfcc = core.stream_mfcc(audio, self.sample_rate, self.block_size, self.mfcc_state, n_fft=self.N_FFT["mfcc"])
+        if mfcc is None:
+            mfcc = core.stream_mfcc(audio, self.sample_rate, self.block_size, self.mfcc_state,
+                                    n_fft=self.N_FFT["mfcc"])
         out = {"loudness": loudness.unsqueeze(-1), "mfcc": mfcc}
         if self.pitch:
             if not self.fused:

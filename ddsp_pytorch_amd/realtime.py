@@ -33,6 +33,12 @@ audio, and the graph computes the loudness from it (`ddsp_hip_stream_loudness`, 
 the normalisation and the control network.  ``pitch_from_audio=True`` on top of it makes the audio the only input:
 that launch becomes `ddsp_hip_stream_analysis`, which computes the loudness and the YIN f0 of the same frames side by
 side over the same ring, and the f0 drives the control network and the synthesis — audio in, audio out.
+
+A ``DDSPAutoencoder`` (the reference's z-conditioned model, ``ddsp/models/encoder.py``) runs the same way, from audio
+alone: the analysis launch becomes `ddsp_hip_stream_analysis_mfcc`, which adds the streamed MFCC of the same frames
+(its 1024-sample window centred in the loudness's 2048, so z, f0 and loudness of one frame describe one instant),
+the MFCC encoder runs with its GRU state carried from call to call in ``encoder_state``, and z joins the decoder
+GRU's input through ``z_mlp``.
 """
 from collections import namedtuple
 
@@ -46,7 +52,8 @@ _Linear = namedtuple("_Linear", "weight bias in_features out_features")
 
 class RealtimeGraph:
     """Graph-replayed realtime forward of a `DDSPDecoder` (the ScriptDDSP realtime model of
-    export.py:23-40: `forward(pitch[1,N,1], loudness[1,N,1]) -> audio[1,N,1]`).
+    export.py:23-40: `forward(pitch[1,N,1], loudness[1,N,1]) -> audio[1,N,1]`) or, from audio, of a
+    `DDSPAutoencoder` (last paragraph).
 
     The model's `decoder.cache_gru` is the stream state (updated in place by every call, as in
     decoder.py:56-60); `reset()` zeroes it and rewinds the noise counter.  The returned tensor
@@ -75,7 +82,24 @@ class RealtimeGraph:
     the synthesis; it lags as the loudness does (`pitch_delay_samples == loudness_delay_samples`).  `self.f0` and
     `self.confidence` are static [1, R] device buffers holding the last call's values, for the host to monitor or
     gate on.  Nothing holds or smooths f0: an unvoiced or silent frame carries YIN's value as it is (a silent frame
-    gives sample_rate / tau_min with confidence 0), and the instrument is then as quiet as its loudness says."""
+    gives sample_rate / tau_min with confidence 0), and the instrument is then as quiet as its loudness says.
+
+    A ``DDSPAutoencoder`` (recognised by ``model.decoder.add_z`` and ``model.encoder``) needs
+    ``loudness_from_audio=True``: its encoder's MFCC can only come from audio.  With ``pitch_from_audio=True``
+    ``__call__(audio)`` is audio in, audio out; without it ``__call__(pitch, audio)``; ``continuous`` / ``reverb`` as for
+    the decoder.  The graph runs `core.stream_analysis_mfcc` on the one analysis state (the loudness, the MFCC and,
+    from audio, the pitch in one launch; `mfcc_delay_samples == loudness_delay_samples`), then the encoder — ``norm``,
+    the GRU with a carried state, ``proj`` — and the decoder with z.  ``encoder_state`` [1, 1, hidden] is the encoder
+    GRU's state between calls: a buffer of this object (the model's state_dict stays the reference's), zero at the
+    start and after `reset()`.  ``z`` is a static [1, R, 16] device buffer with the last call's values.
+    ``fused=True`` runs all of it on `ddsp_hip_dense_rows` and the GRU step kernels (the encoder's GRU always on the
+    step kernels, the decoder's by ``gru_route``): 3 dense launches and R encoder steps more than the decoder's graph —
+    the encoder GRU's input projection (with ``norm`` folded in as a LayerNorm without activation), ``proj``, and
+    ``z_mlp``'s first Linear; ``z_mlp``'s other two blocks ride in ``f0_mlp``'s and ``loudness_mlp``'s launches as a
+    third problem, and the decoder GRU's input projection takes three segments (K = 3 hidden, up to 1536).
+    ``fused=False`` replays the package's eager kernels (``model.encoder.norm``, `core.gru` with the carried state,
+    ``model.encoder.proj``, `gru_decoder_forward` with z).  The capture stays on one stream: the encoder chain is not
+    forked beside the f0 / loudness MLPs."""
 
     def __init__(self, model, call_samples=1024, mean_loudness=0.0, std_loudness=1.0,
                  seed=0x5EEDDD5B, device=None, warmup=3, fused=True, gru_route="steps",
@@ -91,6 +115,10 @@ class RealtimeGraph:
         if not core.synth_frames_in_envelope(model.harmonic_proj.out_features - 1,
                                              model.noise_proj.out_features, bs, 1):
             raise RuntimeError("RealtimeGraph: model shape outside the fused synthesis kernel's envelope")
+        self.autoencoder = bool(getattr(model.decoder, "add_z", False)) and hasattr(model, "encoder")
+        if self.autoencoder and not loudness_from_audio:
+            raise RuntimeError("RealtimeGraph: a DDSPAutoencoder needs loudness_from_audio=True (its encoder's MFCC can "
+                               "only come from audio)")
         self.model = model
         self.device = device
         self.block_size = bs
@@ -136,6 +164,11 @@ class RealtimeGraph:
                                    "computes both from the same frames of the same ring)")
             core.pitch_lags(self.sample_rate, self.pitch_fmin, self.pitch_fmax, self.analysis.n_fft)  # a bad range
             self.pitch_delay_samples = self.loudness_delay_samples
+        self.mfcc_delay_samples = 0
+        self.z = self.mfcc = self.encoder_state = None
+        if self.autoencoder:  # the encoder GRU's carried state is this object's: the model's state_dict stays as it is
+            self.mfcc_delay_samples = self.loudness_delay_samples
+            self.encoder_state = torch.zeros(1, 1, model.encoder.gru.hidden_size, device=device)
         self._inp_h = torch.zeros(2, N, 1).pin_memory()
         self._out_h = torch.zeros(1, N, 1).pin_memory()
         self.fused = bool(fused)
@@ -157,6 +190,8 @@ class RealtimeGraph:
             self.out = self._forward()
         torch.cuda.synchronize(device)
         model.decoder.cache_gru.copy_(cache0)
+        if self.encoder_state is not None:
+            self.encoder_state.zero_()
         self.counter.zero_()
         if self.stream is not None:
             self.stream.reset()
@@ -193,6 +228,17 @@ class RealtimeGraph:
         and the call's f0 and confidence stay in ``self.f0`` / ``self.confidence``."""
         if not self.loudness_from_audio:
             return self.pitch, self.block_size, self.loudness, self.block_size
+        if self.autoencoder:  # one launch, one ring, one time axis: the loudness, the MFCC and (from audio) the pitch
+            got = core.stream_analysis_mfcc(
+                self.loudness, self.sample_rate, self.block_size, self.analysis, pitch=self.pitch_from_audio,
+                fmin=self.pitch_fmin, fmax=self.pitch_fmax, frame_length=self.analysis.n_fft,
+                threshold=self.pitch_threshold, return_confidence=self.pitch_from_audio,
+                n_mfcc=self.model.encoder.gru.input_size)
+            loud, self.mfcc = got[:2]
+            if not self.pitch_from_audio:
+                return self.pitch, self.block_size, loud, 1
+            self.f0, self.confidence = got[2:]
+            return self.f0, 1, loud, 1
         if not self.pitch_from_audio:
             loud = core.stream_loudness(self.loudness, self.sample_rate, self.block_size, self.analysis)
             return self.pitch, self.block_size, loud, 1
@@ -207,7 +253,7 @@ class RealtimeGraph:
         d = m.decoder
         if not core.gru_supported(d.gru):
             raise RuntimeError("RealtimeGraph(fused=True): GRU shape outside the step kernel's")
-        for seq in (d.f0_mlp, d.loudness_mlp, d.out_mlp):
+        for seq in (d.f0_mlp, d.loudness_mlp, d.out_mlp) + ((d.z_mlp,) if self.autoencoder else ()):
             if len(seq) != 9 or any(seq[i].negative_slope != 0.01 for i in (2, 5, 8)):
                 raise RuntimeError("RealtimeGraph(fused=True): mlp(.., .., 3) blocks of core.py:122-129 expected")
         R = self.call_samples // self.block_size
@@ -219,6 +265,14 @@ class RealtimeGraph:
                      "gru": z(Hd), "y4": z(Hd), "y5": z(Hd), "y6": z(Hd),
                      "param": z(m.harmonic_proj.out_features), "mags": z(m.noise_proj.out_features),
                      "f0": z(1), "loud": z(1), "h_last": z(Hd)[:1]}
+        if self.autoencoder:
+            e = m.encoder
+            if not core.gru_supported(e.gru):
+                raise RuntimeError("RealtimeGraph(fused=True): the encoder's GRU shape is outside the step kernel's")
+            He = e.gru.hidden_size
+            self._buf.update({"xpe": z(3 * He), "gru_e": z(He), "z": z(e.proj.out_features), "y1z": z(Hd),
+                              "y2z": z(Hd), "y3z": z(Hd)})
+            self.z = self._buf["z"].view(1, R, -1)
         # the persistent recurrence's sync words (ddsp_hip_gru_forward_persistent), zeroed by the call itself
         self._gru_ws = torch.zeros(int(core._lib.query("gru_persistent_workspace_size")), dtype=torch.uint8,
                                    device=dev)
@@ -234,16 +288,34 @@ class RealtimeGraph:
         inv = 1.0 / self.std_loudness
         f0m, lm, om = d.f0_mlp, d.loudness_mlp, d.out_mlp
         pitch, pitch_ld, loud, loud_ld = self._control_frames()
+        l2z, l3z, xpz = [], [], []
+        if self.autoencoder:
+            # the encoder (encoder.py:22-26) with a carried state: the GRU's input projection of norm(mfcc) (a
+            # LayerNorm without activation), the recurrence on the step kernels writing h_T over the state, proj
+            # -> z; then z_mlp's first Linear.  Its second and third blocks ride in f0_mlp's and loudness_mlp's
+            # launches and its output is the third block of columns of the decoder GRU's input (decoder.py:31-49):
+            # 3 launches + R steps more than the decoder alone
+            e, zm = m.encoder, d.z_mlp
+            ge = e.gru
+            w_ie = _Linear(ge.weight_ih_l0, ge.bias_ih_l0, ge.input_size, 3 * ge.hidden_size)
+            core.dense_rows([([di(self.mfcc.view(R, -1), norm=e.norm, activation=False)], w_ie, b["xpe"])], R, dev)
+            core.gru_recurrence(b["xpe"].view(1, R, -1), ge.weight_hh_l0, ge.bias_hh_l0, self.encoder_state,
+                                b["gru_e"].view(1, R, -1), self.encoder_state, persistent=False)
+            core.dense_rows([([di(b["gru_e"])], e.proj, b["z"])], R, dev)
+            core.dense_rows([([di(b["z"])], zm[0], b["y1z"])], R, dev)
+            l2z = [([di(b["y1z"], norm=zm[1])], zm[3], b["y2z"])]
+            l3z = [([di(b["y2z"], norm=zm[4])], zm[6], b["y3z"])]
+            xpz = [di(b["y3z"], norm=zm[7])]
         core.dense_rows([  # mlp layers 1-2 (core.py:122-129), f0 and loudness
             ([di(pitch, ld=pitch_ld, first=f0m[0], norm=f0m[1], x_copy=b["f0"])], f0m[3], b["y2f"]),
             ([di(loud, ld=loud_ld, scale=inv, shift=-self.mean_loudness * inv, first=lm[0], norm=lm[1],
-                 x_copy=b["loud"])], lm[3], b["y2l"])], R, dev)
+                 x_copy=b["loud"])], lm[3], b["y2l"])] + l2z, R, dev)
         core.dense_rows([([di(b["y2f"], norm=f0m[4])], f0m[6], b["y3f"]),
-                         ([di(b["y2l"], norm=lm[4])], lm[6], b["y3l"])], R, dev)
-        # GRU input projection of cat([f0_mlp(f0), loudness_mlp(loudness)]) (decoder.py:49)
+                         ([di(b["y2l"], norm=lm[4])], lm[6], b["y3l"])] + l3z, R, dev)
+        # GRU input projection of cat([f0_mlp(f0), loudness_mlp(loudness)[, z_mlp(z)]]) (decoder.py:49)
         g = d.gru
         w_ih = _Linear(g.weight_ih_l0, g.bias_ih_l0, g.input_size, 3 * g.hidden_size)
-        core.dense_rows([([di(b["y3f"], norm=f0m[7]), di(b["y3l"], norm=lm[7])], w_ih, b["xp"])], R, dev)
+        core.dense_rows([([di(b["y3f"], norm=f0m[7]), di(b["y3l"], norm=lm[7])] + xpz, w_ih, b["xp"])], R, dev)
         # the state in place: the step kernels write h_T over h0; the persistent launch, whose rescue re-reads h0,
         # into a buffer of its own, copied over the state after it.  The workspace is this object's: the graph holds it
         cache = d.cache_gru
@@ -268,13 +340,21 @@ class RealtimeGraph:
         pitch, pitch_ld, loud, loud_ld = self._control_frames()
         pitch = pitch.view(1, -1, 1)[:, ::pitch_ld]
         loudness = (loud.view(1, -1, 1)[:, ::loud_ld] - self.mean_loudness) / self.std_loudness
-        hidden = gru_decoder_forward(m.decoder, pitch, loudness, None, realtime=True)
+        z = None
+        if self.autoencoder:  # encoder.py:22-26 with the GRU state carried in self.encoder_state
+            e = m.encoder
+            x, h = core.gru(e.norm(self.mfcc), e.gru, self.encoder_state)
+            self.encoder_state.copy_(h)
+            z = self.z = e.proj(x)
+        hidden = gru_decoder_forward(m.decoder, pitch, loudness, z, realtime=True)
         param = m.harmonic_proj(hidden)
         mags = m.noise_proj(hidden)
         return self._synthesis(pitch.contiguous(), param, mags)
 
     def reset(self):
         self.model.decoder.cache_gru.zero_()
+        if self.encoder_state is not None:
+            self.encoder_state.zero_()
         self.counter.zero_()
         if self.stream is not None:
             self.stream.reset()

@@ -234,11 +234,14 @@ int ddsp_hip_reverb_forward(const float* x, const float* noise, const float* dec
  * act_s: x' = x * scale + shift (the exported model's loudness normalisation, export.py:35;
  * 1 and 0 otherwise); with w1/b1 (a K=1 nn.Linear of width `width`, the first layer of
  * core.py:122's mlp(1, ...)) x is one value per row and x'' = w1[c] * x' + b1[c]; with
- * gamma/beta: leaky_relu(layer_norm(x'') * gamma + beta, 0.01), eps 1e-5 (core.py:126).
- * x_copy (nullable, w1 inputs only) receives x' per row.  Up to DDSP_HIP_DENSE_MAX_PROBLEMS
- * independent Linears share one launch.  rows <= 8, K <= 1088 (else DDSP_HIP_ERANGE). */
+ * gamma/beta: leaky_relu(layer_norm(x'') * gamma + beta, 0.01), eps 1e-5 (core.py:126), or with
+ * plain_norm != 0 the LayerNorm alone (the MFCC encoder's `norm`, encoder.py; a zero-filled struct
+ * keeps the LeakyReLU).  x_copy (nullable, w1 inputs only) receives x' per row.  Up to
+ * DDSP_HIP_DENSE_MAX_PROBLEMS independent Linears share one launch (the f0, loudness and z MLPs).
+ * rows <= 8, K <= 1536 (else DDSP_HIP_ERANGE): K <= 1088 runs the kernel with 17 register chunks of
+ * 64 columns per W row, a wider K (the z-conditioned GRU input's 3 x 512) the one with 24. */
 #define DDSP_HIP_DENSE_MAX_INPUTS 3
-#define DDSP_HIP_DENSE_MAX_PROBLEMS 2
+#define DDSP_HIP_DENSE_MAX_PROBLEMS 3
 typedef struct ddsp_hip_dense_input {
   const float* x;      /* [rows, ld] (w1 inputs: x[r * ld] is the row's value) */
   int64_t ld;
@@ -249,6 +252,7 @@ typedef struct ddsp_hip_dense_input {
   const float* gamma;  /* nullable [width]: LayerNorm + LeakyReLU */
   const float* beta;
   float* x_copy;       /* nullable [rows] */
+  int plain_norm;      /* with gamma: 0 = LayerNorm + LeakyReLU(0.01), non-zero = the LayerNorm alone */
 } ddsp_hip_dense_input;
 typedef struct ddsp_hip_dense_problem {
   ddsp_hip_dense_input inputs[DDSP_HIP_DENSE_MAX_INPUTS];
@@ -730,6 +734,36 @@ int ddsp_hip_stream_analysis(const float* x, const float* weights, float* loudne
                              int32_t* period, const uint64_t* counter, void* state, size_t state_bytes, int64_t batch,
                              int64_t call_samples, int64_t frame_length, int64_t hop, int64_t tau_min, int64_t tau_max,
                              float sample_rate, float threshold, void* stream);
+
+/* ddsp_hip_stream_analysis plus ddsp_hip_stream_mfcc of the same frames in ONE launch over ONE state, on ONE time
+ * axis: what a z-conditioned model (the reference's ddsp/models/encoder.py autoencoder) needs per call of a stream.
+ * L = frame_length is the loudness's and the pitch's frame, M = mfcc_n_fft the MFCC's n_fft, M == L or M == L/2.
+ * MFCC slot j of the call uses the M-sample window centred in frame j's L-sample window (sample (L - M)/2 + i of
+ * frame j, i < M), so slot j of loudness_out, mfcc_out and f0 all describe stream frame k R - d(L) + 1 + j, where
+ * ddsp_hip_stream_mfcc alone would emit frame k R - d(M) + 1 + j.  loudness_out / f0 / confidence / period hold
+ * ddsp_hip_stream_analysis' bits; mfcc_out [batch, R, n_mfcc] holds the bits of ddsp_hip_stream_mfcc(n_fft = M) fed
+ * the same stream delayed by (d(L) - d(M)) hop samples (that many zeros first), causal clamp included.
+ * Grid: per item the pitch and the loudness workgroups of ddsp_hip_stream_analysis, then one more workgroup that runs
+ * the streamed MFCC's per-call code over the same ring.  f0 == NULL: no pitch workgroups are launched (loudness and
+ * MFCC only, for a caller who brings a pitch track); confidence and period must then be NULL too and tau_min /
+ * tau_max / sample_rate / threshold are not looked at.
+ * State: ddsp_hip_stream_features_state_bytes(batch, call_samples, L, hop) bytes, zero-filled for a fresh stream, the
+ * layout of "streaming analysis" above: the rings, then the float per item that carries the MFCC's running maximum.
+ * Every workgroup copies its strided share of x into the ring and none reads a position another writes; the counter
+ * is read and never written; a call run twice before the advance gives the same bits (the maximum is folded into a
+ * value that already holds it).
+ * Checked before any HIP call, in this order: the streaming envelope (as ddsp_hip_stream_loudness) and L a power of
+ * two in [64, 2048] (else DDSP_HIP_ERANGE); with f0 the pitch parameters (as ddsp_hip_stream_pitch), without it
+ * confidence == period == NULL (else DDSP_HIP_EINVAL); the MFCC parameters: M in {L, L/2} (else DDSP_HIP_ERANGE) and
+ * n_band_weights, n_mels, n_mfcc, top_db held to ddsp_hip_stream_mfcc's limits; batch == 0: a no-op success; null x /
+ * loudness_out / band tables / dct / mfcc_out / counter / state: DDSP_HIP_EINVAL; a short state: DDSP_HIP_EWORKSPACE. */
+int ddsp_hip_stream_analysis_mfcc(const float* x, const float* weights, float* loudness_out, const int32_t* band_start,
+                                  const int32_t* band_count, const float* band_weights, int64_t n_band_weights,
+                                  const float* dct, float* mfcc_out, float* f0, float* confidence, int32_t* period,
+                                  const uint64_t* counter, void* state, size_t state_bytes, int64_t batch,
+                                  int64_t call_samples, int64_t frame_length, int64_t mfcc_n_fft, int64_t hop,
+                                  int64_t n_mels, int64_t n_mfcc, float top_db, int64_t tau_min, int64_t tau_max,
+                                  float sample_rate, float threshold, void* stream);
 
 /* Two-stage serving pipeline (ddsp_pytorch_amd.synth.PipelinedSynthPath; no reference counterpart:
  * the reference synthesises one batch at a time, decoder.py:101-136).  A HIP stream restricted to

@@ -17,6 +17,10 @@ same definition (include/ddsp_hip.h, "pitch") composed from torch.fft and ATen o
 write today; the package had no pitch path before — and core.stream_pitch at the realtime shape, captured in a HIP
 graph.  DESIGN.md 3f-pitch records a run.
 
+``--leg aligned`` times core.stream_analysis_mfcc (the streamed loudness, MFCC and pitch in one launch over one state,
+on one time axis) against core.stream_analysis + core.stream_mfcc as two launches on two states, and against
+core.stream_analysis alone, the same way.
+
 ``--leg fused`` times core.stream_analysis (the streamed loudness and pitch in one launch over one state) against
 core.stream_loudness + core.stream_pitch (two launches, two states) at the realtime shape, each captured in a HIP
 graph, the legs' windows alternating.  DESIGN.md 3f-fused records a run.
@@ -232,18 +236,52 @@ def fused_leg(dev, reps, windows):
               flush=True)
 
 
+def aligned_leg(dev, reps, windows):
+    """The three-feature launch (core.stream_analysis_mfcc: loudness, MFCC and pitch over one state, on one time
+    axis) against the route without it for the same features (core.stream_analysis + core.stream_mfcc, two launches
+    on two states) and against core.stream_analysis alone, each captured in a HIP graph; the legs' windows alternate
+    as fused_leg's do."""
+    sr, hop, N, L, M = 48000, 256, 1024, 2048, 1024
+    x = 0.1 * torch.randn(1, N, device=dev)
+    sa = core.FeatureStreamState(1, dev, N, L, hop)
+    sf = core.FeatureStreamState(1, dev, N, L, hop, counter=sa.counter)
+    sm = core.FeatureStreamState(1, dev, N, M, hop, counter=sa.counter)
+    kw = dict(return_confidence=True, return_period=True)
+    legs = [
+        ("stream analysis + stream mfcc (two launches, two states)",
+         graphed(lambda: (core.stream_analysis(x, sr, hop, sf, **kw), core.stream_mfcc(x, sr, hop, sm, n_fft=M))), 2),
+        ("stream analysis mfcc (one launch, one state)",
+         graphed(lambda: core.stream_analysis_mfcc(x, sr, hop, sa, mfcc_n_fft=M, **kw)), 1),
+        ("stream analysis mfcc, pitch=False", graphed(lambda: core.stream_analysis_mfcc(x, sr, hop, sa, pitch=False)), 1),
+        ("stream analysis alone", graphed(lambda: core.stream_analysis(x, sr, hop, sf, **kw)), 1),
+        ("stream mfcc alone", graphed(lambda: core.stream_mfcc(x, sr, hop, sm, n_fft=M)), 1),
+    ]
+    ms = [[] for _ in legs]
+    for _ in range(windows):
+        for i, (_, fn, _) in enumerate(legs):
+            ms[i].append(timed(fn, reps, 1)[0])
+    for (leg, _, launches), m in zip(legs, ms):
+        print(json.dumps({"shape": "stream 1x1024 block 256 L 2048 M 1024", "leg": leg, "graph_nodes": launches,
+                          "us": round(1e3 * statistics.median(m), 2), "us_min": round(1e3 * min(m), 2),
+                          "us_max": round(1e3 * max(m), 2), "windows_us": [round(1e3 * v, 2) for v in m]}),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=1000)
     ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--leg", choices=("offline", "stream", "pitch", "fused", "all"), default="all",
-                    help="all: offline and stream (the pitch and fused legs run on request)")
+    ap.add_argument("--leg", choices=("offline", "stream", "pitch", "fused", "aligned", "all"), default="all",
+                    help="all: offline and stream (the pitch, fused and aligned legs run on request)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_features: needs a HIP device (there is no CPU path)")
     dev = torch.device("cuda", 0)
     if args.leg == "fused":
         fused_leg(dev, args.reps, args.windows)
+        return
+    if args.leg == "aligned":
+        aligned_leg(dev, args.reps, args.windows)
         return
     if args.leg == "pitch":
         pitch_leg(dev, args.reps, args.windows)

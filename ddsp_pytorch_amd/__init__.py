@@ -12,7 +12,9 @@ Drop-in for hugofloresgarcia/ddsp_pytorch's synthesis hot path:
   ``features.StreamAnalyzer`` / ``core.stream_loudness`` / ``core.stream_mfcc``: the same per call of a stream;
   ``core.extract_pitch`` / ``core.stream_pitch``: f0 from the audio by the YIN estimator (the reference's
   ``extract_pitch`` is the CREPE network, which this package does not carry), so ``analyze(signal, None, ...)``
-  runs from audio alone; ``core.stream_analysis``: the streamed loudness and pitch in one launch over one state,
+  runs from audio alone; ``core.track_pitch`` (``analyze(..., viterbi=True)``): the same d' decoded over time by a
+  Viterbi path, offline, as the reference's ``crepe.predict(..., viterbi=True)`` decodes its salience;
+  ``core.stream_analysis``: the streamed loudness and pitch in one launch over one state,
   which ``realtime.RealtimeGraph(loudness_from_audio=True, pitch_from_audio=True)`` runs per call (audio in,
   audio out); ``core.stream_analysis_mfcc`` / ``StreamAnalyzer(aligned=True)``: the streamed loudness, MFCC and pitch
   of the same frames in one launch on one time axis, which ``RealtimeGraph`` runs for a ``DDSPAutoencoder`` (the

@@ -119,6 +119,12 @@ SIGNATURES = {
     # pitch (YIN f0), offline and per call of a stream
     "ddsp_hip_pitch": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _F, _F, _P]),
     "ddsp_hip_stream_pitch": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64, _I64, _I64, _F, _F, _P]),
+    # Viterbi-decoded pitch: the salience over lag bins, then the decode
+    "ddsp_hip_pitch_salience": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F,
+                                     _F, _P]),
+    "ddsp_hip_pitch_viterbi_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "ddsp_hip_pitch_viterbi_chunk_frames": (_I64, [_I64]),
+    "ddsp_hip_pitch_viterbi": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64, _F, _P]),
     # streamed loudness + pitch of one call in one launch over one state
     "ddsp_hip_stream_analysis": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64, _I64, _I64, _F, _F,
                                       _P]),

@@ -30,6 +30,7 @@ __all__ = [
     "reverb_spectrum", "reverb_impulse_spectrum", "reverb_apply", "reverb_forward", "reverb_cache_bytes", "set_noise_seed", "safe_log", "stft_magnitude", "multiscale_fft",
     "extract_loudness", "mfcc", "FeatureStreamState", "stream_loudness", "stream_mfcc", "stream_feature_delay",
     "extract_pitch", "stream_pitch", "pitch_lags", "stream_analysis", "stream_analysis_mfcc",
+    "pitch_bins", "pitch_salience", "viterbi_path", "track_pitch",
 ]
 
 
@@ -1043,6 +1044,106 @@ def extract_pitch(signal, sample_rate, block_size, fmin=50.0, fmax=2000.0, frame
     _lib.call("pitch", _lib.ptr(x), _lib.ptr(f0), _lib.ptr(conf), _lib.ptr(period), B, T, L, int(block_size),
               tau_min, tau_max, float(sample_rate), float(threshold), _lib.stream_of(x))
     return _pitch_result(f0, conf, period, one_d)
+
+
+def _pitch_bin_arrays(tau_min, tau_max, bins_per_octave):
+    """(lo, hi) int32 arrays of include/ddsp_hip.h ("pitch_viterbi", Bins), in double precision."""
+    beta = float(bins_per_octave)
+    if not beta > 0.0:
+        raise RuntimeError(f"pitch_bins: bins_per_octave must be positive, got {bins_per_octave}")
+    tau = np.arange(tau_min, tau_max + 1, dtype=np.int64)
+    bins = np.rint(beta * np.log2(float(tau_max) / tau.astype(np.float64))).astype(np.int64)  # halves to even
+    n_bins = int(bins[0]) + 1
+    if n_bins > 1024:
+        raise RuntimeError(f"pitch_bins: {n_bins} bins (lags {tau_min} .. {tau_max} at {bins_per_octave} per octave) "
+                           "exceed the decode's 1024")
+    centre = np.clip(np.rint(float(tau_max) * 2.0 ** (-np.arange(n_bins) / beta)), tau_min, tau_max).astype(np.int64)
+    lo, hi = np.full(n_bins, tau_max + 1, dtype=np.int64), np.full(n_bins, -1, dtype=np.int64)
+    np.minimum.at(lo, bins, tau)
+    np.maximum.at(hi, bins, tau)
+    empty = hi < 0
+    lo[empty], hi[empty] = centre[empty], centre[empty]
+    return lo.astype(np.int32), hi.astype(np.int32)
+
+
+def pitch_bins(sample_rate, fmin, fmax, frame_length, bins_per_octave=48):
+    """(tau_min, tau_max, lo, hi) of include/ddsp_hip.h ("pitch_viterbi"): ``pitch_lags``' lag range and, per
+    log-spaced bin i = rint(bins_per_octave * log2(tau_max / tau)), the smallest and the largest lag in it (a bin no
+    lag falls in holds its centre's nearest lag); host lists of len n_bins <= 1024, built once in double precision."""
+    tau_min, tau_max = pitch_lags(sample_rate, fmin, fmax, frame_length)
+    lo, hi = _pitch_bin_arrays(tau_min, tau_max, bins_per_octave)
+    return tau_min, tau_max, lo.tolist(), hi.tolist()
+
+
+def _pitch_bin_tables(sample_rate, fmin, fmax, frame_length, bins_per_octave, device):
+    """(tau_min, tau_max, lo, hi) with lo / hi on ``device``, cached per parameters as the other analysis tables."""
+    tau_min, tau_max = pitch_lags(sample_rate, fmin, fmax, frame_length)
+    lo, hi = _feature_tables("pitch_bins", (tau_min, tau_max, float(bins_per_octave)), device,
+                             lambda: _pitch_bin_arrays(tau_min, tau_max, bins_per_octave))
+    return tau_min, tau_max, lo, hi
+
+
+def pitch_salience(signal, sample_rate, block_size, fmin=50.0, fmax=2000.0, frame_length=2048, bins_per_octave=48,
+                   return_lag=False, return_raw=False, threshold=0.1):
+    """The salience the Viterbi decode runs over (include/ddsp_hip.h, "pitch_viterbi"): signal [T] or [B, T] (HIP,
+    fp32) -> (cost, f0c[, lag]), each [B, T // block_size, n_bins] ([F, n_bins] for a 1-D signal): per frame of
+    ``extract_pitch`` and per bin of ``pitch_bins``, min(1, d') at the bin's best lag, the f0 candidate there after
+    the parabola, and the lag itself (int32).  ``return_raw``: also ``extract_pitch``'s (f0, confidence, period) for
+    ``threshold``, bit for bit, out of the same launch.  One launch; the bin tables are built on the host at the
+    first call per parameters and device and cached (no host synchronisation afterwards).  No autograd."""
+    x, one_d = _signal_rows(signal, block_size, "pitch_salience")
+    L = int(frame_length)
+    tau_min, tau_max, lo, hi = _pitch_bin_tables(sample_rate, fmin, fmax, L, bins_per_octave, x.device)
+    B, T = x.shape
+    F, NB = T // int(block_size), lo.numel()
+    cost = torch.empty(B, F, NB, dtype=torch.float32, device=x.device)
+    f0c = torch.empty_like(cost)
+    lag = torch.empty(B, F, NB, dtype=torch.int32, device=x.device) if return_lag else None
+    raw = _pitch_outputs(B, F, x.device, True, True) if return_raw else (None, None, None)
+    _lib.call("pitch_salience", _lib.ptr(x), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(cost), _lib.ptr(f0c),
+              _lib.ptr(lag), _lib.ptr(raw[0]), _lib.ptr(raw[1]), _lib.ptr(raw[2]), B, T, L, int(block_size), tau_min,
+              tau_max, NB, float(sample_rate), float(threshold), _lib.stream_of(x))
+    out = tuple(t for t in (cost, f0c, lag) + tuple(raw) if t is not None)
+    return tuple(t[0] for t in out) if one_d else out
+
+
+def viterbi_path(cost, f0c, transition=0.02, max_jump=12):
+    """The decode of include/ddsp_hip.h ("pitch_viterbi"): cost, f0c [B, F, n_bins] or [F, n_bins] (HIP, fp32) ->
+    (f0, confidence, path), each [B, F] or [F]: the path of least summed cost over the frames when a move of k bins
+    (|k| <= ``max_jump`` <= 127) between neighbouring frames costs ``transition`` * k, in fp64 with the smallest index
+    winning every tie; f0 = f0c and confidence = 1 - cost along it, path int32.  One launch, one workgroup per item;
+    no host synchronisation.  No autograd."""
+    _dev(cost, f0c)
+    if cost.dim() not in (2, 3) or cost.shape != f0c.shape:
+        raise RuntimeError(f"viterbi_path: cost and f0c must both be [frames, bins] or [batch, frames, bins], got "
+                           f"{tuple(cost.shape)} and {tuple(f0c.shape)}")
+    one = cost.dim() == 2
+    c, g = (_c(t.detach().float().unsqueeze(0) if one else t.detach().float()) for t in (cost, f0c))
+    B, F, NB = c.shape
+    if NB < 1:
+        raise RuntimeError("viterbi_path: no bins")
+    f0 = torch.empty(B, F, dtype=torch.float32, device=c.device)
+    conf = torch.empty_like(f0)
+    path = torch.empty(B, F, dtype=torch.int32, device=c.device)
+    ws = torch.empty(B * F * NB, dtype=torch.int8, device=c.device)
+    _lib.call("pitch_viterbi", _lib.ptr(c), _lib.ptr(g), _lib.ptr(f0), _lib.ptr(conf), _lib.ptr(path), _lib.ptr(ws),
+              ws.numel(), B, F, NB, int(max_jump), float(transition), _lib.stream_of(c))
+    return (f0[0], conf[0], path[0]) if one else (f0, conf, path)
+
+
+def track_pitch(signal, sample_rate, block_size, fmin=50.0, fmax=2000.0, frame_length=2048, bins_per_octave=48,
+                transition=0.02, max_jump=12, return_confidence=False, return_path=False):
+    """f0 from raw audio with a temporal model: ``pitch_salience`` then ``viterbi_path`` — signal [T] or [B, T] (HIP,
+    fp32) -> f0 in Hz, [T // block_size] or [B, T // block_size] (and on request the confidence 1 - d' along the path
+    and the path's bins, int32).  Where ``extract_pitch`` takes each frame's first dip on its own and jumps an octave
+    when a harmonic outweighs the fundamental, the decode pays ``transition`` per bin (1 / ``bins_per_octave``
+    octave) moved between frames, which is what ``viterbi=True`` buys the reference's CREPE track.  Offline only (the
+    decode needs the whole signal); two launches, no host synchronisation after the first call.  No autograd."""
+    one_d = signal.dim() == 1
+    cost, f0c = pitch_salience(signal.unsqueeze(0) if one_d else signal, sample_rate, block_size, fmin=fmin,
+                               fmax=fmax, frame_length=frame_length, bins_per_octave=bins_per_octave)
+    f0, conf, path = viterbi_path(cost, f0c, transition=transition, max_jump=max_jump)
+    return _pitch_result(f0, conf if return_confidence else None, path if return_path else None, one_d)
 
 
 def mfcc_tables(sample_rate, n_mfcc, n_fft, n_mels, fmin, fmax, device):

@@ -135,12 +135,19 @@ __device__ __forceinline__ void transform_argmin(int& first, double& best, int& 
   }
 }
 
-// Frame f of fetch by the transform's Q threads (thread t, LDS slots lds); the transform's thread 0 writes the
-// frame's outputs to slot o of f0 / conf / period when `write`.  Every thread of the workgroup calls this.
+// Where yin_dprime leaves d'(tau), tau <= tau_max + 1, in the transform's LDS slots: the second half (the scans' PAD
+// doubles come first).
+template <int N>
+__device__ __forceinline__ double* yin_dp(double2* lds) {
+  return reinterpret_cast<double*>(lds) + (N + N / 16);
+}
+
+// d'(tau) of frame f of fetch by the transform's Q threads (thread t, LDS slots lds): dn[r] for this thread's lags
+// tau = t + Q r, and every tau <= tau_max + 1 at yin_dp<N>(lds)[tau], published by the closing barrier.  Every
+// thread of the workgroup calls this.
 template <int N, class Fetch>
-__device__ __forceinline__ void yin_frame(const Fetch& fetch, int f, int t, double2* lds, double* wsum, int* rint,
-                                          const PitchParams& p, bool write, int64_t o, float* __restrict__ f0,
-                                          float* __restrict__ conf, int32_t* __restrict__ period) {
+__device__ __forceinline__ void yin_dprime(const Fetch& fetch, int f, int t, double2* lds, double* wsum,
+                                           const PitchParams& p, double (&dn)[9]) {
   constexpr int Q = N / 16, W = N / 2, PAD = N + N / 16;
   double* buf = reinterpret_cast<double*>(lds);  // the scans' PAD doubles (entry j at lds_idx(j))
   double* dp = buf + PAD;                        // d'(tau), tau <= W, in the second half
@@ -207,7 +214,6 @@ __device__ __forceinline__ void yin_frame(const Fetch& fetch, int f, int t, doub
   __syncthreads();
 
   // d'(tau), tau <= tau_max + 1
-  double dn[9];
 #pragma unroll
   for (int r = 0; r < 9; ++r) {
     const int tau = t + Q * r;
@@ -219,8 +225,17 @@ __device__ __forceinline__ void yin_frame(const Fetch& fetch, int f, int t, doub
     }
   }
   __syncthreads();
+}
 
-  // tau*: the smallest candidate under the threshold, else the smallest index of the minimum
+// tau* of the frame whose d' yin_dprime left (dn, and LDS): the smallest candidate under the threshold, else the
+// smallest index of the minimum; the transform's thread 0 finishes the parabola and writes the frame's outputs to
+// slot o of f0 / conf / period when `write`.  Every thread of the workgroup calls this.
+template <int N>
+__device__ __forceinline__ void yin_pick(const double (&dn)[9], int t, double2* lds, double* wsum, int* rint,
+                                         const PitchParams& p, bool write, int64_t o, float* __restrict__ f0,
+                                         float* __restrict__ conf, int32_t* __restrict__ period) {
+  constexpr int Q = N / 16;
+  const double* dp = yin_dp<N>(lds);
   const double thr = (double)p.threshold;
   int first = INT_MAX, besti = INT_MAX;
   double best = INFINITY;
@@ -243,6 +258,17 @@ __device__ __forceinline__ void yin_frame(const Fetch& fetch, int f, int t, doub
   f0[o] = (float)((double)p.sample_rate / ((double)ts + s));
   if (conf) conf[o] = (float)(1.0 - fmin(1.0, b - 0.25 * (a - c) * s));
   if (period) period[o] = ts;
+}
+
+// Frame f of fetch by the transform's Q threads (thread t, LDS slots lds); the transform's thread 0 writes the
+// frame's outputs to slot o of f0 / conf / period when `write`.  Every thread of the workgroup calls this.
+template <int N, class Fetch>
+__device__ __forceinline__ void yin_frame(const Fetch& fetch, int f, int t, double2* lds, double* wsum, int* rint,
+                                          const PitchParams& p, bool write, int64_t o, float* __restrict__ f0,
+                                          float* __restrict__ conf, int32_t* __restrict__ period) {
+  double dn[9];
+  yin_dprime<N>(fetch, f, t, lds, wsum, p, dn);
+  yin_pick<N>(dn, t, lds, wsum, rint, p, write, o, f0, conf, period);
 }
 
 // The parameters the pitch entry points share (include/ddsp_hip.h), checked before any HIP call.

@@ -537,6 +537,50 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_stream(const at::Tensor& x,
   return {f0, conf, period};
 }
 
+// ---------------- pitch_viterbi: the salience over lag bins and the decode (ddsp_hip_pitch_salience / _viterbi) ------
+// -> (cost, f0c, lag), each [B, F, n_bins] ([F, n_bins] for a 1-D signal)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_salience(const at::Tensor& x, const at::Tensor& lo,
+                                                              const at::Tensor& hi, int64_t frame_length, int64_t hop,
+                                                              int64_t tau_min, int64_t tau_max, double sample_rate) {
+  at::Tensor xc = audio_rows(x, "pitch_salience");
+  TORCH_CHECK(hop >= 1, "pitch_salience: hop must be positive");
+  for (const at::Tensor* t : {&lo, &hi})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->dim() == 1 && t->numel() == lo.numel(),
+                "pitch_salience: lo and hi must be int32 HIP tensors of n_bins values");
+  at::Tensor l = lo.contiguous(), h = hi.contiguous();
+  const int64_t B = xc.size(0), T = xc.size(1), NB = l.numel();
+  at::Tensor cost = at::empty({B, T / hop, NB}, xc.options());
+  at::Tensor f0c = at::empty_like(cost);
+  at::Tensor lag = at::empty({B, T / hop, NB}, xc.options().dtype(at::kInt));
+  ok(ddsp_hip_pitch_salience(xc.data_ptr<float>(), l.data_ptr<int32_t>(), h.data_ptr<int32_t>(),
+                             cost.data_ptr<float>(), f0c.data_ptr<float>(), lag.data_ptr<int32_t>(), nullptr, nullptr,
+                             nullptr, B, T, frame_length, hop, tau_min, tau_max, NB, (float)sample_rate, 0.0f,
+                             stream_of(xc)),
+     "pitch_salience");
+  if (x.dim() == 1) return {cost.select(0, 0), f0c.select(0, 0), lag.select(0, 0)};
+  return {cost, f0c, lag};
+}
+
+// cost, f0c [B, F, n_bins] -> (f0, confidence, path), each [B, F]
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_viterbi(const at::Tensor& cost, const at::Tensor& f0c,
+                                                             double transition, int64_t max_jump) {
+  check_dev(cost, "cost");
+  check_dev(f0c, "f0c");
+  TORCH_CHECK(cost.dim() == 3 && cost.sizes() == f0c.sizes() && cost.size(2) >= 1,
+              "pitch_viterbi: cost and f0c must both be [batch, frames, bins]");
+  at::Tensor c = cost.contiguous(), g = f0c.contiguous();
+  const int64_t B = c.size(0), F = c.size(1), NB = c.size(2);
+  at::Tensor f0 = at::empty({B, F}, c.options());
+  at::Tensor conf = at::empty_like(f0);
+  at::Tensor path = at::empty({B, F}, c.options().dtype(at::kInt));
+  at::Tensor ws = at::empty({B * F * NB}, c.options().dtype(at::kChar));
+  ok(ddsp_hip_pitch_viterbi(c.data_ptr<float>(), g.data_ptr<float>(), f0.data_ptr<float>(), conf.data_ptr<float>(),
+                            path.data_ptr<int32_t>(), ws.data_ptr(), (size_t)ws.numel(), B, F, NB, max_jump,
+                            (float)transition, stream_of(c)),
+     "pitch_viterbi");
+  return {f0, conf, path};
+}
+
 // loudness_stream + pitch_stream in one launch over one state (ddsp_hip_stream_analysis)
 // -> (loudness, f0, confidence, period)
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> analysis_stream(
@@ -675,6 +719,9 @@ TORCH_LIBRARY(ddsp_hip, m) {
         " -> (Tensor, Tensor, Tensor)");
   m.def("pitch_stream(Tensor x, int frame_length, int hop, int tau_min, int tau_max, float sample_rate,"
         " float threshold, Tensor counter, Tensor(a!) state) -> (Tensor, Tensor, Tensor)");
+  m.def("pitch_salience(Tensor x, Tensor lo, Tensor hi, int frame_length, int hop, int tau_min, int tau_max,"
+        " float sample_rate) -> (Tensor, Tensor, Tensor)");
+  m.def("pitch_viterbi(Tensor cost, Tensor f0c, float transition, int max_jump) -> (Tensor, Tensor, Tensor)");
   m.def("analysis_stream(Tensor x, Tensor? weights, int frame_length, int hop, int tau_min, int tau_max,"
         " float sample_rate, float threshold, Tensor counter, Tensor(a!) state) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("analysis_mfcc_stream(Tensor x, Tensor? weights, Tensor band_start, Tensor band_count, Tensor band_weights,"
@@ -710,6 +757,8 @@ TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA 
   m.impl("mfcc_stream", &mfcc_stream);
   m.impl("pitch", &pitch);
   m.impl("pitch_stream", &pitch_stream);
+  m.impl("pitch_salience", &pitch_salience);
+  m.impl("pitch_viterbi", &pitch_viterbi);
   m.impl("analysis_stream", &analysis_stream);
   m.impl("analysis_mfcc_stream", &analysis_mfcc_stream);
 }

@@ -21,11 +21,13 @@ __all__ = ["analyze", "StreamAnalyzer"]
 
 
 def analyze(signal, pitch=None, sample_rate=None, block_size=None, mean_loudness=None, std_loudness=None, fmin=50.0,
-            fmax=2000.0):
+            fmax=2000.0, viterbi=False):
     """signal [T] or [B, T] (HIP, fp32) and pitch (F = T // block_size values per item, [B, F] or [B, F, 1]) ->
     ``{'pitch': [B, F, 1], 'loudness': [B, F, 1], 'mfcc': [B, F, 30]}``, the shapes of ``ddsp/data.py:22-32``
     (the MFCC's last frame is dropped there, ``data.py:25``; the loudness's inside ``extract_loudness``).
-    ``pitch=None``: f0 is computed from the audio (``core.extract_pitch`` over ``fmin`` .. ``fmax`` Hz, YIN).
+    ``pitch=None``: f0 is computed from the audio (``core.extract_pitch`` over ``fmin`` .. ``fmax`` Hz, YIN; with
+    ``viterbi=True`` ``core.track_pitch``, the Viterbi decode over the same frames' d', which keeps the track from
+    jumping octaves the way the reference's ``crepe.predict(..., viterbi=True)`` does).
     ``sample_rate`` and ``block_size`` are required.  With ``mean_loudness`` and ``std_loudness`` the loudness is
     normalised as ``train.py:87`` does, ``(l - mean) / std``.  No autograd, no host synchronisation after the first
     call (see ``core.mfcc``)."""
@@ -40,7 +42,8 @@ def analyze(signal, pitch=None, sample_rate=None, block_size=None, mean_loudness
         loudness = (loudness - mean_loudness) / std_loudness
     mfcc = core.mfcc(x, sample_rate, block_size)[:, :F]
     if pitch is None:
-        pitch = core.extract_pitch(x, sample_rate, block_size, fmin=fmin, fmax=fmax)
+        track = core.track_pitch if viterbi else core.extract_pitch
+        pitch = track(x, sample_rate, block_size, fmin=fmin, fmax=fmax)
     pitch = torch.as_tensor(pitch, dtype=torch.float32, device=x.device)
     if pitch.numel() != B * F:
         raise RuntimeError(f"analyze: pitch must hold {B} x {F} values (T // block_size per item), got "

@@ -716,6 +716,66 @@ int ddsp_hip_stream_pitch(const float* x, float* f0, float* confidence, int32_t*
                           int64_t hop, int64_t tau_min, int64_t tau_max, float sample_rate, float threshold,
                           void* stream);
 
+/* ---------------- pitch_viterbi: a Viterbi-decoded f0 over YIN's d' as the salience, offline ----------------
+ * The reference's extract_pitch is crepe.predict(..., viterbi=True): a salience per frame, then a Viterbi decode over
+ * time.  The decode does not care which estimator made the salience; here the salience is 1 - d' of "pitch" above, so
+ * that a frame whose smallest dip sits an octave off is overruled by its neighbours.  Two launches, offline only (the
+ * decode needs the future).
+ *
+ * Frames and d'.  Exactly ddsp_hip_pitch's: offline reflect-indexed frames, L a power of two in [64, 4096], W = L/2,
+ * hop, d'(tau) for tau = 0 .. tau_max + 1 by steps 1-5 of "pitch" in fp64, the 2^-40 floor and the zero-energy rule
+ * included; tau_min and tau_max as there.
+ *
+ * Bins: host integers, built once in double precision.  With beta = bins per octave (48 is usual: 25 cents),
+ *   bin(tau) = rint(beta log2(tau_max / tau)) for tau in [tau_min, tau_max] (rint: halves to even), so bin(tau_max) = 0;
+ *   n_bins NB = bin(tau_min) + 1, at most 1024 (else DDSP_HIP_ERANGE);
+ *   lo_i / hi_i = the smallest / the largest tau with bin(tau) = i; where no lag falls in bin i (high frequencies),
+ *   lo_i = hi_i = clip(rint(tau_max 2^(-i / beta)), tau_min, tau_max).
+ * The entry point takes lo[NB] and hi[NB] as int32 device arrays and clamps them into tau_min <= lo_i <= hi_i <=
+ * tau_max, so that no table can make it read outside d'.
+ *
+ * Salience, per frame f and bin i:
+ *   tau^ = the smallest tau in [lo_i, hi_i] attaining the minimum of d' over that range;
+ *   cost(f, i) = (float)min(1, d'(tau^));
+ *   f0c(f, i)  = (float)(sr / (tau^ + s)), s by step 7 of "pitch" over d'(tau^ - 1 .. tau^ + 1);
+ *   lag(f, i)  = tau^.
+ * A silent frame gives cost 1 in every bin and f0c = sr / lo_i: finite, never a NaN.
+ *
+ * Decode, per item over its frames t = 0 .. F - 1, all in fp64; lambda = transition (the fp32 value passed, widened),
+ * R = max_jump in bins, 0 <= R <= 127; pen(k) = lambda k (exact):
+ *   delta_0(j) = cost(0, j);
+ *   delta_t(j) = min over i in [max(0, j - R), min(NB - 1, j + R)] of (delta_{t-1}(i) + pen(|i - j|)),
+ *                then + cost(t, j);  bp_t(j) = the smallest i attaining that minimum;
+ *   path(F - 1) = the smallest argmin of delta_{F-1};  path(t - 1) = bp_t(path(t));
+ *   f0(t) = f0c(t, path(t)), confidence(t) = 1 - cost(t, path(t)), path(t) int32: each [batch, F].
+ * Every operation is one fp64 addition or a comparison, so a restatement reproduces the path bit for bit from the
+ * same costs.  With lambda > 0 and all costs equal the path is all zeros.  Fixed orders, no atomics: two runs give the
+ * same bits and an item's bits do not depend on the batch around it.
+ *
+ * ddsp_hip_pitch_salience: x [batch, n_samples] -> cost, f0c [batch, F, NB] fp32, lag [batch, F, NB] int32 (may be
+ * NULL), F = n_samples / hop; pitch_kernel's grid.  With f0 given ([batch, F]; confidence and period [batch, F] may
+ * then be given too) the same launch also writes ddsp_hip_pitch's outputs for the threshold, bit for bit.
+ * Checked before any HIP call, as ddsp_hip_pitch, and: n_bins < 1, confidence or period without f0: DDSP_HIP_EINVAL;
+ * n_bins > 1024: DDSP_HIP_ERANGE; batch == 0: a no-op success; null x / lo / hi / cost / f0c: DDSP_HIP_EINVAL. */
+int ddsp_hip_pitch_salience(const float* x, const int32_t* lo, const int32_t* hi, float* cost, float* f0c,
+                            int32_t* lag, float* f0, float* confidence, int32_t* period, int64_t batch,
+                            int64_t n_samples, int64_t frame_length, int64_t hop, int64_t tau_min, int64_t tau_max,
+                            int64_t n_bins, float sample_rate, float threshold, void* stream);
+
+/* The decode: cost, f0c [batch, frames, n_bins] -> f0, confidence (may be NULL), path [batch, frames].  One workgroup
+ * per item, one thread per bin, one barrier per frame: latency-bound by design (a preprocessing step).  The workspace
+ * holds the back-offsets bp_t(j) - j as int8: ddsp_hip_pitch_viterbi_workspace_bytes = batch frames n_bins bytes (0
+ * for sizes the entry point refuses); nothing in it needs zeroing.  The backtrack stages them through LDS
+ * ddsp_hip_pitch_viterbi_chunk_frames(n_bins) = min(32768 / n_bins, 512) frames at a time (0 outside [1, 1024]).
+ * Checked before any HIP call: negative batch / frames / max_jump, n_bins < 1, transition negative, infinite or NaN:
+ * DDSP_HIP_EINVAL; n_bins > 1024, max_jump > 127: DDSP_HIP_ERANGE; batch == 0 or frames == 0: a no-op success; null
+ * cost / f0c / f0 / path / workspace: DDSP_HIP_EINVAL; a short workspace: DDSP_HIP_EWORKSPACE. */
+size_t ddsp_hip_pitch_viterbi_workspace_bytes(int64_t batch, int64_t frames, int64_t n_bins);
+int64_t ddsp_hip_pitch_viterbi_chunk_frames(int64_t n_bins);
+int ddsp_hip_pitch_viterbi(const float* cost, const float* f0c, float* f0, float* confidence, int32_t* path,
+                           void* workspace, size_t workspace_bytes, int64_t batch, int64_t frames, int64_t n_bins,
+                           int64_t max_jump, float transition, void* stream);
+
 /* ddsp_hip_stream_loudness and ddsp_hip_stream_pitch of one call in ONE launch over ONE state, for a stream whose
  * loudness and pitch use the same frame length L (n_fft == frame_length == L: the same frames of the same samples).
  * loudness_out [batch, R] holds ddsp_hip_stream_loudness(n_fft = L)'s bits and f0 / confidence / period [batch, R]

@@ -17,6 +17,11 @@ same definition (include/ddsp_hip.h, "pitch") composed from torch.fft and ATen o
 write today; the package had no pitch path before — and core.stream_pitch at the realtime shape, captured in a HIP
 graph.  DESIGN.md 3f-pitch records a run.
 
+``--leg viterbi`` times the Viterbi-decoded tracker (core.pitch_salience, core.viterbi_path, core.track_pitch:
+csrc/pitch_viterbi.hip) at the two offline shapes beside core.extract_pitch alone and beside the same definition
+(include/ddsp_hip.h, "pitch_viterbi") composed from torch.fft / ATen ops in fp64 with a per-frame torch loop for the
+recursion, and the decode alone on a minute of audio.  DESIGN.md 3f-viterbi records a run.
+
 ``--leg aligned`` times core.stream_analysis_mfcc (the streamed loudness, MFCC and pitch in one launch over one state,
 on one time axis) against core.stream_analysis + core.stream_mfcc as two launches on two states, and against
 core.stream_analysis alone, the same way.
@@ -56,9 +61,9 @@ def torch_mfcc(x, fb, dct, n_fft, hop, top_db=80.0):
     return (dct @ D).transpose(1, 2)
 
 
-def torch_pitch(x, sr, hop, L, tau_min, tau_max, threshold=0.1):
-    """include/ddsp_hip.h "pitch" as torch ops in fp64: the frames, their transforms, d, d' and the candidates all
-    go through memory.  -> (f0 [B, F] fp32, period [B, F])."""
+def torch_dprime(x, hop, L, tau_max):
+    """d' [B, F, tau_max + 2] of include/ddsp_hip.h "pitch" as torch ops in fp64: the frames, their transforms, d and
+    d' all go through memory."""
     W, F = L // 2, x.shape[1] // hop
     xp = torch.nn.functional.pad(x[:, None], (W, W), mode="reflect")[:, 0]
     Y = xp.unfold(1, L, hop)[:, :F].double()
@@ -73,6 +78,13 @@ def torch_pitch(x, sr, hop, L, tau_min, tau_max, threshold=0.1):
     tau = torch.arange(tau_max + 2, device=x.device, dtype=torch.float64)
     dn = torch.where(S > 0, d * tau / torch.where(S > 0, S, torch.ones_like(S)), torch.ones_like(S))
     dn[..., 0] = 1.0
+    return dn
+
+
+def torch_pitch(x, sr, hop, L, tau_min, tau_max, threshold=0.1):
+    """include/ddsp_hip.h "pitch" as torch ops in fp64 (the candidates too go through memory).
+    -> (f0 [B, F] fp32, period [B, F])."""
+    dn = torch_dprime(x, hop, L, tau_max)
     b, a, cn = dn[..., tau_min:tau_max + 1], dn[..., tau_min - 1:tau_max], dn[..., tau_min + 1:tau_max + 2]
     cand = (b < a) & (b <= cn) & (b < float(torch.tensor(threshold, dtype=torch.float32)))
     first = (torch.cumsum(cand, -1) == 0).sum(-1)
@@ -129,6 +141,91 @@ def pitch_leg(dev, reps, windows):
         print(json.dumps({"shape": "stream 1x1024 block 256", "leg": leg, "graph_nodes": launches,
                           "us": round(1e3 * med, 2), "us_min": round(1e3 * lo, 2), "us_max": round(1e3 * hi, 2)}),
               flush=True)
+
+
+def torch_salience(dn, sr, lo, hi):
+    """include/ddsp_hip.h "pitch_viterbi", the salience, as torch ops in fp64: dn [B, F, tau_max + 2], lo / hi [NB]
+    (long) -> (cost, f0c) fp32 [B, F, NB]."""
+    span = int((hi - lo).max()) + 1
+    idx = lo[:, None] + torch.arange(span, device=dn.device)[None, :]  # [NB, span]
+    inside = idx <= hi[:, None]
+    idx = torch.minimum(idx, hi[:, None])
+    v = dn[..., idx]                                                    # [B, F, NB, span]
+    v = torch.where(inside, v, torch.full_like(v, float("inf")))
+    ts = lo + v.argmin(-1)                                              # the first index of the minimum
+    a, b, cn = (dn.gather(-1, ts + o) for o in (-1, 0, 1))
+    curv = a - 2.0 * b + cn
+    ok = (b <= a) & (b <= cn) & (curv > 0)
+    s = torch.where(ok, 0.5 * (a - cn) / torch.where(ok, curv, torch.ones_like(curv)), torch.zeros_like(curv))
+    return b.clamp(max=1.0).float(), (sr / (ts + s)).float()
+
+
+def torch_viterbi(cost, f0c, lam, R):
+    """The decode as torch ops in fp64 with a per-frame loop for the recursion and another for the backtrack: what
+    a user would write today.  -> (f0, confidence, path) [B, F]."""
+    B, F, NB = cost.shape
+    lam = float(torch.tensor(lam, dtype=torch.float32))
+    pen = lam * torch.arange(-R, R + 1, device=cost.device).abs().double()
+    c = cost.double()
+    delta = c[:, 0]
+    back = torch.zeros(B, F, NB, dtype=torch.long, device=cost.device)
+    j = torch.arange(NB, device=cost.device)
+    for t in range(1, F):
+        padded = torch.nn.functional.pad(delta, (R, R), value=float("inf"))
+        v = padded.unfold(1, 2 * R + 1, 1) + pen                        # [B, NB, 2R + 1]: i = j + k - R
+        best, k = v.min(-1)                                             # (ties: the first, as argmin)
+        back[:, t] = j + k - R
+        delta = best + c[:, t]
+    path = torch.empty(B, F, dtype=torch.long, device=cost.device)
+    path[:, F - 1] = delta.argmin(-1)
+    for t in range(F - 1, 0, -1):
+        path[:, t - 1] = back[:, t].gather(-1, path[:, t:t + 1])[:, 0]
+    g = path[..., None]
+    return f0c.gather(-1, g)[..., 0], 1.0 - cost.gather(-1, g)[..., 0], path.int()
+
+
+def viterbi_leg(dev, reps, windows):
+    """core.pitch_salience, core.viterbi_path and their sum (core.track_pitch) at the two offline shapes, beside
+    core.extract_pitch alone and beside the same definition composed from torch.fft / ATen ops in fp64 with a
+    per-frame loop; then the decode alone on one item of 5625 frames (a minute of audio at block 512)."""
+    L, fmin, fmax, beta, lam, R = 2048, 50.0, 2000.0, 48, 0.02, 12
+    for name, B, T, hop, sr in SHAPES:
+        g = torch.Generator().manual_seed(B + T)
+        t = torch.arange(T) / sr
+        f = 110.0 * 2.0 ** (torch.arange(B)[:, None] / 8.0) * (1.0 + 0.005 * torch.sin(2 * torch.pi * 5.5 * t))[None, :]
+        phase = 2 * torch.pi * torch.cumsum(f.double(), 1) / sr
+        x = 0.2 * sum(torch.sin(h * phase) / h for h in range(1, 7)).float() + 0.003 * torch.randn(B, T, generator=g)
+        x = x.to(dev)
+        tau_min, tau_max, lo, hi = core.pitch_bins(sr, fmin, fmax, L, beta)
+        lo_d, hi_d = (torch.tensor(a, device=dev) for a in (lo, hi))
+        cost, f0c = core.pitch_salience(x, sr, hop)
+
+        def torch_track():
+            return torch_viterbi(*torch_salience(torch_dprime(x, hop, L, tau_max), sr, lo_d, hi_d), lam, R)
+
+        p_hip = core.track_pitch(x, sr, hop, return_path=True)[1]
+        p_t = torch_track()[2]
+        print(json.dumps({"shape": name, "frames": B * (T // hop), "bins": len(lo),
+                          "path_frames_that_differ": int((p_hip != p_t).sum())}), flush=True)
+        legs = [
+            ("salience hip", lambda: core.pitch_salience(x, sr, hop), reps),
+            ("decode hip", lambda: core.viterbi_path(cost, f0c, lam, R), reps),
+            ("track_pitch hip (salience + decode)", lambda: core.track_pitch(x, sr, hop), reps),
+            ("pitch hip (extract_pitch alone)", lambda: core.extract_pitch(x, sr, hop), reps),
+            ("track_pitch torch.fft + per-frame loop (fp64)", torch_track, 2),
+        ]
+        for leg, fn, n in legs:
+            med, lo_ms, hi_ms = timed(fn, n, windows)
+            print(json.dumps({"shape": name, "leg": leg, "reps": n, "ms": round(med, 4), "ms_min": round(lo_ms, 4),
+                              "ms_max": round(hi_ms, 4)}), flush=True)
+    F, NB = 5625, 256
+    g = torch.Generator().manual_seed(F)
+    cost = torch.rand(1, F, NB, generator=g).to(dev)
+    f0c = (50.0 + 1950.0 * torch.rand(1, F, NB, generator=g)).to(dev)
+    med, lo_ms, hi_ms = timed(lambda: core.viterbi_path(cost, f0c, lam, R), max(reps // 10, 5), windows)
+    print(json.dumps({"shape": f"decode 1x{F}x{NB}", "leg": "decode hip", "ms": round(med, 4),
+                      "ms_min": round(lo_ms, 4), "ms_max": round(hi_ms, 4),
+                      "us_per_frame": round(1e3 * med / F, 3)}), flush=True)
 
 
 def timed(fn, reps, windows):
@@ -271,8 +368,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=1000)
     ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--leg", choices=("offline", "stream", "pitch", "fused", "aligned", "all"), default="all",
-                    help="all: offline and stream (the pitch, fused and aligned legs run on request)")
+    ap.add_argument("--leg", choices=("offline", "stream", "pitch", "viterbi", "fused", "aligned", "all"), default="all",
+                    help="all: offline and stream (the pitch, viterbi, fused and aligned legs run on request)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_features: needs a HIP device (there is no CPU path)")
@@ -285,6 +382,9 @@ def main():
         return
     if args.leg == "pitch":
         pitch_leg(dev, args.reps, args.windows)
+        return
+    if args.leg == "viterbi":
+        viterbi_leg(dev, args.reps, args.windows)
         return
     if args.leg in ("stream", "all"):
         stream_leg(dev, args.reps, args.windows)

@@ -8,7 +8,8 @@ SRC := ddsp_pytorch_amd/csrc/synth.hip ddsp_pytorch_amd/csrc/noise.hip ddsp_pyto
        ddsp_pytorch_amd/csrc/gru.hip ddsp_pytorch_amd/csrc/dense.hip ddsp_pytorch_amd/csrc/stream.hip \
        ddsp_pytorch_amd/csrc/stream_reverb.hip ddsp_pytorch_amd/csrc/features.hip \
        ddsp_pytorch_amd/csrc/pitch.hip ddsp_pytorch_amd/csrc/stream_analysis.hip \
-       ddsp_pytorch_amd/csrc/stream_analysis_mfcc.hip ddsp_pytorch_amd/csrc/pitch_viterbi.hip
+       ddsp_pytorch_amd/csrc/stream_analysis_mfcc.hip ddsp_pytorch_amd/csrc/pitch_viterbi.hip \
+       ddsp_pytorch_amd/csrc/stream_pitch_viterbi.hip
 HDR := include/ddsp_hip.h ddsp_pytorch_amd/csrc/common.h ddsp_pytorch_amd/csrc/upols.h ddsp_pytorch_amd/csrc/fft_radix.h \
        ddsp_pytorch_amd/csrc/noise_dsp.h ddsp_pytorch_amd/csrc/stream_state.h ddsp_pytorch_amd/csrc/stft_frames.h \
        ddsp_pytorch_amd/csrc/fft_radix_f64.h ddsp_pytorch_amd/csrc/bf16x3.h ddsp_pytorch_amd/csrc/impulse.h \
@@ -38,9 +39,9 @@ build/twiddle4096_f64.inc: tools/gen_twiddles.py
 	@mkdir -p build
 	python3 tools/gen_twiddles.py 4096 f64 > $@
 
-build/features.o build/pitch.o build/pitch_viterbi.o build/stream_analysis.o build/stream_analysis_mfcc.o: build/twiddle4096_f64.inc
+build/features.o build/pitch.o build/pitch_viterbi.o build/stream_pitch_viterbi.o build/stream_analysis.o build/stream_analysis_mfcc.o: build/twiddle4096_f64.inc
 
-build/upols.o build/noise.o build/synth_frame.o build/backward.o build/stft.o build/stream_reverb.o build/features.o build/pitch.o build/pitch_viterbi.o build/stream_analysis.o build/stream_analysis_mfcc.o: build/twiddle4096.inc
+build/upols.o build/noise.o build/synth_frame.o build/backward.o build/stft.o build/stream_reverb.o build/features.o build/pitch.o build/pitch_viterbi.o build/stream_pitch_viterbi.o build/stream_analysis.o build/stream_analysis_mfcc.o: build/twiddle4096.inc
 
 build/%.o: ddsp_pytorch_amd/csrc/%.hip $(HDR)
 	@mkdir -p build

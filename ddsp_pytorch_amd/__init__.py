@@ -14,6 +14,8 @@ Drop-in for hugofloresgarcia/ddsp_pytorch's synthesis hot path:
   ``extract_pitch`` is the CREPE network, which this package does not carry), so ``analyze(signal, None, ...)``
   runs from audio alone; ``core.track_pitch`` (``analyze(..., viterbi=True)``): the same d' decoded over time by a
   Viterbi path, offline, as the reference's ``crepe.predict(..., viterbi=True)`` decodes its salience;
+  ``core.stream_track_pitch`` / ``StreamAnalyzer(viterbi=True)`` / ``RealtimeGraph(pitch_viterbi=True)``: the same
+  decode per call of a stream, its forward recursion carried on the device and its decision taken at a fixed lag;
   ``core.stream_analysis``: the streamed loudness and pitch in one launch over one state,
   which ``realtime.RealtimeGraph(loudness_from_audio=True, pitch_from_audio=True)`` runs per call (audio in,
   audio out); ``core.stream_analysis_mfcc`` / ``StreamAnalyzer(aligned=True)``: the streamed loudness, MFCC and pitch

@@ -125,6 +125,11 @@ SIGNATURES = {
     "ddsp_hip_pitch_viterbi_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "ddsp_hip_pitch_viterbi_chunk_frames": (_I64, [_I64]),
     "ddsp_hip_pitch_viterbi": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64, _F, _P]),
+    # the same per call of a stream: the salience of the call's frames, then the carried fixed-lag decode
+    "ddsp_hip_stream_pitch_salience": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64,
+                                            _I64, _I64, _I64, _F, _F, _P]),
+    "ddsp_hip_stream_viterbi_state_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "ddsp_hip_stream_pitch_viterbi": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64, _I64, _F, _P]),
     # streamed loudness + pitch of one call in one launch over one state
     "ddsp_hip_stream_analysis": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I64, _I64, _I64, _I64, _I64, _I64, _F, _F,
                                       _P]),

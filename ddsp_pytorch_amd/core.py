@@ -31,6 +31,8 @@ __all__ = [
     "extract_loudness", "mfcc", "FeatureStreamState", "stream_loudness", "stream_mfcc", "stream_feature_delay",
     "extract_pitch", "stream_pitch", "pitch_lags", "stream_analysis", "stream_analysis_mfcc",
     "pitch_bins", "pitch_salience", "viterbi_path", "track_pitch",
+    "ViterbiStreamState", "stream_pitch_salience", "stream_viterbi_path", "stream_track_pitch",
+    "stream_pitch_bin_count",
 ]
 
 
@@ -1138,7 +1140,8 @@ def track_pitch(signal, sample_rate, block_size, fmin=50.0, fmax=2000.0, frame_l
     and the path's bins, int32).  Where ``extract_pitch`` takes each frame's first dip on its own and jumps an octave
     when a harmonic outweighs the fundamental, the decode pays ``transition`` per bin (1 / ``bins_per_octave``
     octave) moved between frames, which is what ``viterbi=True`` buys the reference's CREPE track.  Offline only (the
-    decode needs the whole signal); two launches, no host synchronisation after the first call.  No autograd."""
+    decode needs the whole signal; ``stream_track_pitch`` is its fixed-lag form for a stream); two launches, no host
+    synchronisation after the first call.  No autograd."""
     one_d = signal.dim() == 1
     cost, f0c = pitch_salience(signal.unsqueeze(0) if one_d else signal, sample_rate, block_size, fmin=fmin,
                                fmax=fmax, frame_length=frame_length, bins_per_octave=bins_per_octave)
@@ -1472,6 +1475,113 @@ def stream_analysis_mfcc(x, sample_rate, block_size, state, pitch=True, fmin=50.
               state.buf.numel(), B, N, L, M, int(block_size), int(n_mels), int(n_mfcc), float(top_db), tau_min,
               tau_max, float(sample_rate), float(threshold), _lib.stream_of(xc))
     return (loud, out) + tuple(t for t in (f0, conf, period) if t is not None)
+
+
+# ------------------------------------------------------------------------------------
+# streamed Viterbi pitch (ddsp_hip_stream_pitch_salience / ddsp_hip_stream_pitch_viterbi): ``track_pitch`` for a
+# stream.  The decode's forward recursion is causal; carried from call to call it gives, at every frame n, the offline
+# decode of frames 0 .. n, and its element n - lag is a decision at a fixed, small lag (lag 0: none at all).
+# ------------------------------------------------------------------------------------
+class ViterbiStreamState:
+    """The device state of one streamed Viterbi decode (include/ddsp_hip.h, "pitch_viterbi_stream"): ``buf`` (uint8,
+    ddsp_hip_stream_viterbi_state_bytes: per item the two fp64 rows of delta, then a ring of ``lag`` +
+    ``frames_per_call`` frames of f0c, cost and back-offsets) and ``counter`` (int64[1], the call index).
+    Zero-filled is a fresh stream.  ``counter``: another state's counter tensor to share (the salience's ring's, a
+    ``StreamState``'s), so that one ``stream_advance`` ends the call for all of them; ``reset()`` then zeroes it for
+    all."""
+
+    def __init__(self, batch, device, frames_per_call, n_bins, lag=0, counter=None):
+        self.batch, self.frames, self.n_bins, self.lag = int(batch), int(frames_per_call), int(n_bins), int(lag)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("ddsp_hip: the stream state lives on a HIP device (no CPU fallback)")
+        if self.batch < 1:
+            raise RuntimeError("ViterbiStreamState: batch must be at least 1")
+        nbytes = int(_lib.query("stream_viterbi_state_bytes", self.batch, self.frames, self.n_bins, self.lag))
+        if nbytes == 0:
+            raise RuntimeError("ViterbiStreamState: 1 to 32 frames per call, 1 to 1024 bins and a lag of 0 to 64 "
+                               f"frames; got {self.frames} frames, {self.n_bins} bins, lag {self.lag}")
+        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        if counter is None:
+            counter = torch.zeros(1, dtype=torch.int64, device=device)
+        elif counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != self.buf.device:
+            raise RuntimeError("ViterbiStreamState: counter must be an int64[1] tensor on the state's device")
+        self.counter = counter
+
+    def reset(self):
+        self.buf.zero_()
+        self.counter.zero_()
+
+
+def stream_pitch_salience(x, sample_rate, block_size, state, fmin=50.0, fmax=2000.0, frame_length=2048,
+                          bins_per_octave=48, return_lag=False, return_raw=False, threshold=0.1):
+    """``pitch_salience`` for one call of a stream: x [B, N] or [B, N, 1] -> (cost, f0c[, lag]), each
+    [B, N // block_size, n_bins], of the frames the call completes — the stream's own frames, ``stream_pitch``'s.
+    ``return_raw``: also ``stream_pitch``'s (f0, confidence, period) for ``threshold``, bit for bit, out of the same
+    launch.  ``state``: a ``FeatureStreamState(B, device, N, frame_length, block_size)`` of its own; the call reads
+    its counter and writes its ring, ``stream_advance`` ends the call.  One launch; bin tables cached as
+    ``pitch_salience``'s, no host synchronisation after the first call."""
+    L = int(frame_length)
+    xc = _stream_call_rows(x, state, block_size, L, "stream_pitch_salience")
+    tau_min, tau_max, lo, hi = _pitch_bin_tables(sample_rate, fmin, fmax, L, bins_per_octave, xc.device)
+    B, N = xc.shape
+    R, NB = state.frames, lo.numel()
+    cost = torch.empty(B, R, NB, dtype=torch.float32, device=xc.device)
+    f0c = torch.empty_like(cost)
+    lag = torch.empty(B, R, NB, dtype=torch.int32, device=xc.device) if return_lag else None
+    raw = _pitch_outputs(B, R, xc.device, True, True) if return_raw else (None, None, None)
+    _lib.call("stream_pitch_salience", _lib.ptr(xc), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(cost), _lib.ptr(f0c),
+              _lib.ptr(lag), _lib.ptr(raw[0]), _lib.ptr(raw[1]), _lib.ptr(raw[2]), _lib.ptr(state.counter),
+              _lib.ptr(state.buf), state.buf.numel(), B, N, L, int(block_size), tau_min, tau_max, NB,
+              float(sample_rate), float(threshold), _lib.stream_of(xc))
+    return tuple(t for t in (cost, f0c, lag) + tuple(raw) if t is not None)
+
+
+def stream_viterbi_path(cost, f0c, state, transition=0.02, max_jump=12):
+    """One call of the carried decode (include/ddsp_hip.h, "pitch_viterbi_stream"): cost, f0c [B, R, n_bins] (HIP,
+    fp32) of the call's frames -> (f0, confidence, path), each [B, R]: for emitted frame n = k R + j the decision
+    ``state.lag`` frames back, which is element n - lag of ``viterbi_path`` over frames 0 .. n (before frame ``lag``:
+    element 0).  ``state``: a ``ViterbiStreamState(B, device, R, n_bins, lag)``; the call reads its counter and
+    writes its rows and ring, ``stream_advance`` ends the call, and a call run twice before it gives the same bits.
+    One launch, one workgroup per item; no host synchronisation.  No autograd."""
+    _dev(cost, f0c)
+    if cost.dim() != 3 or cost.shape != f0c.shape:
+        raise RuntimeError(f"stream_viterbi_path: cost and f0c must both be [batch, frames, bins], got "
+                           f"{tuple(cost.shape)} and {tuple(f0c.shape)}")
+    B, R, NB = cost.shape
+    if (state.batch, state.frames, state.n_bins) != (B, R, NB) or state.buf.device != cost.device:
+        raise RuntimeError("stream_viterbi_path: the decode state is for another batch, frames per call, bin count "
+                           "or device")
+    c, g = _c(cost.detach()), _c(f0c.detach())
+    f0 = torch.empty(B, R, dtype=torch.float32, device=c.device)
+    conf = torch.empty_like(f0)
+    path = torch.empty(B, R, dtype=torch.int32, device=c.device)
+    _lib.call("stream_pitch_viterbi", _lib.ptr(c), _lib.ptr(g), _lib.ptr(f0), _lib.ptr(conf), _lib.ptr(path),
+              _lib.ptr(state.counter), _lib.ptr(state.buf), state.buf.numel(), B, R, NB, int(max_jump), state.lag,
+              float(transition), _lib.stream_of(c))
+    return f0, conf, path
+
+
+def stream_track_pitch(x, sample_rate, block_size, ring_state, viterbi_state, fmin=50.0, fmax=2000.0,
+                       frame_length=2048, bins_per_octave=48, transition=0.02, max_jump=12, return_confidence=False,
+                       return_path=False):
+    """``track_pitch`` for one call of a stream: ``stream_pitch_salience`` over ``ring_state`` then
+    ``stream_viterbi_path`` over ``viterbi_state`` — x [B, N] or [B, N, 1] -> f0 [B, N // block_size] (and on
+    request the confidence and the path's bins).  Slot j of call k is the decision for stream frame
+    k R - ring_state.delay_frames + j - viterbi_state.lag: the streamed features' delay plus the decode's lag (0
+    already removes the octave jumps of ``stream_pitch``; a few frames bring the decision to the offline path's).
+    The two states share a counter (``ViterbiStreamState(..., counter=ring_state.counter)``) or are advanced
+    together; ``stream_advance`` ends the call.  Two launches, no host synchronisation after the first call."""
+    cost, f0c = stream_pitch_salience(x, sample_rate, block_size, ring_state, fmin=fmin, fmax=fmax,
+                                      frame_length=frame_length, bins_per_octave=bins_per_octave)
+    f0, conf, path = stream_viterbi_path(cost, f0c, viterbi_state, transition=transition, max_jump=max_jump)
+    return _pitch_result(f0, conf if return_confidence else None, path if return_path else None, False)
+
+
+def stream_pitch_bin_count(sample_rate, fmin=50.0, fmax=2000.0, frame_length=2048, bins_per_octave=48):
+    """n_bins of ``pitch_bins`` for these parameters: what a ``ViterbiStreamState`` is sized by."""
+    tau_min, tau_max = pitch_lags(sample_rate, fmin, fmax, frame_length)
+    return len(_pitch_bin_arrays(tau_min, tau_max, bins_per_octave)[0])
 
 
 from . import grad as _grad  # noqa: E402  (autograd Functions over the backward kernels)

@@ -271,6 +271,40 @@ __device__ __forceinline__ void yin_frame(const Fetch& fetch, int f, int t, doub
   yin_pick<N>(dn, t, lds, wsum, rint, p, write, o, f0, conf, period);
 }
 
+// ---------------- pitch_viterbi: the salience of one frame (include/ddsp_hip.h, "pitch_viterbi") ----------------
+constexpr int kMaxBins = 1024;  // n_bins cap: the decodes run one thread per bin
+constexpr int kMaxJump = 127;   // max_jump cap: the back-offsets are int8
+
+// The salience of one frame from its d' in LDS (yin_dprime's): bins t, t + Q, ... of the transform's Q threads; the
+// offline and the streamed salience kernels (pitch_viterbi.hip, stream_pitch_viterbi.hip) share it.
+template <int N>
+__device__ __forceinline__ void salience_bins(const double* dp, int t, const PitchParams& p,
+                                              const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
+                                              int n_bins, int64_t o, float* __restrict__ cost,
+                                              float* __restrict__ f0c, int32_t* __restrict__ lag) {
+  constexpr int Q = N / 16;
+  for (int i = t; i < n_bins; i += Q) {
+    const int l = min(max(lo[i], p.tau_min), p.tau_max);
+    const int h = min(max(hi[i], l), p.tau_max);
+    int ts = l;
+    double b = dp[l];
+    for (int tau = l + 1; tau <= h; ++tau) {
+      const double v = dp[tau];
+      if (v < b) {
+        b = v;
+        ts = tau;
+      }
+    }
+    const double a = dp[ts - 1], c = dp[ts + 1];
+    const double curv = a - 2.0 * b + c;
+    double s = 0.0;
+    if (b <= a && b <= c && curv > 0.0) s = 0.5 * (a - c) / curv;
+    cost[o + i] = (float)fmin(1.0, b);
+    f0c[o + i] = (float)((double)p.sample_rate / ((double)ts + s));
+    if (lag) lag[o + i] = ts;
+  }
+}
+
 // The parameters the pitch entry points share (include/ddsp_hip.h), checked before any HIP call.
 inline int check_pitch_params(int64_t L, int64_t tau_min, int64_t tau_max, float sample_rate) {
   if (L < kPitchMinFrame || L > 4096 || (L & (L - 1))) return DDSP_HIP_ERANGE;

@@ -19,8 +19,6 @@
 namespace ddsp {
 namespace {
 
-constexpr int kMaxBins = 1024;                 // n_bins cap: one thread per bin
-constexpr int kMaxJump = 127;                  // max_jump cap: the back-offsets are int8
 constexpr int kViterbiChunkBytes = 32 * 1024;  // back-offsets staged per backtrack chunk
 constexpr int kViterbiMaxChunk = 512;          // frames per chunk at most (the chunk's path in LDS)
 
@@ -28,35 +26,6 @@ constexpr int kViterbiMaxChunk = 512;          // frames per chunk at most (the 
 __host__ __device__ inline int viterbi_chunk_frames(int n_bins) {
   const int g = kViterbiChunkBytes / n_bins;
   return g < kViterbiMaxChunk ? g : kViterbiMaxChunk;
-}
-
-// The salience of one frame from its d' in LDS: bins t, t + Q, ... of the transform's Q threads.
-template <int N>
-__device__ __forceinline__ void salience_bins(const double* dp, int t, const PitchParams& p,
-                                              const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
-                                              int n_bins, int64_t o, float* __restrict__ cost,
-                                              float* __restrict__ f0c, int32_t* __restrict__ lag) {
-  constexpr int Q = N / 16;
-  for (int i = t; i < n_bins; i += Q) {
-    const int l = min(max(lo[i], p.tau_min), p.tau_max);
-    const int h = min(max(hi[i], l), p.tau_max);
-    int ts = l;
-    double b = dp[l];
-    for (int tau = l + 1; tau <= h; ++tau) {
-      const double v = dp[tau];
-      if (v < b) {
-        b = v;
-        ts = tau;
-      }
-    }
-    const double a = dp[ts - 1], c = dp[ts + 1];
-    const double curv = a - 2.0 * b + c;
-    double s = 0.0;
-    if (b <= a && b <= c && curv > 0.0) s = 0.5 * (a - c) / curv;
-    cost[o + i] = (float)fmin(1.0, b);
-    f0c[o + i] = (float)((double)p.sample_rate / ((double)ts + s));
-    if (lag) lag[o + i] = ts;
-  }
 }
 
 // grid (ceil(frames / (kPoints/N)), B), kPoints/16 threads; cost / f0c / lag [B, frames, n_bins], f0 / conf /

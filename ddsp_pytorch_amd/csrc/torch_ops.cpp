@@ -581,6 +581,55 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_viterbi(const at::Tensor& c
   return {f0, conf, path};
 }
 
+// ---------------- pitch_viterbi_stream: the same per call of a stream (ddsp_hip_stream_pitch_salience / _viterbi) ----
+// -> (cost, f0c, lag), each [B, R, n_bins]
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_salience_stream(const at::Tensor& x, const at::Tensor& lo,
+                                                                     const at::Tensor& hi, int64_t frame_length,
+                                                                     int64_t hop, int64_t tau_min, int64_t tau_max,
+                                                                     double sample_rate, const at::Tensor& counter,
+                                                                     at::Tensor& state) {
+  at::Tensor xc = call_rows(x, "pitch_salience_stream");
+  check_stream(counter, state, xc);
+  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "pitch_salience_stream: call_samples must be a multiple of hop");
+  for (const at::Tensor* t : {&lo, &hi})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->dim() == 1 && t->numel() == lo.numel(),
+                "pitch_salience_stream: lo and hi must be int32 HIP tensors of n_bins values");
+  at::Tensor l = lo.contiguous(), h = hi.contiguous();
+  const int64_t B = xc.size(0), N = xc.size(1), NB = l.numel();
+  at::Tensor cost = at::empty({B, N / hop, NB}, xc.options());
+  at::Tensor f0c = at::empty_like(cost);
+  at::Tensor lag = at::empty({B, N / hop, NB}, xc.options().dtype(at::kInt));
+  ok(ddsp_hip_stream_pitch_salience(xc.data_ptr<float>(), l.data_ptr<int32_t>(), h.data_ptr<int32_t>(),
+                                    cost.data_ptr<float>(), f0c.data_ptr<float>(), lag.data_ptr<int32_t>(), nullptr,
+                                    nullptr, nullptr, reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()),
+                                    state.data_ptr(), (size_t)state.numel(), B, N, frame_length, hop, tau_min, tau_max,
+                                    NB, (float)sample_rate, 0.0f, stream_of(xc)),
+     "stream_pitch_salience");
+  return {cost, f0c, lag};
+}
+
+// cost, f0c [B, R, n_bins] of one call -> (f0, confidence, path), each [B, R], `lag` frames back
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_viterbi_stream(const at::Tensor& cost, const at::Tensor& f0c,
+                                                                    double transition, int64_t max_jump, int64_t lag,
+                                                                    const at::Tensor& counter, at::Tensor& state) {
+  check_dev(cost, "cost");
+  check_dev(f0c, "f0c");
+  check_stream(counter, state, cost);
+  TORCH_CHECK(cost.dim() == 3 && cost.sizes() == f0c.sizes() && cost.size(2) >= 1,
+              "pitch_viterbi_stream: cost and f0c must both be [batch, frames, bins]");
+  at::Tensor c = cost.contiguous(), g = f0c.contiguous();
+  const int64_t B = c.size(0), R = c.size(1), NB = c.size(2);
+  at::Tensor f0 = at::empty({B, R}, c.options());
+  at::Tensor conf = at::empty_like(f0);
+  at::Tensor path = at::empty({B, R}, c.options().dtype(at::kInt));
+  ok(ddsp_hip_stream_pitch_viterbi(c.data_ptr<float>(), g.data_ptr<float>(), f0.data_ptr<float>(),
+                                   conf.data_ptr<float>(), path.data_ptr<int32_t>(),
+                                   reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
+                                   (size_t)state.numel(), B, R, NB, max_jump, lag, (float)transition, stream_of(c)),
+     "stream_pitch_viterbi");
+  return {f0, conf, path};
+}
+
 // loudness_stream + pitch_stream in one launch over one state (ddsp_hip_stream_analysis)
 // -> (loudness, f0, confidence, period)
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> analysis_stream(
@@ -722,6 +771,10 @@ TORCH_LIBRARY(ddsp_hip, m) {
   m.def("pitch_salience(Tensor x, Tensor lo, Tensor hi, int frame_length, int hop, int tau_min, int tau_max,"
         " float sample_rate) -> (Tensor, Tensor, Tensor)");
   m.def("pitch_viterbi(Tensor cost, Tensor f0c, float transition, int max_jump) -> (Tensor, Tensor, Tensor)");
+  m.def("pitch_salience_stream(Tensor x, Tensor lo, Tensor hi, int frame_length, int hop, int tau_min, int tau_max,"
+        " float sample_rate, Tensor counter, Tensor(a!) state) -> (Tensor, Tensor, Tensor)");
+  m.def("pitch_viterbi_stream(Tensor cost, Tensor f0c, float transition, int max_jump, int lag, Tensor counter,"
+        " Tensor(a!) state) -> (Tensor, Tensor, Tensor)");
   m.def("analysis_stream(Tensor x, Tensor? weights, int frame_length, int hop, int tau_min, int tau_max,"
         " float sample_rate, float threshold, Tensor counter, Tensor(a!) state) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("analysis_mfcc_stream(Tensor x, Tensor? weights, Tensor band_start, Tensor band_count, Tensor band_weights,"
@@ -759,6 +812,8 @@ TORCH_LIBRARY_IMPL(ddsp_hip, CUDA, m) {  // HIP tensors dispatch under the CUDA 
   m.impl("pitch_stream", &pitch_stream);
   m.impl("pitch_salience", &pitch_salience);
   m.impl("pitch_viterbi", &pitch_viterbi);
+  m.impl("pitch_salience_stream", &pitch_salience_stream);
+  m.impl("pitch_viterbi_stream", &pitch_viterbi_stream);
   m.impl("analysis_stream", &analysis_stream);
   m.impl("analysis_mfcc_stream", &analysis_mfcc_stream);
 }

@@ -10,8 +10,8 @@ can be passed in as before, and without one ``analyze`` computes f0 on the devic
 
 ``StreamAnalyzer`` is the same front end for a realtime stream: audio comes in call by call and each call returns
 the frames it completes (``core.stream_loudness``, ``core.stream_mfcc`` and, on request, ``core.stream_pitch``;
-``aligned=True``: all of them from one launch on one time axis, ``core.stream_analysis_mfcc``), the history
-carried on the device.
+``aligned=True``: all of them from one launch on one time axis, ``core.stream_analysis_mfcc``; ``viterbi=True``: the
+pitch from the streamed Viterbi decode, ``core.stream_track_pitch``), the history carried on the device.
 """
 import torch
 
@@ -67,6 +67,15 @@ class StreamAnalyzer:
     ``pitch_state`` too), the MFCC window centred in the loudness's, so that ``delay_frames['mfcc'] ==
     delay_frames['loudness']`` — what a model that consumes all three per frame needs.  The MFCC's top_db clamp is
     causal (``core.stream_mfcc``).
+    ``viterbi=True`` (needs ``pitch=True``): ``'pitch'`` and ``'confidence'`` come from the streamed Viterbi decode
+    (``core.stream_track_pitch``: the salience of the call's frames, then the carried decode with its decision
+    ``pitch_lag`` frames back; ``pitch_transition`` per bin moved, at most ``pitch_max_jump`` bins a frame), which
+    removes the octave jumps the per-frame pick makes under a strong second harmonic — at ``pitch_lag=0`` with no
+    added latency; ``delay_frames['pitch']`` grows by ``pitch_lag``.  In this first cut the decode does not ride in
+    the fused kernels, which are untouched: the loudness (``aligned=True``: the loudness and the MFCC, from
+    ``core.stream_analysis_mfcc(pitch=False)``) comes from its existing launch, and the pitch from the two new
+    launches over a pitch ring of its own (``pitch_state``) and the decode state (``viterbi_state``), on the shared
+    counter.  ``fused=True`` is the loudness and the per-frame pick in one launch and is refused with ``viterbi``.
     ``mean_loudness`` / ``std_loudness`` as in ``analyze``.  After one warm-up call (the tables) nothing
     synchronises with the host: a call can be captured in a HIP graph over a static input buffer.  ``counter``: a
     stream counter to share (e.g. a ``core.StreamState``'s), with ``advance=False`` when that stream's own advance
@@ -76,12 +85,17 @@ class StreamAnalyzer:
 
     def __init__(self, sample_rate, block_size, call_samples, batch=1, device="cuda", mean_loudness=None,
                  std_loudness=None, counter=None, advance=True, pitch=False, fmin=50.0, fmax=2000.0, fused=False,
-                 aligned=False):
+                 aligned=False, viterbi=False, pitch_lag=0, pitch_transition=0.02, pitch_max_jump=12):
         if (mean_loudness is None) != (std_loudness is None):
             raise ValueError("StreamAnalyzer: mean_loudness and std_loudness go together")
         if fused and not pitch:
             raise ValueError("StreamAnalyzer: fused=True is the loudness and the pitch in one launch; it needs "
                              "pitch=True")
+        if viterbi and not pitch:
+            raise ValueError("StreamAnalyzer: viterbi=True decodes the pitch; it needs pitch=True")
+        if viterbi and fused:
+            raise ValueError("StreamAnalyzer: fused=True is the loudness and the per-frame pitch in one launch; "
+                             "viterbi=True takes the pitch from the salience and the decode instead")
         self.sample_rate, self.block_size, self.call_samples = float(sample_rate), int(block_size), int(call_samples)
         self.mean_loudness, self.std_loudness = mean_loudness, std_loudness
         self.advance = bool(advance)
@@ -96,9 +110,18 @@ class StreamAnalyzer:
                                                       counter=self.counter)
         self.delay_frames = {"loudness": self.loudness_state.delay_frames, "mfcc": self.mfcc_state.delay_frames}
         self.pitch, self.fmin, self.fmax = bool(pitch), float(fmin), float(fmax)
-        self.fused = bool(fused) or (self.aligned and self.pitch)
-        self.pitch_state = None
-        if self.pitch:
+        self.viterbi, self.pitch_lag = bool(viterbi), int(pitch_lag)
+        self.pitch_transition, self.pitch_max_jump = float(pitch_transition), int(pitch_max_jump)
+        self.fused = bool(fused) or (self.aligned and self.pitch and not self.viterbi)
+        self.pitch_state = self.viterbi_state = None
+        if self.viterbi:  # a pitch ring of its own and the decode state, both on the shared counter
+            n_bins = core.stream_pitch_bin_count(sample_rate, fmin, fmax, self.N_FFT["pitch"])
+            self.pitch_state = core.FeatureStreamState(batch, device, call_samples, self.N_FFT["pitch"], block_size,
+                                                       counter=self.counter)
+            self.viterbi_state = core.ViterbiStreamState(batch, device, self.pitch_state.frames, n_bins,
+                                                         self.pitch_lag, counter=self.counter)
+            self.delay_frames["pitch"] = self.pitch_state.delay_frames + self.pitch_lag
+        elif self.pitch:
             core.pitch_lags(sample_rate, fmin, fmax, self.N_FFT["pitch"])  # a bad range is refused here
             if self.fused:  # one ring for both: the same frames of the same samples
                 if self.N_FFT["pitch"] != self.N_FFT["loudness"]:
@@ -117,17 +140,19 @@ class StreamAnalyzer:
             self.mfcc_state.reset()
         if self.pitch_state is not None and self.pitch_state is not self.loudness_state:
             self.pitch_state.reset()
+        if self.viterbi_state is not None:
+            self.viterbi_state.reset()
 
     @torch.no_grad()
     def __call__(self, audio):
         f0 = conf = mfcc = None
         if self.aligned:
             got = core.stream_analysis_mfcc(audio, self.sample_rate, self.block_size, self.loudness_state,
-                                            pitch=self.pitch, fmin=self.fmin, fmax=self.fmax,
-                                            frame_length=self.N_FFT["loudness"], return_confidence=self.pitch,
+                                            pitch=self.fused, fmin=self.fmin, fmax=self.fmax,
+                                            frame_length=self.N_FFT["loudness"], return_confidence=self.fused,
                                             mfcc_n_fft=self.N_FFT["mfcc"])
             loudness, mfcc = got[:2]
-            if self.pitch:
+            if self.fused:
                 f0, conf = got[2:]
         elif self.fused:
             loudness, f0, conf = core.stream_analysis(audio, self.sample_rate, self.block_size, self.loudness_state,
@@ -143,7 +168,13 @@ class StreamAnalyzer:
                                     n_fft=self.N_FFT["mfcc"])
         out = {"loudness": loudness.unsqueeze(-1), "mfcc": mfcc}
         if self.pitch:
-            if not self.fused:
+            if self.viterbi:
+                f0, conf = core.stream_track_pitch(audio, self.sample_rate, self.block_size, self.pitch_state,
+                                                   self.viterbi_state, fmin=self.fmin, fmax=self.fmax,
+                                                   frame_length=self.N_FFT["pitch"],
+                                                   transition=self.pitch_transition, max_jump=self.pitch_max_jump,
+                                                   return_confidence=True)
+            elif not self.fused:
                 f0, conf = core.stream_pitch(audio, self.sample_rate, self.block_size, self.pitch_state,
                                              fmin=self.fmin, fmax=self.fmax, frame_length=self.N_FFT["pitch"],
                                              return_confidence=True)

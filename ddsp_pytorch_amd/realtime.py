@@ -84,6 +84,17 @@ class RealtimeGraph:
     gate on.  Nothing holds or smooths f0: an unvoiced or silent frame carries YIN's value as it is (a silent frame
     gives sample_rate / tau_min with confidence 0), and the instrument is then as quiet as its loudness says.
 
+    ``pitch_viterbi=True`` (needs ``pitch_from_audio=True``; decoder or autoencoder, with or without ``continuous`` /
+    ``reverb``): the graph's f0 is the streamed Viterbi decode's (`core.stream_track_pitch`: ``pitch_transition`` per
+    bin moved, at most ``pitch_max_jump`` bins a frame, the decision ``pitch_lag`` frames back), so an octave jump of
+    the per-frame pick under a strong second harmonic no longer passes through the control network and the
+    oscillator bank as a one-frame yodel.  The analysis launch then computes the loudness (and the MFCC) without the
+    pitch, and two more launches — the salience over a pitch ring of its own, `self.pitch_ring`, and the carried
+    decode, `self.viterbi` — give `self.f0` and `self.confidence` (1 - d' along the path).
+    `pitch_delay_samples == loudness_delay_samples + pitch_lag * block_size`; the loudness is NOT delayed to match
+    (the stance above for an external pitch), and ``pitch_lag=0``, the default, adds no latency.  `reset()` gives a
+    fresh decode.
+
     A ``DDSPAutoencoder`` (recognised by ``model.decoder.add_z`` and ``model.encoder``) needs
     ``loudness_from_audio=True``: its encoder's MFCC can only come from audio.  With ``pitch_from_audio=True``
     ``__call__(audio)`` is audio in, audio out; without it ``__call__(pitch, audio)``; ``continuous`` / ``reverb`` as for
@@ -104,7 +115,8 @@ class RealtimeGraph:
     def __init__(self, model, call_samples=1024, mean_loudness=0.0, std_loudness=1.0,
                  seed=0x5EEDDD5B, device=None, warmup=3, fused=True, gru_route="steps",
                  continuous=False, reverb=False, wrap=None, loudness_from_audio=False, pitch_from_audio=False,
-                 pitch_fmin=50.0, pitch_fmax=2000.0, pitch_threshold=0.1):
+                 pitch_fmin=50.0, pitch_fmax=2000.0, pitch_threshold=0.1, pitch_viterbi=False, pitch_lag=0,
+                 pitch_transition=0.02, pitch_max_jump=12):
         device = torch.device(device) if device is not None else next(model.parameters()).device
         if device.type != "cuda":
             raise RuntimeError("RealtimeGraph: the model must be on a HIP device")
@@ -164,6 +176,18 @@ class RealtimeGraph:
                                    "computes both from the same frames of the same ring)")
             core.pitch_lags(self.sample_rate, self.pitch_fmin, self.pitch_fmax, self.analysis.n_fft)  # a bad range
             self.pitch_delay_samples = self.loudness_delay_samples
+        self.pitch_viterbi, self.pitch_lag = bool(pitch_viterbi), int(pitch_lag)
+        self.pitch_transition, self.pitch_max_jump = float(pitch_transition), int(pitch_max_jump)
+        self.pitch_ring = self.viterbi = None
+        if self.pitch_viterbi:
+            if not self.pitch_from_audio:
+                raise RuntimeError("RealtimeGraph: pitch_viterbi=True decodes the pitch computed from the audio; it "
+                                   "needs pitch_from_audio=True")
+            n_bins = core.stream_pitch_bin_count(self.sample_rate, self.pitch_fmin, self.pitch_fmax,
+                                                 self.analysis.n_fft)
+            self.pitch_ring = core.FeatureStreamState(1, device, N, self.analysis.n_fft, bs, counter=self.counter)
+            self.viterbi = core.ViterbiStreamState(1, device, N // bs, n_bins, self.pitch_lag, counter=self.counter)
+            self.pitch_delay_samples = self.loudness_delay_samples + self.pitch_lag * bs
         self.mfcc_delay_samples = 0
         self.z = self.mfcc = self.encoder_state = None
         if self.autoencoder:  # the encoder GRU's carried state is this object's: the model's state_dict stays as it is
@@ -197,6 +221,9 @@ class RealtimeGraph:
             self.stream.reset()
         if self.analysis is not None:
             self.analysis.reset()
+        if self.viterbi is not None:
+            self.pitch_ring.reset()
+            self.viterbi.reset()
 
     def refresh(self):
         """Rebuild the streamed reverb's IR spectra from the model's reverb parameters (in place: the
@@ -225,22 +252,32 @@ class RealtimeGraph:
         """The call's pitch and loudness, one value per frame: (pitch, its stride, loudness, its stride) — the
         inputs decimated by block_size; with ``loudness_from_audio`` the loudness is the streamed analysis of the
         audio in the loudness buffer (stride 1); with ``pitch_from_audio`` both come from that audio in one launch,
-        and the call's f0 and confidence stay in ``self.f0`` / ``self.confidence``."""
+        and the call's f0 and confidence stay in ``self.f0`` / ``self.confidence``; with ``pitch_viterbi`` that launch
+        leaves the pitch out and the salience and the carried decode give them."""
         if not self.loudness_from_audio:
             return self.pitch, self.block_size, self.loudness, self.block_size
+        raw_pitch = self.pitch_from_audio and not self.pitch_viterbi  # the per-frame pick, in the analysis launch
+        if self.pitch_viterbi:
+            self.f0, self.confidence = core.stream_track_pitch(
+                self.loudness, self.sample_rate, self.block_size, self.pitch_ring, self.viterbi, fmin=self.pitch_fmin,
+                fmax=self.pitch_fmax, frame_length=self.analysis.n_fft, transition=self.pitch_transition,
+                max_jump=self.pitch_max_jump, return_confidence=True)
         if self.autoencoder:  # one launch, one ring, one time axis: the loudness, the MFCC and (from audio) the pitch
             got = core.stream_analysis_mfcc(
-                self.loudness, self.sample_rate, self.block_size, self.analysis, pitch=self.pitch_from_audio,
+                self.loudness, self.sample_rate, self.block_size, self.analysis, pitch=raw_pitch,
                 fmin=self.pitch_fmin, fmax=self.pitch_fmax, frame_length=self.analysis.n_fft,
-                threshold=self.pitch_threshold, return_confidence=self.pitch_from_audio,
+                threshold=self.pitch_threshold, return_confidence=raw_pitch,
                 n_mfcc=self.model.encoder.gru.input_size)
             loud, self.mfcc = got[:2]
             if not self.pitch_from_audio:
                 return self.pitch, self.block_size, loud, 1
-            self.f0, self.confidence = got[2:]
+            if raw_pitch:
+                self.f0, self.confidence = got[2:]
             return self.f0, 1, loud, 1
-        if not self.pitch_from_audio:
+        if not raw_pitch:
             loud = core.stream_loudness(self.loudness, self.sample_rate, self.block_size, self.analysis)
+            if self.pitch_viterbi:
+                return self.f0, 1, loud, 1
             return self.pitch, self.block_size, loud, 1
         loud, self.f0, self.confidence = core.stream_analysis(
             self.loudness, self.sample_rate, self.block_size, self.analysis, fmin=self.pitch_fmin,
@@ -360,6 +397,9 @@ class RealtimeGraph:
             self.stream.reset()
         if self.analysis is not None:
             self.analysis.reset()
+        if self.viterbi is not None:
+            self.pitch_ring.reset()
+            self.viterbi.reset()
 
     @torch.no_grad()
     def __call__(self, pitch, loudness=None):

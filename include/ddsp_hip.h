@@ -720,7 +720,7 @@ int ddsp_hip_stream_pitch(const float* x, float* f0, float* confidence, int32_t*
  * The reference's extract_pitch is crepe.predict(..., viterbi=True): a salience per frame, then a Viterbi decode over
  * time.  The decode does not care which estimator made the salience; here the salience is 1 - d' of "pitch" above, so
  * that a frame whose smallest dip sits an octave off is overruled by its neighbours.  Two launches, offline only (the
- * decode needs the future).
+ * decode needs the future; "pitch_viterbi_stream" below is its fixed-lag form for a stream).
  *
  * Frames and d'.  Exactly ddsp_hip_pitch's: offline reflect-indexed frames, L a power of two in [64, 4096], W = L/2,
  * hop, d'(tau) for tau = 0 .. tau_max + 1 by steps 1-5 of "pitch" in fp64, the 2^-40 floor and the zero-energy rule
@@ -775,6 +775,72 @@ int64_t ddsp_hip_pitch_viterbi_chunk_frames(int64_t n_bins);
 int ddsp_hip_pitch_viterbi(const float* cost, const float* f0c, float* f0, float* confidence, int32_t* path,
                            void* workspace, size_t workspace_bytes, int64_t batch, int64_t frames, int64_t n_bins,
                            int64_t max_jump, float transition, void* stream);
+
+/* ---------------- pitch_viterbi_stream: the same decode per call of a stream, at a fixed lag ----------------
+ * Only the final backtrack of "pitch_viterbi" needs the future; the forward recursion is causal.  Carried from call
+ * to call in a device state, it gives at frame n the best endpoint s_n = argmin delta_n, and walking its
+ * back-pointers D frames gives a decision for frame n - D that has seen D frames of its future.  Two launches per
+ * call, salience then decode (not one: the decode needs every frame's costs, and no workgroup here waits for
+ * another).  No reference counterpart: crepe.predict(..., viterbi=True) decodes a whole file.
+ *
+ * Salience.  ddsp_hip_stream_pitch_salience is ddsp_hip_pitch_salience over the stream's own frames, as
+ * ddsp_hip_stream_pitch is to ddsp_hip_pitch: call k emits f = k R - d + 1 + j, zeros before the stream, L, hop,
+ * tau_min, tau_max, lo, hi and the per-frame definition exactly as in "pitch_viterbi".  x [batch, call_samples] ->
+ * cost, f0c [batch, R, NB] fp32, lag [batch, R, NB] int32 (may be NULL); with f0 given ([batch, R]; confidence and
+ * period may then be given too) the same launch also writes ddsp_hip_stream_pitch's outputs for the threshold, bit
+ * for bit.  One launch, ddsp_hip_stream_pitch's grid.  State: a ring buffer of ddsp_hip_stream_features_state_bytes(
+ * batch, call_samples, frame_length, hop) bytes of its own, zero-filled for a fresh stream; the call copies x into
+ * the ring under the argument of "streaming analysis", so a call run twice before the advance gives the same bits.
+ * Checked before any HIP call, in this order: the streaming envelope; the pitch parameters (as
+ * ddsp_hip_stream_pitch); n_bins < 1: DDSP_HIP_EINVAL, n_bins > 1024: DDSP_HIP_ERANGE; confidence or period without
+ * f0: DDSP_HIP_EINVAL; batch == 0: a no-op success; null x / lo / hi / cost / f0c / counter / state:
+ * DDSP_HIP_EINVAL; a short state: DDSP_HIP_EWORKSPACE. */
+int ddsp_hip_stream_pitch_salience(const float* x, const int32_t* lo, const int32_t* hi, float* cost, float* f0c,
+                                   int32_t* lag, float* f0, float* confidence, int32_t* period,
+                                   const uint64_t* counter, void* state, size_t state_bytes, int64_t batch,
+                                   int64_t call_samples, int64_t frame_length, int64_t hop, int64_t tau_min,
+                                   int64_t tau_max, int64_t n_bins, float sample_rate, float threshold,
+                                   void* stream);
+
+/* The carried decode.  R = frames_per_call in [1, 32]; NB = n_bins <= 1024; J = max_jump <= 127; lambda = transition
+ * (the fp32 value passed, widened); D = lag in frames, 0 <= D <= 64.  Call k = *counter takes cost, f0c [batch, R, NB]
+ * of the stream's emitted frames n = k R + j, j < R, and, per item, all in fp64:
+ *   delta_0(j) = cost(0, j) — "fresh" is taken from counter == 0, not from the stored bits;
+ *   delta_n, bp_n  exactly the recursion of "pitch_viterbi" (one addition or comparison per operation, the smallest
+ *                  i among equals), continued across calls;
+ *   s_n        = the smallest argmin of delta_n;
+ *   m          = n - min(D, n);
+ *   path(n)    = bp_{m+1}( ... bp_n(s_n)): min(D, n) steps back from s_n (none for D = 0: path(n) = s_n);
+ *   f0(n)      = f0c(m, path(n)), confidence(n) = 1 - cost(m, path(n)).
+ * Outputs f0, confidence (may be NULL) fp32 and path int32, each [batch, R]: slot j of call k describes emitted frame
+ * m = k R + j - D once n >= D (before that, frame 0 repeatedly: the stream has no earlier decision to give).
+ * By construction path(n) is element m of ddsp_hip_pitch_viterbi's path over frames 0 .. n, so the offline
+ * restatement is the yardstick, and a restatement reproduces the stream bit for bit from the same costs.
+ * delta is never renormalised: a frame adds at most 1 + lambda J (1.24 at the defaults), so after 2^32 frames (265
+ * days at 187.5 frames a second) delta is below 2^33 and its fp64 spacing at most 2^-20, 1/20000 of lambda = 0.02;
+ * every rounding is the restatement's too, and the result does not depend on how the stream is cut into calls.
+ *
+ * State: ddsp_hip_stream_viterbi_state_bytes(batch, R, NB, D) bytes, 16-byte aligned, zero-filled for a fresh stream:
+ * per item double delta[2][NB], then a ring of P = D + R frames (frame n in slot n mod P) as float f0c[P][NB], float
+ * cost[P][NB] and int8 bp[P][NB] (the back-offsets bp_n(j) - j; f0c and cost because frame m may belong to an earlier
+ * call), the item rounded up to 8 bytes: batch * roundup8(16 NB + 9 P NB), rounded up to 16; 0 outside the envelope
+ * and for batch < 1.  Call k reads row k & 1 and writes row (k + 1) & 1; it writes slots k R .. k R + R - 1 and
+ * reads back no further than frame k R - D, whose slot is that of frame k R + R: with depth D + R nothing the call
+ * reads is overwritten by it, so a call run twice before the advance gives the same bits.  The counter is read and
+ * never written (ddsp_hip_stream_advance ends the call) and may be shared with the salience's ring and any other
+ * stream state.
+ * One launch: one workgroup per item, one thread per bin, one barrier per frame; the R backtracks run side by side on
+ * R threads over the ring in global memory.  Fixed orders, no atomics: two runs give the same bits and an item's bits
+ * do not depend on the batch around it.
+ * Checked before any HIP call: negative batch / max_jump / lag, frames_per_call < 1, n_bins < 1, transition negative,
+ * infinite or NaN: DDSP_HIP_EINVAL; frames_per_call > 32, n_bins > 1024, max_jump > 127, lag > 64: DDSP_HIP_ERANGE;
+ * batch == 0: a no-op success; null cost / f0c / f0 / path / counter / state: DDSP_HIP_EINVAL; a short state:
+ * DDSP_HIP_EWORKSPACE. */
+size_t ddsp_hip_stream_viterbi_state_bytes(int64_t batch, int64_t frames_per_call, int64_t n_bins, int64_t lag);
+int ddsp_hip_stream_pitch_viterbi(const float* cost, const float* f0c, float* f0, float* confidence, int32_t* path,
+                                  const uint64_t* counter, void* state, size_t state_bytes, int64_t batch,
+                                  int64_t frames_per_call, int64_t n_bins, int64_t max_jump, int64_t lag,
+                                  float transition, void* stream);
 
 /* ddsp_hip_stream_loudness and ddsp_hip_stream_pitch of one call in ONE launch over ONE state, for a stream whose
  * loudness and pitch use the same frame length L (n_fft == frame_length == L: the same frames of the same samples).

@@ -33,7 +33,7 @@ from .core import (amp_to_impulse_response, fft_convolve, harmonic_synth, remove
 from .decoder import DDSPDecoder
 from .encoder import DDSPAutoencoder
 from . import features
-from .features import StreamAnalyzer, analyze
+from .features import StreamAnalysisPlan, StreamAnalyzer, analyze, stream_analysis_route
 from .install import install
 from .modules import FilteredNoise, HarmonicSynth, Reverb
 from . import synth  # noqa: E402  (SynthPath, make_inputs: the bench's and the tests' synthesis-path driver)

@@ -974,6 +974,12 @@ def _feature_tables(kind, params, device, make):
     return tabs
 
 
+def _a_weighting(sample_rate, n_fft, device):
+    """``a_weighting_table`` on ``device``, cached per (sample_rate, n_fft, device)."""
+    return _feature_tables("a_weighting", (float(sample_rate), int(n_fft)), device,
+                           lambda: (a_weighting_table(sample_rate, n_fft),))[0]
+
+
 def _signal_rows(signal, block_size, name):
     """signal [T] or [B, T] on a HIP device -> (contiguous detached [B, T], whether it was 1-D)."""
     _dev(signal)
@@ -994,8 +1000,7 @@ def extract_loudness(signal, sample_rate, block_size, n_fft=2048):
     requires grad is analysed detached."""
     x, one_d = _signal_rows(signal, block_size, "extract_loudness")
     n_fft = int(n_fft)
-    (w,) = _feature_tables("a_weighting", (float(sample_rate), n_fft), x.device,
-                           lambda: (a_weighting_table(sample_rate, n_fft),))
+    w = _a_weighting(sample_rate, n_fft, x.device)
     B, T = x.shape
     out = torch.empty(B, T // int(block_size), dtype=torch.float32, device=x.device)
     _lib.call("loudness", _lib.ptr(x), _lib.ptr(w), _lib.ptr(out), B, T, n_fft, int(block_size), _lib.stream_of(x))
@@ -1085,6 +1090,14 @@ def _pitch_bin_tables(sample_rate, fmin, fmax, frame_length, bins_per_octave, de
     return tau_min, tau_max, lo, hi
 
 
+def _salience_outputs(B, F, NB, device, return_lag, return_raw):
+    """(cost, f0c, lag, f0, confidence, period) as the salience's launch takes them: None for what is not asked for."""
+    cost = torch.empty(B, F, NB, dtype=torch.float32, device=device)
+    lag = torch.empty(B, F, NB, dtype=torch.int32, device=device) if return_lag else None
+    raw = _pitch_outputs(B, F, device, True, True) if return_raw else (None, None, None)
+    return (cost, torch.empty_like(cost), lag) + raw
+
+
 def pitch_salience(signal, sample_rate, block_size, fmin=50.0, fmax=2000.0, frame_length=2048, bins_per_octave=48,
                    return_lag=False, return_raw=False, threshold=0.1):
     """The salience the Viterbi decode runs over (include/ddsp_hip.h, "pitch_viterbi"): signal [T] or [B, T] (HIP,
@@ -1097,16 +1110,11 @@ def pitch_salience(signal, sample_rate, block_size, fmin=50.0, fmax=2000.0, fram
     L = int(frame_length)
     tau_min, tau_max, lo, hi = _pitch_bin_tables(sample_rate, fmin, fmax, L, bins_per_octave, x.device)
     B, T = x.shape
-    F, NB = T // int(block_size), lo.numel()
-    cost = torch.empty(B, F, NB, dtype=torch.float32, device=x.device)
-    f0c = torch.empty_like(cost)
-    lag = torch.empty(B, F, NB, dtype=torch.int32, device=x.device) if return_lag else None
-    raw = _pitch_outputs(B, F, x.device, True, True) if return_raw else (None, None, None)
-    _lib.call("pitch_salience", _lib.ptr(x), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(cost), _lib.ptr(f0c),
-              _lib.ptr(lag), _lib.ptr(raw[0]), _lib.ptr(raw[1]), _lib.ptr(raw[2]), B, T, L, int(block_size), tau_min,
-              tau_max, NB, float(sample_rate), float(threshold), _lib.stream_of(x))
-    out = tuple(t for t in (cost, f0c, lag) + tuple(raw) if t is not None)
-    return tuple(t[0] for t in out) if one_d else out
+    NB = lo.numel()
+    out = _salience_outputs(B, T // int(block_size), NB, x.device, return_lag, return_raw)
+    _lib.call("pitch_salience", _lib.ptr(x), _lib.ptr(lo), _lib.ptr(hi), *map(_lib.ptr, out), B, T, L,
+              int(block_size), tau_min, tau_max, NB, float(sample_rate), float(threshold), _lib.stream_of(x))
+    return tuple(t[0] if one_d else t for t in out if t is not None)
 
 
 def viterbi_path(cost, f0c, transition=0.02, max_jump=12):
@@ -1203,7 +1211,31 @@ def _reverb_apply_launch(x, spectrum, ir_length):
 # seamless realtime streaming (ddsp_hip_stream_*): K calls of N samples render what one call of
 # K N samples renders — the oscillator phase carried between calls, a reverb with its full IR
 # ------------------------------------------------------------------------------------
-class StreamState:
+class _DeviceState:
+    """What the stream states share: ``buf``, zero-filled uint8 on a HIP device, and ``counter``, int64[1] beside it
+    (a fresh one, or another state's to share); ``reset()`` zeroes both."""
+
+    @staticmethod
+    def _hip_device(device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("ddsp_hip: the stream state lives on a HIP device (no CPU fallback)")
+        return device
+
+    def _allocate(self, nbytes, device, counter=None):
+        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        if counter is None:
+            counter = torch.zeros(1, dtype=torch.int64, device=device)
+        elif counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != self.buf.device:
+            raise RuntimeError(f"{type(self).__name__}: counter must be an int64[1] tensor on the state's device")
+        self.counter = counter
+
+    def reset(self):
+        self.buf.zero_()
+        self.counter.zero_()
+
+
+class StreamState(_DeviceState):
     """The device state of one realtime stream: ``buf`` (uint8, ddsp_hip_stream_state_bytes: the phase
     carry per item, then — with ``ir_length`` > 0 — the streamed reverb's input history and its ring of
     block spectra) and ``counter`` (int64[1], the call index: Philox offset and ring slot).  Zero-filled
@@ -1217,20 +1249,12 @@ class StreamState:
         if nbytes == 0:
             raise RuntimeError("StreamState: the streamed reverb takes calls of a power-of-two size in "
                                f"[64, 2048] samples; got {self.call_samples}")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("ddsp_hip: the stream state lives on a HIP device (no CPU fallback)")
-        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
-        self.counter = torch.zeros(1, dtype=torch.int64, device=device)
+        self._allocate(nbytes, self._hip_device(device))
 
     @property
     def carry(self):
         """float64 [batch] view of the running phase prefix (writable: a preset phase)."""
         return self.buf[:8 * self.batch].view(torch.float64)
-
-    def reset(self):
-        self.buf.zero_()
-        self.counter.zero_()
 
 
 def stream_spectrum(impulse, call_samples):
@@ -1321,7 +1345,7 @@ def stream_feature_delay(n_fft, hop):
     return -(-(int(n_fft) // 2) // int(hop)) - 1
 
 
-class FeatureStreamState:
+class FeatureStreamState(_DeviceState):
     """The device state of one streamed feature (loudness, MFCC or pitch): ``buf`` (uint8,
     ddsp_hip_stream_features_state_bytes: per item a ring of the carried samples plus one call, then the
     MFCC's running maximum per item) and ``counter`` (int64[1], the call index).  Zero-filled is a fresh
@@ -1330,9 +1354,7 @@ class FeatureStreamState:
 
     def __init__(self, batch, device, call_samples, n_fft, hop, counter=None):
         self.batch, self.call_samples, self.n_fft, self.hop = int(batch), int(call_samples), int(n_fft), int(hop)
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("ddsp_hip: the stream state lives on a HIP device (no CPU fallback)")
+        device = self._hip_device(device)
         if self.batch < 1:
             raise RuntimeError("FeatureStreamState: batch must be at least 1")
         nbytes = int(_lib.query("stream_features_state_bytes", self.batch, self.call_samples, self.n_fft, self.hop))
@@ -1342,16 +1364,7 @@ class FeatureStreamState:
                                f"hop {self.hop}")
         self.frames = self.call_samples // self.hop
         self.delay_frames = stream_feature_delay(self.n_fft, self.hop)
-        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
-        if counter is None:
-            counter = torch.zeros(1, dtype=torch.int64, device=device)
-        elif counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != self.buf.device:
-            raise RuntimeError("FeatureStreamState: counter must be an int64[1] tensor on the state's device")
-        self.counter = counter
-
-    def reset(self):
-        self.buf.zero_()
-        self.counter.zero_()
+        self._allocate(nbytes, device, counter)
 
 
 def _stream_call_rows(x, state, block_size, n_fft, name):
@@ -1375,8 +1388,7 @@ def stream_loudness(x, sample_rate, block_size, state, n_fft=2048):
     ``extract_loudness``'s, no host synchronisation after the first call."""
     xc = _stream_call_rows(x, state, block_size, n_fft, "stream_loudness")
     n_fft = int(n_fft)
-    (w,) = _feature_tables("a_weighting", (float(sample_rate), n_fft), xc.device,
-                           lambda: (a_weighting_table(sample_rate, n_fft),))
+    w = _a_weighting(sample_rate, n_fft, xc.device)
     B, N = xc.shape
     out = torch.empty(B, state.frames, dtype=torch.float32, device=xc.device)
     _lib.call("stream_loudness", _lib.ptr(xc), _lib.ptr(w), _lib.ptr(out), _lib.ptr(state.counter),
@@ -1430,8 +1442,7 @@ def stream_analysis(x, sample_rate, block_size, state, fmin=50.0, fmax=2000.0, f
     L = int(frame_length)
     xc = _stream_call_rows(x, state, block_size, L, "stream_analysis")
     tau_min, tau_max = pitch_lags(sample_rate, fmin, fmax, L)
-    (w,) = _feature_tables("a_weighting", (float(sample_rate), L), xc.device,
-                           lambda: (a_weighting_table(sample_rate, L),))
+    w = _a_weighting(sample_rate, L, xc.device)
     B, N = xc.shape
     loud = torch.empty(B, state.frames, dtype=torch.float32, device=xc.device)
     f0, conf, period = _pitch_outputs(B, state.frames, xc.device, return_confidence, return_period)
@@ -1460,8 +1471,7 @@ def stream_analysis_mfcc(x, sample_rate, block_size, state, pitch=True, fmin=50.
     if not pitch and (return_confidence or return_period):
         raise RuntimeError("stream_analysis_mfcc: confidence and period come with pitch=True")
     tau_min, tau_max = pitch_lags(sample_rate, fmin, fmax, L) if pitch else (0, 0)
-    (w,) = _feature_tables("a_weighting", (float(sample_rate), L), xc.device,
-                           lambda: (a_weighting_table(sample_rate, L),))
+    w = _a_weighting(sample_rate, L, xc.device)
     band_start, band_count, band_weights, dct = mfcc_tables(sample_rate, n_mfcc, M, n_mels, mel_fmin, mel_fmax,
                                                             xc.device)
     B, N = xc.shape
@@ -1482,7 +1492,7 @@ def stream_analysis_mfcc(x, sample_rate, block_size, state, pitch=True, fmin=50.
 # stream.  The decode's forward recursion is causal; carried from call to call it gives, at every frame n, the offline
 # decode of frames 0 .. n, and its element n - lag is a decision at a fixed, small lag (lag 0: none at all).
 # ------------------------------------------------------------------------------------
-class ViterbiStreamState:
+class ViterbiStreamState(_DeviceState):
     """The device state of one streamed Viterbi decode (include/ddsp_hip.h, "pitch_viterbi_stream"): ``buf`` (uint8,
     ddsp_hip_stream_viterbi_state_bytes: per item the two fp64 rows of delta, then a ring of ``lag`` +
     ``frames_per_call`` frames of f0c, cost and back-offsets) and ``counter`` (int64[1], the call index).
@@ -1492,25 +1502,14 @@ class ViterbiStreamState:
 
     def __init__(self, batch, device, frames_per_call, n_bins, lag=0, counter=None):
         self.batch, self.frames, self.n_bins, self.lag = int(batch), int(frames_per_call), int(n_bins), int(lag)
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("ddsp_hip: the stream state lives on a HIP device (no CPU fallback)")
+        device = self._hip_device(device)
         if self.batch < 1:
             raise RuntimeError("ViterbiStreamState: batch must be at least 1")
         nbytes = int(_lib.query("stream_viterbi_state_bytes", self.batch, self.frames, self.n_bins, self.lag))
         if nbytes == 0:
             raise RuntimeError("ViterbiStreamState: 1 to 32 frames per call, 1 to 1024 bins and a lag of 0 to 64 "
                                f"frames; got {self.frames} frames, {self.n_bins} bins, lag {self.lag}")
-        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
-        if counter is None:
-            counter = torch.zeros(1, dtype=torch.int64, device=device)
-        elif counter.dtype != torch.int64 or counter.numel() != 1 or counter.device != self.buf.device:
-            raise RuntimeError("ViterbiStreamState: counter must be an int64[1] tensor on the state's device")
-        self.counter = counter
-
-    def reset(self):
-        self.buf.zero_()
-        self.counter.zero_()
+        self._allocate(nbytes, device, counter)
 
 
 def stream_pitch_salience(x, sample_rate, block_size, state, fmin=50.0, fmax=2000.0, frame_length=2048,
@@ -1525,16 +1524,12 @@ def stream_pitch_salience(x, sample_rate, block_size, state, fmin=50.0, fmax=200
     xc = _stream_call_rows(x, state, block_size, L, "stream_pitch_salience")
     tau_min, tau_max, lo, hi = _pitch_bin_tables(sample_rate, fmin, fmax, L, bins_per_octave, xc.device)
     B, N = xc.shape
-    R, NB = state.frames, lo.numel()
-    cost = torch.empty(B, R, NB, dtype=torch.float32, device=xc.device)
-    f0c = torch.empty_like(cost)
-    lag = torch.empty(B, R, NB, dtype=torch.int32, device=xc.device) if return_lag else None
-    raw = _pitch_outputs(B, R, xc.device, True, True) if return_raw else (None, None, None)
-    _lib.call("stream_pitch_salience", _lib.ptr(xc), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(cost), _lib.ptr(f0c),
-              _lib.ptr(lag), _lib.ptr(raw[0]), _lib.ptr(raw[1]), _lib.ptr(raw[2]), _lib.ptr(state.counter),
-              _lib.ptr(state.buf), state.buf.numel(), B, N, L, int(block_size), tau_min, tau_max, NB,
-              float(sample_rate), float(threshold), _lib.stream_of(xc))
-    return tuple(t for t in (cost, f0c, lag) + tuple(raw) if t is not None)
+    NB = lo.numel()
+    out = _salience_outputs(B, state.frames, NB, xc.device, return_lag, return_raw)
+    _lib.call("stream_pitch_salience", _lib.ptr(xc), _lib.ptr(lo), _lib.ptr(hi), *map(_lib.ptr, out),
+              _lib.ptr(state.counter), _lib.ptr(state.buf), state.buf.numel(), B, N, L, int(block_size), tau_min,
+              tau_max, NB, float(sample_rate), float(threshold), _lib.stream_of(xc))
+    return tuple(t for t in out if t is not None)
 
 
 def stream_viterbi_path(cost, f0c, state, transition=0.02, max_jump=12):

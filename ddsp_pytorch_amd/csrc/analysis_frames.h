@@ -145,5 +145,12 @@ struct StreamArgs {
   void* stream;
 };
 
+// One call's StreamArgs from the sizes check_stream_features gave (host); the ring starts the state.
+inline StreamArgs stream_args(const float* x, const uint64_t* counter, void* state, int64_t B, int64_t n, int64_t hop,
+                              const StreamSizes& sz, void* stream) {
+  return {x, counter, reinterpret_cast<float*>(state), B, (int)n, (int)sz.len, (int)sz.hs, (int)hop, (int)sz.frames,
+          stream};
+}
+
 }  // namespace
 }  // namespace ddsp

@@ -375,9 +375,8 @@ int ddsp_hip_stream_loudness(const float* x, const float* weights, float* out, c
   if (batch == 0) return DDSP_HIP_OK;
   if (!x || !out || !counter || !state) return DDSP_HIP_EINVAL;
   if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
-  const StreamArgs a{x, counter, reinterpret_cast<float*>(state), batch, (int)call_samples, (int)sz.len, (int)sz.hs,
-                     (int)hop, (int)sz.frames, stream};
-  return stream_loudness_dispatch(a, n_fft, weights, out);
+  return stream_loudness_dispatch(stream_args(x, counter, state, batch, call_samples, hop, sz, stream), n_fft, weights,
+                                  out);
 }
 
 int ddsp_hip_stream_mfcc(const float* x, const int32_t* band_start, const int32_t* band_count,
@@ -394,11 +393,9 @@ int ddsp_hip_stream_mfcc(const float* x, const int32_t* band_start, const int32_
   if (batch == 0) return DDSP_HIP_OK;
   if (!x || !band_start || !band_count || !band_weights || !dct || !out || !counter || !state) return DDSP_HIP_EINVAL;
   if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
-  float* ring = reinterpret_cast<float*>(state);
-  const StreamArgs a{x, counter, ring, batch, (int)call_samples, (int)sz.len, (int)sz.hs, (int)hop, (int)sz.frames,
-                     stream};
+  const StreamArgs a = stream_args(x, counter, state, batch, call_samples, hop, sz, stream);
   const MfccTables m{band_start, band_count, band_weights, (int)n_band_weights, dct, (int)n_mels, (int)n_mfcc, top_db};
-  return stream_mfcc_dispatch(a, n_fft, m, ring + (size_t)batch * (size_t)sz.len, out);
+  return stream_mfcc_dispatch(a, n_fft, m, a.ring + (size_t)batch * (size_t)sz.len, out);
 }
 
 }  // extern "C"

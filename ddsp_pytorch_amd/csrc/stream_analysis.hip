@@ -85,8 +85,7 @@ int ddsp_hip_stream_analysis(const float* x, const float* weights, float* loudne
   if (batch == 0) return DDSP_HIP_OK;
   if (!x || !loudness_out || !f0 || !counter || !state) return DDSP_HIP_EINVAL;
   if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
-  const StreamArgs a{x, counter, reinterpret_cast<float*>(state), batch, (int)call_samples, (int)sz.len, (int)sz.hs,
-                     (int)hop, (int)sz.frames, stream};
+  const StreamArgs a = stream_args(x, counter, state, batch, call_samples, hop, sz, stream);
   const PitchParams p{(int)tau_min, (int)tau_max, sample_rate, threshold};
   return stream_analysis_dispatch(a, frame_length, weights, loudness_out, p, f0, confidence, period);
 }

@@ -127,9 +127,7 @@ int ddsp_hip_stream_analysis_mfcc(const float* x, const float* weights, float* l
   if (!x || !loudness_out || !band_start || !band_count || !band_weights || !dct || !mfcc_out || !counter || !state)
     return DDSP_HIP_EINVAL;
   if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
-  float* ring = reinterpret_cast<float*>(state);
-  const StreamArgs a{x, counter, ring, batch, (int)call_samples, (int)sz.len, (int)sz.hs, (int)hop, (int)sz.frames,
-                     stream};
+  const StreamArgs a = stream_args(x, counter, state, batch, call_samples, hop, sz, stream);
   const AnalysisMfccArgs g{weights,
                            loudness_out,
                            PitchParams{(int)tau_min, (int)tau_max, sample_rate, threshold},
@@ -138,7 +136,7 @@ int ddsp_hip_stream_analysis_mfcc(const float* x, const float* weights, float* l
                            period,
                            MfccTables{band_start, band_count, band_weights, (int)n_band_weights, dct, (int)n_mels,
                                       (int)n_mfcc, top_db},
-                           ring + (size_t)batch * (size_t)sz.len,
+                           a.ring + (size_t)batch * (size_t)sz.len,
                            mfcc_out};
   return stream_analysis_mfcc_dispatch(a, frame_length, mfcc_n_fft != frame_length, g);
 }

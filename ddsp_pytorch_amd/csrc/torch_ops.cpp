@@ -344,6 +344,9 @@ void check_stream(const at::Tensor& counter, const at::Tensor& state, const at::
               "ddsp_hip: the stream counter must be an int64 tensor on the inputs' device");
 }
 
+// the call counter as the C-ABI takes it
+uint64_t* counter_ptr(const at::Tensor& counter) { return reinterpret_cast<uint64_t*>(counter.data_ptr<int64_t>()); }
+
 at::Tensor synth_frames_stream(const at::Tensor& f0, const at::Tensor& param, const at::Tensor& mags,
                                int64_t block_size, double sample_rate, double bias,
                                const std::optional<at::Tensor>& noise, int64_t seed, const at::Tensor& counter,
@@ -352,9 +355,9 @@ at::Tensor synth_frames_stream(const at::Tensor& f0, const at::Tensor& param, co
   check_stream(counter, state, f0);
   at::Tensor out = at::empty({a.B, a.F * block_size, 1}, a.f.options());
   ok(ddsp_hip_stream_synth_frames(a.f.data_ptr<float>(), a.p.data_ptr<float>(), a.m.data_ptr<float>(), (float)bias,
-                                  a.np, (uint64_t)seed, reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()),
-                                  state.data_ptr(), (size_t)state.numel(), wrap ? 1 : 0, out.data_ptr<float>(), nullptr,
-                                  nullptr, a.B, a.F, a.H, a.NB, block_size, (float)sample_rate, stream_of(a.f)),
+                                  a.np, (uint64_t)seed, counter_ptr(counter), state.data_ptr(), (size_t)state.numel(),
+                                  wrap ? 1 : 0, out.data_ptr<float>(), nullptr, nullptr, a.B, a.F, a.H, a.NB,
+                                  block_size, (float)sample_rate, stream_of(a.f)),
      "stream_synth_frames");
   return out;
 }
@@ -382,8 +385,8 @@ at::Tensor reverb_stream(const at::Tensor& x, const at::Tensor& spectrum, int64_
   at::Tensor xc = c16(x);
   at::Tensor out = at::empty_like(xc);
   ok(ddsp_hip_stream_reverb(xc.data_ptr<float>(), spectrum.data_ptr<float>(), (size_t)spectrum.numel(),
-                            reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
-                            (size_t)state.numel(), out.data_ptr<float>(), B, N, ir_length, stream_of(xc)),
+                            counter_ptr(counter), state.data_ptr(), (size_t)state.numel(), out.data_ptr<float>(), B, N,
+                            ir_length, stream_of(xc)),
      "stream_reverb");
   return out;
 }
@@ -394,9 +397,8 @@ void stream_advance(const at::Tensor& f0, int64_t block_size, double sample_rate
   check_stream(counter, state, f0);
   TORCH_CHECK(f0.dim() == 3 && f0.size(2) == 1, "stream_advance: f0 [B,F,1] expected");
   at::Tensor f = f0.contiguous();
-  ok(ddsp_hip_stream_advance(f.data_ptr<float>(), reinterpret_cast<uint64_t*>(counter.data_ptr<int64_t>()),
-                             state.data_ptr(), (size_t)state.numel(), wrap ? 1 : 0, f.size(0), f.size(1), block_size,
-                             (float)sample_rate, stream_of(f)),
+  ok(ddsp_hip_stream_advance(f.data_ptr<float>(), counter_ptr(counter), state.data_ptr(), (size_t)state.numel(),
+                             wrap ? 1 : 0, f.size(0), f.size(1), block_size, (float)sample_rate, stream_of(f)),
      "stream_advance");
 }
 
@@ -408,19 +410,67 @@ at::Tensor audio_rows(const at::Tensor& x, const char* op) {
   return c16(x.dim() == 1 ? x.unsqueeze(0) : x);
 }
 
+// one call of a stream: x [B, N] or [B, N, 1] -> the rows [B, N] contiguous
+at::Tensor call_rows(const at::Tensor& x, const char* op) {
+  check_dev(x, "x");
+  TORCH_CHECK((x.dim() == 2 || x.dim() == 3) && x.numel() == x.size(0) * x.size(1), op,
+              ": x [batch, call_samples] or [batch, call_samples, 1] expected");
+  return c16(x.reshape({x.size(0), x.size(1)}));
+}
+
+// R, the frames one call [B, N] completes
+int64_t call_frames(const at::Tensor& xc, int64_t hop, const char* op) {
+  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, op, ": call_samples must be a multiple of hop");
+  return xc.size(1) / hop;
+}
+
+// the optional A-weighting table of n/2+1 values (`n_name`: what the op calls n) -> contiguous, or undefined
+at::Tensor weights_table(const std::optional<at::Tensor>& weights, int64_t n, const char* op, const char* n_name) {
+  if (!weights.has_value() || !weights->defined()) return at::Tensor();
+  check_dev(*weights, "weights");
+  TORCH_CHECK(weights->numel() == n / 2 + 1, op, ": weights must hold ", n_name, "/2+1 values");
+  return weights->contiguous();
+}
+const float* ptr_or_null(const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
+
+// the mel tables of the MFCC, contiguous, n_mfcc and n_mels taken from dct (the caller has checked band_weights' and
+// dct's device, and its hop, before)
+struct MelTables {
+  at::Tensor bs, bc, bw, d;
+  int64_t n_mfcc, n_mels;
+};
+MelTables mel_tables(const at::Tensor& band_start, const at::Tensor& band_count, const at::Tensor& band_weights,
+                     const at::Tensor& dct, const char* op) {
+  TORCH_CHECK(dct.dim() == 2, op, ": dct [n_mfcc, n_mels] expected");
+  for (const at::Tensor* t : {&band_start, &band_count})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->numel() == dct.size(1), op,
+                ": band_start and band_count must be int32 HIP tensors of n_mels values");
+  return {band_start.contiguous(), band_count.contiguous(), band_weights.contiguous(), dct.contiguous(), dct.size(0),
+          dct.size(1)};
+}
+
+// the decode's bin tables (lo, hi), contiguous
+std::pair<at::Tensor, at::Tensor> bin_tables(const at::Tensor& lo, const at::Tensor& hi, const char* op) {
+  for (const at::Tensor* t : {&lo, &hi})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->dim() == 1 && t->numel() == lo.numel(), op,
+                ": lo and hi must be int32 HIP tensors of n_bins values");
+  return {lo.contiguous(), hi.contiguous()};
+}
+
+using Tensor3 = std::tuple<at::Tensor, at::Tensor, at::Tensor>;
+// fp32, fp32 and int32 outputs of one shape: (f0, confidence, period or path) [B, F]; (cost, f0c, lag) [B, F, n_bins]
+Tensor3 three_outputs(const at::Tensor& like, at::IntArrayRef shape) {
+  at::Tensor a = at::empty(shape, like.options());
+  return {a, at::empty_like(a), at::empty(shape, like.options().dtype(at::kInt))};
+}
+
 at::Tensor loudness(const at::Tensor& x, const std::optional<at::Tensor>& weights, int64_t n_fft, int64_t hop) {
   at::Tensor xc = audio_rows(x, "loudness");  // core.py:81-97 extract_loudness
   TORCH_CHECK(hop >= 1, "loudness: hop must be positive");
   const int64_t B = xc.size(0), T = xc.size(1);
-  at::Tensor w;
-  if (weights.has_value() && weights->defined()) {
-    check_dev(*weights, "weights");
-    TORCH_CHECK(weights->numel() == n_fft / 2 + 1, "loudness: weights must hold n_fft/2+1 values");
-    w = weights->contiguous();
-  }
+  at::Tensor w = weights_table(weights, n_fft, "loudness", "n_fft");
   at::Tensor out = at::empty({B, T / hop}, xc.options());
-  ok(ddsp_hip_loudness(xc.data_ptr<float>(), w.defined() ? w.data_ptr<float>() : nullptr, out.data_ptr<float>(), B, T,
-                       n_fft, hop, stream_of(xc)),
+  ok(ddsp_hip_loudness(xc.data_ptr<float>(), ptr_or_null(w), out.data_ptr<float>(), B, T, n_fft, hop, stream_of(xc)),
      "loudness");
   return x.dim() == 1 ? out.select(0, 0) : out;
 }
@@ -431,48 +481,27 @@ at::Tensor mfcc(const at::Tensor& x, const at::Tensor& band_start, const at::Ten
   check_dev(band_weights, "band_weights");
   check_dev(dct, "dct");
   TORCH_CHECK(hop >= 1, "mfcc: hop must be positive");
-  TORCH_CHECK(dct.dim() == 2, "mfcc: dct [n_mfcc, n_mels] expected");
-  const int64_t B = xc.size(0), T = xc.size(1), n_mfcc = dct.size(0), n_mels = dct.size(1);
-  for (const at::Tensor* t : {&band_start, &band_count})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->numel() == n_mels,
-                "mfcc: band_start and band_count must be int32 HIP tensors of n_mels values");
-  at::Tensor bs = band_start.contiguous(), bc = band_count.contiguous(), bw = band_weights.contiguous(),
-             d = dct.contiguous();
-  const int64_t frames = T / hop + 1;
-  at::Tensor out = at::empty({B, frames, n_mfcc}, xc.options());
-  at::Tensor ws = workspace(ddsp_hip_mfcc_workspace_size(B, T, n_fft, hop, n_mels), xc);
-  ok(ddsp_hip_mfcc(xc.data_ptr<float>(), bs.data_ptr<int32_t>(), bc.data_ptr<int32_t>(), bw.data_ptr<float>(),
-                   bw.numel(), d.data_ptr<float>(), out.data_ptr<float>(), B, T, n_fft, hop, n_mels, n_mfcc,
+  const MelTables m = mel_tables(band_start, band_count, band_weights, dct, "mfcc");
+  const int64_t B = xc.size(0), T = xc.size(1), frames = T / hop + 1;
+  at::Tensor out = at::empty({B, frames, m.n_mfcc}, xc.options());
+  at::Tensor ws = workspace(ddsp_hip_mfcc_workspace_size(B, T, n_fft, hop, m.n_mels), xc);
+  ok(ddsp_hip_mfcc(xc.data_ptr<float>(), m.bs.data_ptr<int32_t>(), m.bc.data_ptr<int32_t>(), m.bw.data_ptr<float>(),
+                   m.bw.numel(), m.d.data_ptr<float>(), out.data_ptr<float>(), B, T, n_fft, hop, m.n_mels, m.n_mfcc,
                    (float)top_db, ws.data_ptr(), (size_t)ws.numel(), stream_of(xc)),
      "mfcc");
   return x.dim() == 1 ? out.select(0, 0) : out;
 }
 
 // ---------------- streaming analysis: one call of a stream (ddsp_hip_stream_loudness / _mfcc) ----------------
-// x [B, N] or [B, N, 1] -> the rows [B, N] contiguous
-at::Tensor call_rows(const at::Tensor& x, const char* op) {
-  check_dev(x, "x");
-  TORCH_CHECK((x.dim() == 2 || x.dim() == 3) && x.numel() == x.size(0) * x.size(1), op,
-              ": x [batch, call_samples] or [batch, call_samples, 1] expected");
-  return c16(x.reshape({x.size(0), x.size(1)}));
-}
-
 at::Tensor loudness_stream(const at::Tensor& x, const std::optional<at::Tensor>& weights, int64_t n_fft, int64_t hop,
                            const at::Tensor& counter, at::Tensor& state) {
   at::Tensor xc = call_rows(x, "loudness_stream");
   check_stream(counter, state, xc);
-  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "loudness_stream: call_samples must be a multiple of hop");
-  const int64_t B = xc.size(0), N = xc.size(1);
-  at::Tensor w;
-  if (weights.has_value() && weights->defined()) {
-    check_dev(*weights, "weights");
-    TORCH_CHECK(weights->numel() == n_fft / 2 + 1, "loudness_stream: weights must hold n_fft/2+1 values");
-    w = weights->contiguous();
-  }
-  at::Tensor out = at::empty({B, N / hop}, xc.options());
-  ok(ddsp_hip_stream_loudness(xc.data_ptr<float>(), w.defined() ? w.data_ptr<float>() : nullptr, out.data_ptr<float>(),
-                              reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
-                              (size_t)state.numel(), B, N, n_fft, hop, stream_of(xc)),
+  const int64_t R = call_frames(xc, hop, "loudness_stream"), B = xc.size(0), N = xc.size(1);
+  at::Tensor w = weights_table(weights, n_fft, "loudness_stream", "n_fft");
+  at::Tensor out = at::empty({B, R}, xc.options());
+  ok(ddsp_hip_stream_loudness(xc.data_ptr<float>(), ptr_or_null(w), out.data_ptr<float>(), counter_ptr(counter),
+                              state.data_ptr(), (size_t)state.numel(), B, N, n_fft, hop, stream_of(xc)),
      "stream_loudness");
   return out;
 }
@@ -484,134 +513,107 @@ at::Tensor mfcc_stream(const at::Tensor& x, const at::Tensor& band_start, const 
   check_stream(counter, state, xc);
   check_dev(band_weights, "band_weights");
   check_dev(dct, "dct");
-  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "mfcc_stream: call_samples must be a multiple of hop");
-  TORCH_CHECK(dct.dim() == 2, "mfcc_stream: dct [n_mfcc, n_mels] expected");
-  const int64_t B = xc.size(0), N = xc.size(1), n_mfcc = dct.size(0), n_mels = dct.size(1);
-  for (const at::Tensor* t : {&band_start, &band_count})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->numel() == n_mels,
-                "mfcc_stream: band_start and band_count must be int32 HIP tensors of n_mels values");
-  at::Tensor bs = band_start.contiguous(), bc = band_count.contiguous(), bw = band_weights.contiguous(),
-             d = dct.contiguous();
-  at::Tensor out = at::empty({B, N / hop, n_mfcc}, xc.options());
-  ok(ddsp_hip_stream_mfcc(xc.data_ptr<float>(), bs.data_ptr<int32_t>(), bc.data_ptr<int32_t>(), bw.data_ptr<float>(),
-                          bw.numel(), d.data_ptr<float>(), out.data_ptr<float>(),
-                          reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
-                          (size_t)state.numel(), B, N, n_fft, hop, n_mels, n_mfcc, (float)top_db, stream_of(xc)),
+  const int64_t R = call_frames(xc, hop, "mfcc_stream"), B = xc.size(0), N = xc.size(1);
+  const MelTables m = mel_tables(band_start, band_count, band_weights, dct, "mfcc_stream");
+  at::Tensor out = at::empty({B, R, m.n_mfcc}, xc.options());
+  ok(ddsp_hip_stream_mfcc(xc.data_ptr<float>(), m.bs.data_ptr<int32_t>(), m.bc.data_ptr<int32_t>(),
+                          m.bw.data_ptr<float>(), m.bw.numel(), m.d.data_ptr<float>(), out.data_ptr<float>(),
+                          counter_ptr(counter), state.data_ptr(), (size_t)state.numel(), B, N, n_fft, hop, m.n_mels,
+                          m.n_mfcc, (float)top_db, stream_of(xc)),
      "stream_mfcc");
   return out;
 }
 
 // ---------------- pitch: YIN f0 (ddsp_hip_pitch / ddsp_hip_stream_pitch) -> (f0, confidence, period) ----------------
-std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch(const at::Tensor& x, int64_t frame_length, int64_t hop,
-                                                     int64_t tau_min, int64_t tau_max, double sample_rate,
-                                                     double threshold) {
+Tensor3 pitch(const at::Tensor& x, int64_t frame_length, int64_t hop, int64_t tau_min, int64_t tau_max,
+              double sample_rate, double threshold) {
   at::Tensor xc = audio_rows(x, "pitch");
   TORCH_CHECK(hop >= 1, "pitch: hop must be positive");
   const int64_t B = xc.size(0), T = xc.size(1);
-  at::Tensor f0 = at::empty({B, T / hop}, xc.options());
-  at::Tensor conf = at::empty_like(f0);
-  at::Tensor period = at::empty({B, T / hop}, xc.options().dtype(at::kInt));
+  const Tensor3 out = three_outputs(xc, {B, T / hop});
+  const auto& [f0, conf, period] = out;
   ok(ddsp_hip_pitch(xc.data_ptr<float>(), f0.data_ptr<float>(), conf.data_ptr<float>(), period.data_ptr<int32_t>(), B,
                     T, frame_length, hop, tau_min, tau_max, (float)sample_rate, (float)threshold, stream_of(xc)),
      "pitch");
   if (x.dim() == 1) return {f0.select(0, 0), conf.select(0, 0), period.select(0, 0)};
-  return {f0, conf, period};
+  return out;
 }
 
-std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_stream(const at::Tensor& x, int64_t frame_length, int64_t hop,
-                                                            int64_t tau_min, int64_t tau_max, double sample_rate,
-                                                            double threshold, const at::Tensor& counter,
-                                                            at::Tensor& state) {
+Tensor3 pitch_stream(const at::Tensor& x, int64_t frame_length, int64_t hop, int64_t tau_min, int64_t tau_max,
+                     double sample_rate, double threshold, const at::Tensor& counter, at::Tensor& state) {
   at::Tensor xc = call_rows(x, "pitch_stream");
   check_stream(counter, state, xc);
-  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "pitch_stream: call_samples must be a multiple of hop");
-  const int64_t B = xc.size(0), N = xc.size(1);
-  at::Tensor f0 = at::empty({B, N / hop}, xc.options());
-  at::Tensor conf = at::empty_like(f0);
-  at::Tensor period = at::empty({B, N / hop}, xc.options().dtype(at::kInt));
+  const int64_t R = call_frames(xc, hop, "pitch_stream"), B = xc.size(0), N = xc.size(1);
+  const Tensor3 out = three_outputs(xc, {B, R});
+  const auto& [f0, conf, period] = out;
   ok(ddsp_hip_stream_pitch(xc.data_ptr<float>(), f0.data_ptr<float>(), conf.data_ptr<float>(),
-                           period.data_ptr<int32_t>(), reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()),
-                           state.data_ptr(), (size_t)state.numel(), B, N, frame_length, hop, tau_min, tau_max,
-                           (float)sample_rate, (float)threshold, stream_of(xc)),
+                           period.data_ptr<int32_t>(), counter_ptr(counter), state.data_ptr(), (size_t)state.numel(), B,
+                           N, frame_length, hop, tau_min, tau_max, (float)sample_rate, (float)threshold, stream_of(xc)),
      "stream_pitch");
-  return {f0, conf, period};
+  return out;
 }
 
 // ---------------- pitch_viterbi: the salience over lag bins and the decode (ddsp_hip_pitch_salience / _viterbi) ------
 // -> (cost, f0c, lag), each [B, F, n_bins] ([F, n_bins] for a 1-D signal)
-std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_salience(const at::Tensor& x, const at::Tensor& lo,
-                                                              const at::Tensor& hi, int64_t frame_length, int64_t hop,
-                                                              int64_t tau_min, int64_t tau_max, double sample_rate) {
+Tensor3 pitch_salience(const at::Tensor& x, const at::Tensor& lo, const at::Tensor& hi, int64_t frame_length,
+                       int64_t hop, int64_t tau_min, int64_t tau_max, double sample_rate) {
   at::Tensor xc = audio_rows(x, "pitch_salience");
   TORCH_CHECK(hop >= 1, "pitch_salience: hop must be positive");
-  for (const at::Tensor* t : {&lo, &hi})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->dim() == 1 && t->numel() == lo.numel(),
-                "pitch_salience: lo and hi must be int32 HIP tensors of n_bins values");
-  at::Tensor l = lo.contiguous(), h = hi.contiguous();
+  const auto [l, h] = bin_tables(lo, hi, "pitch_salience");
   const int64_t B = xc.size(0), T = xc.size(1), NB = l.numel();
-  at::Tensor cost = at::empty({B, T / hop, NB}, xc.options());
-  at::Tensor f0c = at::empty_like(cost);
-  at::Tensor lag = at::empty({B, T / hop, NB}, xc.options().dtype(at::kInt));
+  const Tensor3 out = three_outputs(xc, {B, T / hop, NB});
+  const auto& [cost, f0c, lag] = out;
   ok(ddsp_hip_pitch_salience(xc.data_ptr<float>(), l.data_ptr<int32_t>(), h.data_ptr<int32_t>(),
                              cost.data_ptr<float>(), f0c.data_ptr<float>(), lag.data_ptr<int32_t>(), nullptr, nullptr,
                              nullptr, B, T, frame_length, hop, tau_min, tau_max, NB, (float)sample_rate, 0.0f,
                              stream_of(xc)),
      "pitch_salience");
   if (x.dim() == 1) return {cost.select(0, 0), f0c.select(0, 0), lag.select(0, 0)};
-  return {cost, f0c, lag};
+  return out;
 }
 
 // cost, f0c [B, F, n_bins] -> (f0, confidence, path), each [B, F]
-std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_viterbi(const at::Tensor& cost, const at::Tensor& f0c,
-                                                             double transition, int64_t max_jump) {
+Tensor3 pitch_viterbi(const at::Tensor& cost, const at::Tensor& f0c, double transition, int64_t max_jump) {
   check_dev(cost, "cost");
   check_dev(f0c, "f0c");
   TORCH_CHECK(cost.dim() == 3 && cost.sizes() == f0c.sizes() && cost.size(2) >= 1,
               "pitch_viterbi: cost and f0c must both be [batch, frames, bins]");
   at::Tensor c = cost.contiguous(), g = f0c.contiguous();
   const int64_t B = c.size(0), F = c.size(1), NB = c.size(2);
-  at::Tensor f0 = at::empty({B, F}, c.options());
-  at::Tensor conf = at::empty_like(f0);
-  at::Tensor path = at::empty({B, F}, c.options().dtype(at::kInt));
+  const Tensor3 out = three_outputs(c, {B, F});
+  const auto& [f0, conf, path] = out;
   at::Tensor ws = at::empty({B * F * NB}, c.options().dtype(at::kChar));
   ok(ddsp_hip_pitch_viterbi(c.data_ptr<float>(), g.data_ptr<float>(), f0.data_ptr<float>(), conf.data_ptr<float>(),
                             path.data_ptr<int32_t>(), ws.data_ptr(), (size_t)ws.numel(), B, F, NB, max_jump,
                             (float)transition, stream_of(c)),
      "pitch_viterbi");
-  return {f0, conf, path};
+  return out;
 }
 
 // ---------------- pitch_viterbi_stream: the same per call of a stream (ddsp_hip_stream_pitch_salience / _viterbi) ----
 // -> (cost, f0c, lag), each [B, R, n_bins]
-std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_salience_stream(const at::Tensor& x, const at::Tensor& lo,
-                                                                     const at::Tensor& hi, int64_t frame_length,
-                                                                     int64_t hop, int64_t tau_min, int64_t tau_max,
-                                                                     double sample_rate, const at::Tensor& counter,
-                                                                     at::Tensor& state) {
+Tensor3 pitch_salience_stream(const at::Tensor& x, const at::Tensor& lo, const at::Tensor& hi, int64_t frame_length,
+                              int64_t hop, int64_t tau_min, int64_t tau_max, double sample_rate,
+                              const at::Tensor& counter, at::Tensor& state) {
   at::Tensor xc = call_rows(x, "pitch_salience_stream");
   check_stream(counter, state, xc);
-  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "pitch_salience_stream: call_samples must be a multiple of hop");
-  for (const at::Tensor* t : {&lo, &hi})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->dim() == 1 && t->numel() == lo.numel(),
-                "pitch_salience_stream: lo and hi must be int32 HIP tensors of n_bins values");
-  at::Tensor l = lo.contiguous(), h = hi.contiguous();
+  const int64_t R = call_frames(xc, hop, "pitch_salience_stream");
+  const auto [l, h] = bin_tables(lo, hi, "pitch_salience_stream");
   const int64_t B = xc.size(0), N = xc.size(1), NB = l.numel();
-  at::Tensor cost = at::empty({B, N / hop, NB}, xc.options());
-  at::Tensor f0c = at::empty_like(cost);
-  at::Tensor lag = at::empty({B, N / hop, NB}, xc.options().dtype(at::kInt));
+  const Tensor3 out = three_outputs(xc, {B, R, NB});
+  const auto& [cost, f0c, lag] = out;
   ok(ddsp_hip_stream_pitch_salience(xc.data_ptr<float>(), l.data_ptr<int32_t>(), h.data_ptr<int32_t>(),
                                     cost.data_ptr<float>(), f0c.data_ptr<float>(), lag.data_ptr<int32_t>(), nullptr,
-                                    nullptr, nullptr, reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()),
-                                    state.data_ptr(), (size_t)state.numel(), B, N, frame_length, hop, tau_min, tau_max,
-                                    NB, (float)sample_rate, 0.0f, stream_of(xc)),
+                                    nullptr, nullptr, counter_ptr(counter), state.data_ptr(), (size_t)state.numel(), B,
+                                    N, frame_length, hop, tau_min, tau_max, NB, (float)sample_rate, 0.0f,
+                                    stream_of(xc)),
      "stream_pitch_salience");
-  return {cost, f0c, lag};
+  return out;
 }
 
 // cost, f0c [B, R, n_bins] of one call -> (f0, confidence, path), each [B, R], `lag` frames back
-std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_viterbi_stream(const at::Tensor& cost, const at::Tensor& f0c,
-                                                                    double transition, int64_t max_jump, int64_t lag,
-                                                                    const at::Tensor& counter, at::Tensor& state) {
+Tensor3 pitch_viterbi_stream(const at::Tensor& cost, const at::Tensor& f0c, double transition, int64_t max_jump,
+                             int64_t lag, const at::Tensor& counter, at::Tensor& state) {
   check_dev(cost, "cost");
   check_dev(f0c, "f0c");
   check_stream(counter, state, cost);
@@ -619,15 +621,14 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> pitch_viterbi_stream(const at::Te
               "pitch_viterbi_stream: cost and f0c must both be [batch, frames, bins]");
   at::Tensor c = cost.contiguous(), g = f0c.contiguous();
   const int64_t B = c.size(0), R = c.size(1), NB = c.size(2);
-  at::Tensor f0 = at::empty({B, R}, c.options());
-  at::Tensor conf = at::empty_like(f0);
-  at::Tensor path = at::empty({B, R}, c.options().dtype(at::kInt));
+  const Tensor3 out = three_outputs(c, {B, R});
+  const auto& [f0, conf, path] = out;
   ok(ddsp_hip_stream_pitch_viterbi(c.data_ptr<float>(), g.data_ptr<float>(), f0.data_ptr<float>(),
-                                   conf.data_ptr<float>(), path.data_ptr<int32_t>(),
-                                   reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
-                                   (size_t)state.numel(), B, R, NB, max_jump, lag, (float)transition, stream_of(c)),
+                                   conf.data_ptr<float>(), path.data_ptr<int32_t>(), counter_ptr(counter),
+                                   state.data_ptr(), (size_t)state.numel(), B, R, NB, max_jump, lag, (float)transition,
+                                   stream_of(c)),
      "stream_pitch_viterbi");
-  return {f0, conf, path};
+  return out;
 }
 
 // loudness_stream + pitch_stream in one launch over one state (ddsp_hip_stream_analysis)
@@ -637,25 +638,14 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> analysis_stream(
     int64_t tau_max, double sample_rate, double threshold, const at::Tensor& counter, at::Tensor& state) {
   at::Tensor xc = call_rows(x, "analysis_stream");
   check_stream(counter, state, xc);
-  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "analysis_stream: call_samples must be a multiple of hop");
-  const int64_t B = xc.size(0), N = xc.size(1);
-  at::Tensor w;
-  if (weights.has_value() && weights->defined()) {
-    check_dev(*weights, "weights");
-    TORCH_CHECK(weights->numel() == frame_length / 2 + 1,
-                "analysis_stream: weights must hold frame_length/2+1 values");
-    w = weights->contiguous();
-  }
-  at::Tensor loud = at::empty({B, N / hop}, xc.options());
-  at::Tensor f0 = at::empty_like(loud);
-  at::Tensor conf = at::empty_like(loud);
-  at::Tensor period = at::empty({B, N / hop}, xc.options().dtype(at::kInt));
-  ok(ddsp_hip_stream_analysis(xc.data_ptr<float>(), w.defined() ? w.data_ptr<float>() : nullptr,
-                              loud.data_ptr<float>(), f0.data_ptr<float>(), conf.data_ptr<float>(),
-                              period.data_ptr<int32_t>(),
-                              reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()), state.data_ptr(),
-                              (size_t)state.numel(), B, N, frame_length, hop, tau_min, tau_max, (float)sample_rate,
-                              (float)threshold, stream_of(xc)),
+  const int64_t R = call_frames(xc, hop, "analysis_stream"), B = xc.size(0), N = xc.size(1);
+  at::Tensor w = weights_table(weights, frame_length, "analysis_stream", "frame_length");
+  at::Tensor loud = at::empty({B, R}, xc.options());
+  const auto [f0, conf, period] = three_outputs(xc, {B, R});
+  ok(ddsp_hip_stream_analysis(xc.data_ptr<float>(), ptr_or_null(w), loud.data_ptr<float>(), f0.data_ptr<float>(),
+                              conf.data_ptr<float>(), period.data_ptr<int32_t>(), counter_ptr(counter),
+                              state.data_ptr(), (size_t)state.numel(), B, N, frame_length, hop, tau_min, tau_max,
+                              (float)sample_rate, (float)threshold, stream_of(xc)),
      "stream_analysis");
   return {loud, f0, conf, period};
 }
@@ -671,34 +661,19 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> analysis_
   check_stream(counter, state, xc);
   check_dev(band_weights, "band_weights");
   check_dev(dct, "dct");
-  TORCH_CHECK(hop >= 1 && xc.size(1) % hop == 0, "analysis_mfcc_stream: call_samples must be a multiple of hop");
-  TORCH_CHECK(dct.dim() == 2, "analysis_mfcc_stream: dct [n_mfcc, n_mels] expected");
-  const int64_t B = xc.size(0), N = xc.size(1), n_mfcc = dct.size(0), n_mels = dct.size(1);
-  for (const at::Tensor* t : {&band_start, &band_count})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->numel() == n_mels,
-                "analysis_mfcc_stream: band_start and band_count must be int32 HIP tensors of n_mels values");
-  at::Tensor w;
-  if (weights.has_value() && weights->defined()) {
-    check_dev(*weights, "weights");
-    TORCH_CHECK(weights->numel() == frame_length / 2 + 1,
-                "analysis_mfcc_stream: weights must hold frame_length/2+1 values");
-    w = weights->contiguous();
-  }
-  at::Tensor bs = band_start.contiguous(), bc = band_count.contiguous(), bw = band_weights.contiguous(),
-             d = dct.contiguous();
-  const int64_t R = N / hop, Rp = pitch ? R : 0;
+  const int64_t R = call_frames(xc, hop, "analysis_mfcc_stream"), B = xc.size(0), N = xc.size(1);
+  const MelTables m = mel_tables(band_start, band_count, band_weights, dct, "analysis_mfcc_stream");
+  at::Tensor w = weights_table(weights, frame_length, "analysis_mfcc_stream", "frame_length");
   at::Tensor loud = at::empty({B, R}, xc.options());
-  at::Tensor out = at::empty({B, R, n_mfcc}, xc.options());
-  at::Tensor f0 = at::empty({B, Rp}, xc.options());
-  at::Tensor conf = at::empty_like(f0);
-  at::Tensor period = at::empty({B, Rp}, xc.options().dtype(at::kInt));
+  at::Tensor out = at::empty({B, R, m.n_mfcc}, xc.options());
+  const auto [f0, conf, period] = three_outputs(xc, {B, pitch ? R : 0});
   ok(ddsp_hip_stream_analysis_mfcc(
-         xc.data_ptr<float>(), w.defined() ? w.data_ptr<float>() : nullptr, loud.data_ptr<float>(),
-         bs.data_ptr<int32_t>(), bc.data_ptr<int32_t>(), bw.data_ptr<float>(), bw.numel(), d.data_ptr<float>(),
-         out.data_ptr<float>(), pitch ? f0.data_ptr<float>() : nullptr, pitch ? conf.data_ptr<float>() : nullptr,
-         pitch ? period.data_ptr<int32_t>() : nullptr, reinterpret_cast<const uint64_t*>(counter.data_ptr<int64_t>()),
-         state.data_ptr(), (size_t)state.numel(), B, N, frame_length, mfcc_n_fft, hop, n_mels, n_mfcc, (float)top_db,
-         tau_min, tau_max, (float)sample_rate, (float)threshold, stream_of(xc)),
+         xc.data_ptr<float>(), ptr_or_null(w), loud.data_ptr<float>(), m.bs.data_ptr<int32_t>(),
+         m.bc.data_ptr<int32_t>(), m.bw.data_ptr<float>(), m.bw.numel(), m.d.data_ptr<float>(), out.data_ptr<float>(),
+         pitch ? f0.data_ptr<float>() : nullptr, pitch ? conf.data_ptr<float>() : nullptr,
+         pitch ? period.data_ptr<int32_t>() : nullptr, counter_ptr(counter), state.data_ptr(), (size_t)state.numel(), B,
+         N, frame_length, mfcc_n_fft, hop, m.n_mels, m.n_mfcc, (float)top_db, tau_min, tau_max, (float)sample_rate,
+         (float)threshold, stream_of(xc)),
      "stream_analysis_mfcc");
   return {loud, out, f0, conf, period};
 }

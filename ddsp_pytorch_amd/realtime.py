@@ -46,6 +46,7 @@ import torch
 
 from . import core
 from .decoder import gru_decoder_forward
+from .features import StreamAnalysisPlan, stream_analysis_route
 
 _Linear = namedtuple("_Linear", "weight bias in_features out_features")
 
@@ -88,12 +89,13 @@ class RealtimeGraph:
     ``reverb``): the graph's f0 is the streamed Viterbi decode's (`core.stream_track_pitch`: ``pitch_transition`` per
     bin moved, at most ``pitch_max_jump`` bins a frame, the decision ``pitch_lag`` frames back), so an octave jump of
     the per-frame pick under a strong second harmonic no longer passes through the control network and the
-    oscillator bank as a one-frame yodel.  The analysis launch then computes the loudness (and the MFCC) without the
-    pitch, and two more launches — the salience over a pitch ring of its own, `self.pitch_ring`, and the carried
-    decode, `self.viterbi` — give `self.f0` and `self.confidence` (1 - d' along the path).
+    oscillator bank as a one-frame yodel.  The salience runs over a pitch ring of its own, `self.pitch_ring`, the
+    carried decode over `self.viterbi`, and they give `self.f0` and `self.confidence` (1 - d' along the path).
     `pitch_delay_samples == loudness_delay_samples + pitch_lag * block_size`; the loudness is NOT delayed to match
     (the stance above for an external pitch), and ``pitch_lag=0``, the default, adds no latency.  `reset()` gives a
-    fresh decode.
+    fresh decode.  Which launches the analysis makes over which rings, for any of these options, is
+    `features.stream_analysis_route`'s table at `route_for`'s (mfcc, pitch); `self.plan`
+    (features.StreamAnalysisPlan) holds the states and runs it.
 
     A ``DDSPAutoencoder`` (recognised by ``model.decoder.add_z`` and ``model.encoder``) needs
     ``loudness_from_audio=True``: its encoder's MFCC can only come from audio.  With ``pitch_from_audio=True``
@@ -159,39 +161,28 @@ class RealtimeGraph:
             if self.reverb:
                 self._spec = torch.empty(int(core._lib.query("stream_spectrum_floats", N, L)), device=device)
                 self.refresh()
-        self.loudness_from_audio = bool(loudness_from_audio)
-        self.analysis = None
-        self.loudness_delay_samples = 0
-        if self.loudness_from_audio:  # raises on a call size or block the streamed analysis cannot take
-            self.analysis = core.FeatureStreamState(1, device, N, 2048, bs, counter=self.counter)
-            self.loudness_delay_samples = self.analysis.delay_frames * bs
-        self.pitch_from_audio = bool(pitch_from_audio)
-        self.pitch_fmin, self.pitch_fmax = float(pitch_fmin), float(pitch_fmax)
-        self.pitch_threshold = float(pitch_threshold)
-        self.pitch_delay_samples = 0
-        self.f0 = self.confidence = None
-        if self.pitch_from_audio:
-            if not self.loudness_from_audio:
-                raise RuntimeError("RealtimeGraph: pitch_from_audio=True needs loudness_from_audio=True (one launch "
-                                   "computes both from the same frames of the same ring)")
-            core.pitch_lags(self.sample_rate, self.pitch_fmin, self.pitch_fmax, self.analysis.n_fft)  # a bad range
-            self.pitch_delay_samples = self.loudness_delay_samples
-        self.pitch_viterbi, self.pitch_lag = bool(pitch_viterbi), int(pitch_lag)
-        self.pitch_transition, self.pitch_max_jump = float(pitch_transition), int(pitch_max_jump)
-        self.pitch_ring = self.viterbi = None
-        if self.pitch_viterbi:
-            if not self.pitch_from_audio:
-                raise RuntimeError("RealtimeGraph: pitch_viterbi=True decodes the pitch computed from the audio; it "
-                                   "needs pitch_from_audio=True")
-            n_bins = core.stream_pitch_bin_count(self.sample_rate, self.pitch_fmin, self.pitch_fmax,
-                                                 self.analysis.n_fft)
-            self.pitch_ring = core.FeatureStreamState(1, device, N, self.analysis.n_fft, bs, counter=self.counter)
-            self.viterbi = core.ViterbiStreamState(1, device, N // bs, n_bins, self.pitch_lag, counter=self.counter)
-            self.pitch_delay_samples = self.loudness_delay_samples + self.pitch_lag * bs
-        self.mfcc_delay_samples = 0
-        self.z = self.mfcc = self.encoder_state = None
+        self.loudness_from_audio, self.pitch_from_audio = bool(loudness_from_audio), bool(pitch_from_audio)
+        self.pitch_viterbi = bool(pitch_viterbi)
+        if self.pitch_from_audio and not self.loudness_from_audio:
+            raise RuntimeError("RealtimeGraph: pitch_from_audio=True needs loudness_from_audio=True (one launch "
+                               "computes both from the same frames of the same ring)")
+        route = self.route_for(self.autoencoder, self.pitch_from_audio, self.pitch_viterbi)
+        self.plan = self.analysis = self.pitch_ring = self.viterbi = None
+        self.f0 = self.confidence = self.z = self.mfcc = self.encoder_state = None
+        delay = {}
+        if self.loudness_from_audio:  # raises on a call size, a block or a pitch range the analysis cannot take
+            self.plan = StreamAnalysisPlan(
+                stream_analysis_route(*route), self.sample_rate, bs, N, 1, device, counter=self.counter,
+                n_mfcc=model.encoder.gru.input_size if self.autoencoder else 30, fmin=pitch_fmin, fmax=pitch_fmax,
+                threshold=pitch_threshold, pitch_lag=pitch_lag, pitch_transition=pitch_transition,
+                pitch_max_jump=pitch_max_jump)
+            delay = self.plan.delay_frames
+            self.analysis, self.viterbi = self.plan.states["loudness"], self.plan.viterbi_state
+            if self.pitch_viterbi:  # the salience's ring; the per-frame pick reads the analysis's
+                self.pitch_ring = self.plan.states["pitch"]
+        self.loudness_delay_samples, self.pitch_delay_samples, self.mfcc_delay_samples = (
+            delay.get(k, 0) * bs for k in ("loudness", "pitch", "mfcc"))
         if self.autoencoder:  # the encoder GRU's carried state is this object's: the model's state_dict stays as it is
-            self.mfcc_delay_samples = self.loudness_delay_samples
             self.encoder_state = torch.zeros(1, 1, model.encoder.gru.hidden_size, device=device)
         self._inp_h = torch.zeros(2, N, 1).pin_memory()
         self._out_h = torch.zeros(1, N, 1).pin_memory()
@@ -213,17 +204,8 @@ class RealtimeGraph:
         with torch.no_grad(), torch.cuda.graph(self.graph):
             self.out = self._forward()
         torch.cuda.synchronize(device)
+        self.reset()  # the warm-up and the capture ran the stream
         model.decoder.cache_gru.copy_(cache0)
-        if self.encoder_state is not None:
-            self.encoder_state.zero_()
-        self.counter.zero_()
-        if self.stream is not None:
-            self.stream.reset()
-        if self.analysis is not None:
-            self.analysis.reset()
-        if self.viterbi is not None:
-            self.pitch_ring.reset()
-            self.viterbi.reset()
 
     def refresh(self):
         """Rebuild the streamed reverb's IR spectra from the model's reverb parameters (in place: the
@@ -251,39 +233,23 @@ class RealtimeGraph:
     def _control_frames(self):
         """The call's pitch and loudness, one value per frame: (pitch, its stride, loudness, its stride) — the
         inputs decimated by block_size; with ``loudness_from_audio`` the loudness is the streamed analysis of the
-        audio in the loudness buffer (stride 1); with ``pitch_from_audio`` both come from that audio in one launch,
-        and the call's f0 and confidence stay in ``self.f0`` / ``self.confidence``; with ``pitch_viterbi`` that launch
-        leaves the pitch out and the salience and the carried decode give them."""
+        audio in the loudness buffer (stride 1); with ``pitch_from_audio`` both come from that audio, and the call's
+        f0 and confidence stay in ``self.f0`` / ``self.confidence`` (the MFCC in ``self.mfcc``): ``self.plan``'s run."""
         if not self.loudness_from_audio:
             return self.pitch, self.block_size, self.loudness, self.block_size
-        raw_pitch = self.pitch_from_audio and not self.pitch_viterbi  # the per-frame pick, in the analysis launch
-        if self.pitch_viterbi:
-            self.f0, self.confidence = core.stream_track_pitch(
-                self.loudness, self.sample_rate, self.block_size, self.pitch_ring, self.viterbi, fmin=self.pitch_fmin,
-                fmax=self.pitch_fmax, frame_length=self.analysis.n_fft, transition=self.pitch_transition,
-                max_jump=self.pitch_max_jump, return_confidence=True)
-        if self.autoencoder:  # one launch, one ring, one time axis: the loudness, the MFCC and (from audio) the pitch
-            got = core.stream_analysis_mfcc(
-                self.loudness, self.sample_rate, self.block_size, self.analysis, pitch=raw_pitch,
-                fmin=self.pitch_fmin, fmax=self.pitch_fmax, frame_length=self.analysis.n_fft,
-                threshold=self.pitch_threshold, return_confidence=raw_pitch,
-                n_mfcc=self.model.encoder.gru.input_size)
-            loud, self.mfcc = got[:2]
-            if not self.pitch_from_audio:
-                return self.pitch, self.block_size, loud, 1
-            if raw_pitch:
-                self.f0, self.confidence = got[2:]
-            return self.f0, 1, loud, 1
-        if not raw_pitch:
-            loud = core.stream_loudness(self.loudness, self.sample_rate, self.block_size, self.analysis)
-            if self.pitch_viterbi:
-                return self.f0, 1, loud, 1
+        loud, self.mfcc, self.f0, self.confidence = self.plan.run(self.loudness)
+        if not self.pitch_from_audio:
             return self.pitch, self.block_size, loud, 1
-        loud, self.f0, self.confidence = core.stream_analysis(
-            self.loudness, self.sample_rate, self.block_size, self.analysis, fmin=self.pitch_fmin,
-            fmax=self.pitch_fmax, frame_length=self.analysis.n_fft, threshold=self.pitch_threshold,
-            return_confidence=True)
         return self.f0, 1, loud, 1
+
+    @staticmethod
+    def route_for(autoencoder=False, pitch_from_audio=False, pitch_viterbi=False):
+        """The flags -> ``features.stream_analysis_route``'s (mfcc, pitch) of the graph's analysis."""
+        if pitch_viterbi and not pitch_from_audio:
+            raise RuntimeError("RealtimeGraph: pitch_viterbi=True decodes the pitch computed from the audio; it "
+                               "needs pitch_from_audio=True")
+        pitch = None if not pitch_from_audio else "viterbi" if pitch_viterbi else "fused"
+        return "aligned" if autoencoder else None, pitch
 
     def _setup_fused(self):
         m, dev = self.model, self.device
@@ -395,11 +361,8 @@ class RealtimeGraph:
         self.counter.zero_()
         if self.stream is not None:
             self.stream.reset()
-        if self.analysis is not None:
-            self.analysis.reset()
-        if self.viterbi is not None:
-            self.pitch_ring.reset()
-            self.viterbi.reset()
+        if self.plan is not None:
+            self.plan.reset()
 
     @torch.no_grad()
     def __call__(self, pitch, loudness=None):

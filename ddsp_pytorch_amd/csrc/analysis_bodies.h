@@ -1,8 +1,15 @@
-// The per-frame bodies of the analysis kernels, written once: the loudness's reduction over a packed spectrum
-// (features.hip's loudness kernels), the YIN estimator of one frame (pitch.hip's kernels) and the streamed MFCC of
-// one call (features.hip's stream_mfcc_kernel), with the envelope and the grid arithmetic that go with them.
-// stream_analysis.hip and stream_analysis_mfcc.hip run them side by side in one launch, in different workgroups;
-// since the bodies are these, their bits are those of the separate launches.
+// The workgroup roles of the analysis kernels, written once; the kernels are shells around them, each with its own
+// __shared__ arrays and its own source of frames (analysis_frames.h):
+//   loudness_role    packed_spectrum + loudness_sums   features.hip's loudness kernels, both fused kernels
+//   pitch_role       yin_frame                         pitch.hip's kernels, both fused kernels
+//   salience_role    yin_dprime + salience_bins (+ yin_pick)   the two salience kernels
+//   stream_mfcc_body the streamed MFCC of one call     features.hip's stream_mfcc_kernel, stream_analysis_mfcc.hip
+//   mel_rows, workgroup_max                            mel_db_kernel and stream_mfcc_body
+//   viterbi_rows                                       the two decode kernels
+//   wave_argmin                                        transform_argmin (YIN's pick) and the streamed decode
+// with the envelopes and the grid arithmetic that go with them.  stream_analysis.hip and stream_analysis_mfcc.hip
+// run the roles side by side in one launch, in different workgroups; since a role has one definition, their bits are
+// those of the separate launches.
 #pragma once
 
 #include <climits>
@@ -47,6 +54,27 @@ __device__ __forceinline__ void loudness_sums(const double2* lds, const float* _
   transform_sum2<Q>(sa, sb, red, tr);
 }
 
+// The loudness role of a workgroup: workgroup `block` of the role takes frames fa = 2 (block TPW + tr) and fa + 1 of
+// item b's fetch through one packed transform per transform tr (lds_all: the workgroup's kPoints<N> + kPoints<N>/16
+// slots) and writes their loudness to out[b, fa], out[b, fa + 1] (out [B, frames]; red: 8 doubles).  Every thread
+// of the workgroup calls this.
+template <int N, class Fetch>
+__device__ __forceinline__ void loudness_role(const Fetch& fetch, unsigned block, const float* w,
+                                              double2* lds_all, double* red, float* out, int b) {
+  constexpr int Q = N / 16, TPW = kPoints<N> / N, BINS = N / 2 + 1;
+  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;  // thread t of the workgroup's transform tr
+  double2* lds = lds_all + tr * (N + N / 16);
+  const int frames = fetch.frames;
+  const int fa = 2 * (block * TPW + tr);
+  packed_spectrum<N>(fetch, fa, t, lds);
+  double sa, sb;
+  loudness_sums<N>(lds, w, t, tr, red, sa, sb);
+  if (t != 0 || fa >= frames) return;
+  float* o = out + (int64_t)b * frames + fa;
+  o[0] = (float)(sa / (double)BINS);
+  if (fa + 1 < frames) o[1] = (float)(sb / (double)BINS);
+}
+
 // two frames per transform, kPoints/N transforms per workgroup
 inline unsigned frame_blocks(int64_t n_fft, int64_t frames) {
   const int64_t per = 2 * ((n_fft == 4096 ? 4096 : 2048) / n_fft);
@@ -60,6 +88,10 @@ struct PitchParams {
   int tau_min, tau_max;
   float sample_rate, threshold;
 };
+
+inline PitchParams pitch_params(int64_t tau_min, int64_t tau_max, float sample_rate, float threshold) {
+  return {(int)tau_min, (int)tau_max, sample_rate, threshold};
+}
 
 // In-place inclusive prefix sums of buf[lds_idx(j)], j < N, by the transform's Q = N/16 threads: thread t sums its
 // 16 consecutive entries in order, the threads' totals are scanned (a shuffle scan inside the wave; Q > 64: the
@@ -104,19 +136,26 @@ __device__ __forceinline__ void take_min(double& v, int& i, double ov, int oi) {
   }
 }
 
+// The smallest pair over each WIDTH lanes of a wave, valid in the first of them; a fixed order.  Any ints in `mins`
+// are each reduced to their smallest beside it, step by step in the same loop (YIN's first candidate).
+template <int WIDTH, class... Ints>
+__device__ __forceinline__ void wave_argmin(double& v, int& vi, Ints&... mins) {
+#pragma unroll
+  for (int o = WIDTH / 2; o > 0; o >>= 1) {
+    ((mins = min(mins, __shfl_down(mins, o, WIDTH))), ...);
+    const double ov = __shfl_down(v, o, WIDTH);
+    const int oi = __shfl_down(vi, o, WIDTH);
+    take_min(v, vi, ov, oi);
+  }
+}
+
 // Over the transform's Q threads: first <- the smallest `first`, (best, besti) <- the smallest pair; valid in the
 // transform's thread t == 0.  Q > 64: whole waves through LDS (one barrier); every thread of the workgroup calls it.
 template <int Q>
 __device__ __forceinline__ void transform_argmin(int& first, double& best, int& besti, double* rbest, int* rint,
                                                  int t) {
   constexpr int WIDTH = Q < 64 ? Q : 64;
-#pragma unroll
-  for (int o = WIDTH / 2; o > 0; o >>= 1) {
-    first = min(first, __shfl_down(first, o, WIDTH));
-    const double ov = __shfl_down(best, o, WIDTH);
-    const int oi = __shfl_down(besti, o, WIDTH);
-    take_min(best, besti, ov, oi);
-  }
+  wave_argmin<WIDTH>(best, besti, first);
   if constexpr (Q > 64) {
     const int lane = t & 63, wid = t >> 6;
     if (lane == 0) {
@@ -271,6 +310,20 @@ __device__ __forceinline__ void yin_frame(const Fetch& fetch, int f, int t, doub
   yin_pick<N>(dn, t, lds, wsum, rint, p, write, o, f0, conf, period);
 }
 
+// The pitch role of a workgroup: workgroup `block` of the role runs yin_frame on frame f = block TPW + tr of item
+// b's fetch, one frame per transform tr of lds_all, into slot [b, f] of f0 / conf / period [B, frames] (wsum: 4
+// doubles, rint: 8 ints).  Every thread of the workgroup calls this.
+template <int N, class Fetch>
+__device__ __forceinline__ void pitch_role(const Fetch& fetch, unsigned block, double2* lds_all, double* wsum,
+                                           int* rint, const PitchParams& p, int b, float* f0, float* conf,
+                                           int32_t* period) {
+  constexpr int Q = N / 16;
+  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;  // thread t of the workgroup's transform tr
+  const int f = block * (kPoints<N> / N) + tr;
+  yin_frame<N>(fetch, f, t, lds_all + tr * (N + N / 16), wsum, rint, p, f < fetch.frames,
+               (int64_t)b * fetch.frames + f, f0, conf, period);
+}
+
 // ---------------- pitch_viterbi: the salience of one frame (include/ddsp_hip.h, "pitch_viterbi") ----------------
 constexpr int kMaxBins = 1024;  // n_bins cap: the decodes run one thread per bin
 constexpr int kMaxJump = 127;   // max_jump cap: the back-offsets are int8
@@ -304,6 +357,43 @@ __device__ __forceinline__ void salience_bins(const double* dp, int t, const Pit
     if (lag) lag[o + i] = ts;
   }
 }
+
+// The salience role of a workgroup: workgroup `block` takes frame f = block TPW + tr of item b's fetch, one frame per
+// transform tr of lds_all: its d', then its bins into cost / f0c / lag [B, frames, n_bins], and, when f0 is given,
+// yin_pick on the same d' into f0 / conf / period [B, frames] (the pitch role's bits).  f0 is uniform over the grid,
+// as it has to be: yin_pick holds a barrier.  Every thread of the workgroup calls this.
+template <int N, class Fetch>
+__device__ __forceinline__ void salience_role(const Fetch& fetch, unsigned block, double2* lds_all, double* wsum,
+                                              int* rint, const PitchParams& p, int b, const int32_t* lo,
+                                              const int32_t* hi, int n_bins, float* cost, float* f0c, int32_t* lag,
+                                              float* f0, float* conf, int32_t* period) {
+  constexpr int Q = N / 16;
+  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;  // thread t of the workgroup's transform tr
+  const int f = block * (kPoints<N> / N) + tr;
+  double2* lds = lds_all + tr * (N + N / 16);
+  double dn[9];
+  yin_dprime<N>(fetch, f, t, lds, wsum, p, dn);
+  const int64_t o = (int64_t)b * fetch.frames + f;
+  if (f < fetch.frames) salience_bins<N>(yin_dp<N>(lds), t, p, lo, hi, n_bins, o * n_bins, cost, f0c, lag);
+  if (f0) yin_pick<N>(dn, t, lds, wsum, rint, p, f < fetch.frames, o, f0, conf, period);
+}
+
+// ---------------- the decodes' shared pieces (pitch_viterbi.hip, stream_pitch_viterbi.hip) ----------------
+constexpr int kViterbiStride = kMaxBins + 2 * kMaxJump;  // doubles per padded row of delta
+
+// The two padded rows (rows: 2 kViterbiStride doubles) set to +inf by the workgroup's nt threads and published.
+// Returns the first row's prev: delta(i) lives at prev[i], with prev[-R .. -1] and prev[NB .. NB + R - 1] left +inf
+// (no bounds branch in the neighbour loop); the second row's is prev + kViterbiStride.
+__device__ __forceinline__ double* viterbi_rows(double* rows, int j, int nt, int R) {
+  for (int i = j; i < 2 * kViterbiStride; i += nt) rows[i] = INFINITY;
+  __syncthreads();
+  return rows + R;
+}
+
+// (The neighbour loop of the recursion, min over |k| <= R of prev[j + k] + lam |k|, and the fold of the waves' pairs
+// stay written out in the two decode kernels.  The offline decode is latency-bound per frame, and each of its pieces
+// tried as a function here changed its code: the neighbour loop, in every form, came out with its exit block after
+// the body and a commuted v_add_f64; pitch_viterbi.hip says what wave_argmin and the fold did.)
 
 // The parameters the pitch entry points share (include/ddsp_hip.h), checked before any HIP call.
 inline int check_pitch_params(int64_t L, int64_t tau_min, int64_t tau_max, float sample_rate) {
@@ -379,6 +469,40 @@ __device__ __forceinline__ float2 mel_db_pair(const double2* lds, const float* _
   return make_float2(10.0f * log10f(fmaxf(1e-10f, (float)ea)), 10.0f * log10f(fmaxf(1e-10f, (float)eb)));
 }
 
+// Mel rows t, t + Q, ... (stage_bands' tables) of the two packed frames whose powers are in lds: frame a's to Da[m]
+// when va, frame b's to Da[n_mels + m] when vb, and the stored values folded into mx.
+template <int N>
+__device__ __forceinline__ void mel_rows(const double2* lds, int t, const float* band_w, int n_w,
+                                         const int* s_start, const int* s_count, const int* s_off, int n_mels,
+                                         bool va, bool vb, float* Da, float& mx) {
+  for (int m = t; m < n_mels; m += N / 16) {
+    const float2 d = mel_db_pair(lds, band_w, n_w, s_start[m], s_count[m], s_off[m]);
+    if (va) {
+      Da[m] = d.x;
+      mx = fmaxf(mx, d.x);
+    }
+    if (vb) {
+      Da[n_mels + m] = d.y;
+      mx = fmaxf(mx, d.y);
+    }
+  }
+}
+
+// The largest mx over a workgroup of WAVES waves (s_max: WAVES floats), valid in thread 0; one barrier.
+template <int WAVES>
+__device__ __forceinline__ float workgroup_max(float mx, float* s_max) {
+  const int tid = threadIdx.x;
+  mx = wave_max(mx);
+  if ((tid & 63) == 0) s_max[tid >> 6] = mx;
+  __syncthreads();
+  if (tid == 0) {
+    mx = s_max[0];
+#pragma unroll
+    for (int i = 1; i < WAVES; ++i) mx = fmaxf(mx, s_max[i]);
+  }
+  return mx;
+}
+
 // One pass of the MFCC's loop: frames fa and fa + 1 of the call through the packed transform, then both frames'
 // power over the spectrum in place (the thread that owns the pair {k, N-k} writes slot k; no other thread reads k
 // or N-k), published by the closing barrier.  Kept out of line on purpose: inlined into the caller's loop over
@@ -431,36 +555,20 @@ __device__ __forceinline__ void stream_mfcc_body(const StreamFetch& fetch, bool 
   float* sT = reinterpret_cast<float*>(lds_all);
   float* sD = s.sD;
   const int frames = fetch.frames, n_mels = m.n_mels, n_mfcc = m.n_mfcc;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x;
   stage_bands<THREADS, BINS>(m.start, m.count, n_mels, s.s_start, s.s_count, s.s_off, s.s_wave);
-  const int tr = tid / Q, t = tid - tr * Q;
+  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;  // thread t of the workgroup's transform tr
   double2* lds = lds_all + tr * (N + N / 16);
   float mx = -INFINITY;
   for (int f0 = 0; f0 < frames; f0 += 2 * TPW) {
     const int fa = f0 + 2 * tr;
     spectrum_power_pass<N>(fetch, fa, t, lds);  // (its barriers publish s_*)
     const bool va = fa < frames, vb = fa + 1 < frames;
-    float* Da = sD + (va ? fa : 0) * n_mels;
-    for (int mm = t; mm < n_mels; mm += Q) {
-      const float2 d = mel_db_pair(lds, m.w, m.n_w, s.s_start[mm], s.s_count[mm], s.s_off[mm]);
-      if (va) {
-        Da[mm] = d.x;
-        mx = fmaxf(mx, d.x);
-      }
-      if (vb) {
-        Da[n_mels + mm] = d.y;
-        mx = fmaxf(mx, d.y);
-      }
-    }
+    mel_rows<N>(lds, t, m.w, m.n_w, s.s_start, s.s_count, s.s_off, n_mels, va, vb, sD + (va ? fa : 0) * n_mels, mx);
     __syncthreads();  // the powers consumed before the next pass (or the DCT table) overwrites them
   }
-  mx = wave_max(mx);
-  if (lane == 0) s.s_max[wid] = mx;
-  __syncthreads();
+  float r = workgroup_max<WAVES>(mx, s.s_max);
   if (tid == 0) {
-    float r = s.s_max[0];
-#pragma unroll
-    for (int i = 1; i < WAVES; ++i) r = fmaxf(r, s.s_max[i]);
     if (carried) r = fmaxf(r, *runmax);
     *runmax = r;
     *s.s_floor = r - m.top_db;
@@ -504,24 +612,18 @@ __device__ __forceinline__ void stream_mfcc_body(const StreamFetch& fetch, bool 
   }
 }
 
-// The streamed MFCC's parameters (include/ddsp_hip.h, ddsp_hip_stream_mfcc's limits), checked before any HIP call;
-// the streaming envelope is the caller's.
-inline int check_stream_mfcc_params(int64_t n_band_weights, int64_t n_mels, int64_t n_mfcc, float top_db) {
-  if (n_band_weights < 0 || n_band_weights > INT32_MAX || !(top_db >= 0.0f)) return DDSP_HIP_EINVAL;
-  if (n_mels < 1 || n_mfcc < 1 || n_mfcc > n_mels) return DDSP_HIP_EINVAL;
-  return n_mels > kMaxMels ? DDSP_HIP_ERANGE : DDSP_HIP_OK;
+// The MFCC parameters that are invalid whatever the envelope (include/ddsp_hip.h), checked before any HIP call.
+inline bool mfcc_params_invalid(int64_t n_band_weights, int64_t n_mels, int64_t n_mfcc, float top_db) {
+  return n_band_weights < 0 || n_band_weights > INT32_MAX || !(top_db >= 0.0f) || n_mels < 1 || n_mfcc < 1 ||
+         n_mfcc > n_mels;
 }
 
-#define DDSP_FOR_FRAME_LENGTH(L, CALL) \
-  switch (L) {                         \
-    case 64: return CALL(64);          \
-    case 128: return CALL(128);        \
-    case 256: return CALL(256);        \
-    case 512: return CALL(512);        \
-    case 1024: return CALL(1024);      \
-    case 2048: return CALL(2048);      \
-    default: return CALL(4096);        \
-  }
+// The streamed MFCC's parameters where nothing is checked between the invalid ones and the n_mels cap
+// (ddsp_hip_stream_analysis_mfcc); the streaming envelope is the caller's.
+inline int check_stream_mfcc_params(int64_t n_band_weights, int64_t n_mels, int64_t n_mfcc, float top_db) {
+  if (mfcc_params_invalid(n_band_weights, n_mels, n_mfcc, top_db)) return DDSP_HIP_EINVAL;
+  return n_mels > kMaxMels ? DDSP_HIP_ERANGE : DDSP_HIP_OK;
+}
 
 }  // namespace
 }  // namespace ddsp

@@ -1,10 +1,14 @@
 // What the analysis kernels share (features.hip: loudness, MFCC; pitch.hip: YIN f0): where a frame's samples come
-// from, offline (reflect padding) and per call of a stream (the carried ring), the call arithmetic of a stream, and
-// the identities by which two real sequences ride one complex fp64 transform.  Written once, so that the features
-// cannot disagree about a frame.  (analysis_bodies.h holds what is computed per frame.)
+// from, offline (reflect padding) and per call of a stream (the carried ring), the call arithmetic of a stream and its
+// opening (open_stream_call), how a workgroup's threads split over its transforms, the identities
+// by which two real sequences ride one complex fp64 transform, and the launchers' dispatch on the transform size
+// (for_frame_length).  Written once, so that the features cannot disagree about a frame.  (analysis_bodies.h holds
+// what is computed per frame: the workgroup roles.)
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "common.h"
 #include "fft_radix_f64.h"
@@ -15,6 +19,12 @@ namespace {
 
 template <int N>
 constexpr int kPoints = N == 4096 ? 4096 : 2048;  // points per workgroup; threads = points / 16
+
+// A workgroup's threads split over its kPoints<N>/N transforms, Q = N/16 threads each: thread t = threadIdx.x - tr * Q
+// of transform tr = threadIdx.x / Q, whose LDS slots (N + N/16 double2: lds_idx's padding) start at
+// lds_all + tr * (N + N/16).  The roles of analysis_bodies.h spell this line out: gathered in a struct, handed back
+// through references, or with t behind a function, the same arithmetic came out of the compiler with other register
+// counts in kernels around it (gfx950: loudness_kernel<32> and the kernels of N = 512).
 
 // Where a frame's samples come from: fetch(f, i) is sample i (0 <= i < N) of frame f's N-sample window, 0.0f for a
 // frame the caller does not have.  Offline: frame f of row xr[T] is centred at f * hop with reflect padding.
@@ -116,6 +126,19 @@ struct StreamCall {
   }
 };
 
+// How every streamed kernel opens call k (the counter's value) for item b: thread `i0` of the `stride` that share the
+// item copies its share of the call's input into the ring, and the item's fetch comes back.  A role whose window is
+// shorter than the ring's moves the fetch's rel0 forward.
+__device__ __forceinline__ StreamFetch open_stream_call(uint64_t k, float* ring, const float* __restrict__ x, int n,
+                                                        int len, int hs, int hop, int frames, int b, int i0,
+                                                        int stride) {
+  const StreamCall call{k, n, len, hs, hop, frames};
+  float* rb = ring + (int64_t)b * len;
+  const float* xb = x + (int64_t)b * n;
+  call.store(rb, xb, i0, stride);
+  return call.fetch(rb, xb);
+}
+
 // The streaming envelope (include/ddsp_hip.h) and the sizes it implies.
 struct StreamSizes {
   int64_t frames, hs, len;  // frames per call, carried samples, ring floats per item
@@ -150,6 +173,17 @@ inline StreamArgs stream_args(const float* x, const uint64_t* counter, void* sta
                               const StreamSizes& sz, void* stream) {
   return {x, counter, reinterpret_cast<float*>(state), B, (int)n, (int)sz.len, (int)sz.hs, (int)hop, (int)sz.frames,
           stream};
+}
+
+// The launchers' one dispatch on the transform size: f(std::integral_constant<int, L>{}) for a power of two L in
+// [N, MAX), f(<MAX>) for anything else (the entry points have checked L against their envelopes).
+template <int N, int MAX = 4096, class F>
+inline int for_frame_length(int64_t L, const F& f) {
+  if constexpr (N < MAX) {
+    return L == N ? f(std::integral_constant<int, N>{}) : for_frame_length<2 * N, MAX>(L, f);
+  } else {
+    return f(std::integral_constant<int, MAX>{});
+  }
 }
 
 }  // namespace

@@ -22,8 +22,9 @@
 //
 // A workgroup transforms kPoints<N> points: 2048 (128 threads, 34 KB of LDS, 2048/N transforms) or, for
 // N = 4096, one transform of 4096 (256 threads, 68 KB: gfx950's LDS is 160 KB per CU).
-// The loudness's reduction over a packed spectrum (loudness_sums) and the MFCC's pieces (the band tables, the mel
-// rows, the streamed call's body) are in analysis_bodies.h, shared with stream_analysis.hip.
+// The kernels are shells around analysis_bodies.h's roles: loudness_kernel and stream_loudness_kernel around
+// loudness_role, stream_mfcc_kernel around stream_mfcc_body, mel_db_kernel around the MFCC's pieces (stage_bands,
+// mel_rows, workgroup_max); stream_analysis.hip and stream_analysis_mfcc.hip run the same roles.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,20 +40,11 @@ template <int N>
 __global__ void __launch_bounds__(kPoints<N> / 16) loudness_kernel(const float* __restrict__ x, int64_t T, int hop,
                                                                    int frames, const float* __restrict__ w,
                                                                    float* __restrict__ out) {
-  constexpr int Q = N / 16, TPW = kPoints<N> / N, BINS = N / 2 + 1;
+  constexpr int TPW = kPoints<N> / N;
   __shared__ double2 lds_all[TPW * (N + N / 16)];
   __shared__ double red[8];
-  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;
-  double2* lds = lds_all + tr * (N + N / 16);
   const int b = blockIdx.y;
-  const int fa = 2 * (blockIdx.x * TPW + tr);
-  packed_spectrum<N>(ReflectFetch<N>{x + (int64_t)b * T, T, hop, frames}, fa, t, lds);
-  double sa, sb;
-  loudness_sums<N>(lds, w, t, tr, red, sa, sb);
-  if (t != 0 || fa >= frames) return;
-  float* o = out + (int64_t)b * frames + fa;
-  o[0] = (float)(sa / (double)BINS);
-  if (fa + 1 < frames) o[1] = (float)(sb / (double)BINS);
+  loudness_role<N>(ReflectFetch<N>{x + (int64_t)b * T, T, hop, frames}, blockIdx.x, w, lds_all, red, out, b);
 }
 
 // MFCC launch (a).  grid (ceil(frames / (2 * kPoints/N)), B), kPoints/16 threads.  Mel row m is the band
@@ -72,9 +64,8 @@ __global__ void __launch_bounds__(kPoints<N> / 16) mel_db_kernel(const float* __
   __shared__ int s_start[kMaxMels], s_count[kMaxMels], s_off[kMaxMels];
   __shared__ int s_wave[WAVES];
   __shared__ float s_max[WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   stage_bands<THREADS, BINS>(band_start, band_count, n_mels, s_start, s_count, s_off, s_wave);
-  const int tr = tid / Q, t = tid - tr * Q;
+  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;
   double2* lds = lds_all + tr * (N + N / 16);
   const int b = blockIdx.y;
   const int fa = 2 * (blockIdx.x * TPW + tr);
@@ -85,29 +76,11 @@ __global__ void __launch_bounds__(kPoints<N> / 16) mel_db_kernel(const float* __
   for (int k = t; k < BINS; k += Q) lds[lds_idx(k)] = packed_power<N>(lds, k);
   __syncthreads();
   const bool va = fa < frames, vb = fa + 1 < frames;
-  float* Da = D + ((int64_t)b * frames + (va ? fa : 0)) * n_mels;
   float mx = -INFINITY;
-  for (int m = t; m < n_mels; m += Q) {
-    const float2 d = mel_db_pair(lds, band_w, n_w, s_start[m], s_count[m], s_off[m]);
-    const float da = d.x, db = d.y;
-    if (va) {
-      Da[m] = da;
-      mx = fmaxf(mx, da);
-    }
-    if (vb) {
-      Da[n_mels + m] = db;
-      mx = fmaxf(mx, db);
-    }
-  }
-  mx = wave_max(mx);
-  if (lane == 0) s_max[wid] = mx;
-  __syncthreads();
-  if (tid == 0) {
-    float r = s_max[0];
-#pragma unroll
-    for (int i = 1; i < WAVES; ++i) r = fmaxf(r, s_max[i]);
-    wgmax[(int64_t)b * gridDim.x + blockIdx.x] = r;
-  }
+  mel_rows<N>(lds, t, band_w, n_w, s_start, s_count, s_off, n_mels, va, vb,
+              D + ((int64_t)b * frames + (va ? fa : 0)) * n_mels, mx);
+  mx = workgroup_max<WAVES>(mx, s_max);
+  if (threadIdx.x == 0) wgmax[(int64_t)b * gridDim.x + blockIdx.x] = mx;
 }
 
 // MFCC launch (b).  grid (ceil(frames / kDctFrames), B), 256 threads.  The item's maximum from its nblk
@@ -177,25 +150,13 @@ __global__ void __launch_bounds__(kPoints<N> / 16) stream_loudness_kernel(const 
                                                                           const uint64_t* __restrict__ counter,
                                                                           float* ring, int n, int len, int hs,
                                                                           int hop, int frames) {
-  constexpr int Q = N / 16, TPW = kPoints<N> / N;
+  constexpr int TPW = kPoints<N> / N;
   __shared__ double2 lds_all[TPW * (N + N / 16)];
   __shared__ double red[8];
-  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;
-  double2* lds = lds_all + tr * (N + N / 16);
   const int b = blockIdx.y;
-  const int fa = 2 * (blockIdx.x * TPW + tr);
-  const StreamCall call{*counter, n, len, hs, hop, frames};
-  float* rb = ring + (int64_t)b * len;
-  const float* xb = x + (int64_t)b * n;
-  call.store(rb, xb, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
-  packed_spectrum<N>(call.fetch(rb, xb), fa, t, lds);
-  double sa, sb;
-  loudness_sums<N>(lds, w, t, tr, red, sa, sb);
-  if (t != 0 || fa >= frames) return;
-  constexpr int BINS = N / 2 + 1;
-  float* o = out + (int64_t)b * frames + fa;
-  o[0] = (float)(sa / (double)BINS);
-  if (fa + 1 < frames) o[1] = (float)(sb / (double)BINS);
+  const StreamFetch fetch = open_stream_call(*counter, ring, x, n, len, hs, hop, frames, b,
+                                             blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  loudness_role<N>(fetch, blockIdx.x, w, lds_all, red, out, b);
 }
 
 // The MFCC of one call in one launch: grid (B), kPoints/16 threads, one workgroup per item running
@@ -216,11 +177,8 @@ __global__ void __launch_bounds__(kPoints<N> / 16) stream_mfcc_kernel(
   __shared__ float s_floor;
   const int b = blockIdx.x;
   const uint64_t k = *counter;
-  const StreamCall call{k, n, len, hs, hop, frames};
-  float* rb = ring + (int64_t)b * len;
-  const float* xb = x + (int64_t)b * n;
-  call.store(rb, xb, threadIdx.x, THREADS);
-  stream_mfcc_body<N>(call.fetch(rb, xb), k != 0, lds_all, MfccLds{sD, s_start, s_count, s_off, s_wave, s_max, &s_floor},
+  const StreamFetch fetch = open_stream_call(k, ring, x, n, len, hs, hop, frames, b, threadIdx.x, THREADS);
+  stream_mfcc_body<N>(fetch, k != 0, lds_all, MfccLds{sD, s_start, s_count, s_off, s_wave, s_max, &s_floor},
                       MfccTables{band_start, band_count, band_w, n_w, dct, n_mels, n_mfcc, top_db}, runmax + b,
                       out + (int64_t)b * frames * n_mfcc);
 }
@@ -234,81 +192,44 @@ int check_features(int64_t B, int64_t T, int64_t n_fft, int64_t hop) {
   return DDSP_HIP_OK;
 }
 
-int check_mfcc(int64_t B, int64_t T, int64_t n_fft, int64_t hop, int64_t n_mels, int64_t n_mfcc) {
-  if (n_mels < 1 || n_mfcc < 1 || n_mfcc > n_mels) return DDSP_HIP_EINVAL;
-  const int st = check_features(B, T, n_fft, hop);
-  if (st) return st;
-  return n_mels > kMaxMels ? DDSP_HIP_ERANGE : DDSP_HIP_OK;
+int launch_loudness(const float* x, const float* w, float* out, int64_t B, int64_t T, int64_t n_fft, int hop,
+                    int frames, void* stream) {
+  return for_frame_length<16>(n_fft, [&](auto size) {
+    constexpr int N = decltype(size)::value;
+    hipLaunchKernelGGL(loudness_kernel<N>, dim3(frame_blocks(N, frames), (unsigned)B), dim3(kPoints<N> / 16), 0,
+                       S(stream), x, T, hop, frames, w, out);
+    return launch_status();
+  });
 }
 
-template <int N>
-int loudness_launch(const float* x, const float* w, float* out, int64_t B, int64_t T, int hop, int frames,
-                    void* stream) {
-  hipLaunchKernelGGL(loudness_kernel<N>, dim3(frame_blocks(N, frames), (unsigned)B), dim3(kPoints<N> / 16), 0,
-                     S(stream), x, T, hop, frames, w, out);
-  return launch_status();
+int launch_mel_db(const float* x, const int* bs, const int* bc, const float* bw, int n_w, int n_mels, float* D,
+                  float* wgmax, int64_t B, int64_t T, int64_t n_fft, int hop, int frames, void* stream) {
+  return for_frame_length<16>(n_fft, [&](auto size) {
+    constexpr int N = decltype(size)::value;
+    hipLaunchKernelGGL(mel_db_kernel<N>, dim3(frame_blocks(N, frames), (unsigned)B), dim3(kPoints<N> / 16), 0,
+                       S(stream), x, T, hop, frames, bs, bc, bw, n_w, n_mels, D, wgmax);
+    return launch_status();
+  });
 }
 
-template <int N>
-int mel_db_launch(const float* x, const int* bs, const int* bc, const float* bw, int n_w, int n_mels, float* D,
-                  float* wgmax, int64_t B, int64_t T, int hop, int frames, void* stream) {
-  hipLaunchKernelGGL(mel_db_kernel<N>, dim3(frame_blocks(N, frames), (unsigned)B), dim3(kPoints<N> / 16), 0,
-                     S(stream), x, T, hop, frames, bs, bc, bw, n_w, n_mels, D, wgmax);
-  return launch_status();
+int launch_stream_loudness(const StreamArgs& a, int64_t n_fft, const float* w, float* out) {
+  return for_frame_length<16>(n_fft, [&](auto size) {
+    constexpr int N = decltype(size)::value;
+    hipLaunchKernelGGL(stream_loudness_kernel<N>, dim3(frame_blocks(N, a.frames), (unsigned)a.B),
+                       dim3(kPoints<N> / 16), 0, S(a.stream), a.x, w, out, a.counter, a.ring, a.n, a.len, a.hs, a.hop,
+                       a.frames);
+    return launch_status();
+  });
 }
 
-#define DDSP_FOR_N_FFT(n_fft, CALL)         \
-  switch (n_fft) {                          \
-    case 16: return CALL(16);               \
-    case 32: return CALL(32);               \
-    case 64: return CALL(64);               \
-    case 128: return CALL(128);             \
-    case 256: return CALL(256);             \
-    case 512: return CALL(512);             \
-    case 1024: return CALL(1024);           \
-    case 2048: return CALL(2048);           \
-    default: return CALL(4096);             \
-  }
-
-int loudness_dispatch(const float* x, const float* w, float* out, int64_t B, int64_t T, int64_t n_fft, int hop,
-                      int frames, void* stream) {
-#define DDSP_CALL(N) loudness_launch<N>(x, w, out, B, T, hop, frames, stream)
-  DDSP_FOR_N_FFT(n_fft, DDSP_CALL)
-#undef DDSP_CALL
-}
-
-int mel_db_dispatch(const float* x, const int* bs, const int* bc, const float* bw, int n_w, int n_mels, float* D,
-                    float* wgmax, int64_t B, int64_t T, int64_t n_fft, int hop, int frames, void* stream) {
-#define DDSP_CALL(N) mel_db_launch<N>(x, bs, bc, bw, n_w, n_mels, D, wgmax, B, T, hop, frames, stream)
-  DDSP_FOR_N_FFT(n_fft, DDSP_CALL)
-#undef DDSP_CALL
-}
-
-template <int N>
-int stream_loudness_launch(const StreamArgs& a, const float* w, float* out) {
-  hipLaunchKernelGGL(stream_loudness_kernel<N>, dim3(frame_blocks(N, a.frames), (unsigned)a.B), dim3(kPoints<N> / 16),
-                     0, S(a.stream), a.x, w, out, a.counter, a.ring, a.n, a.len, a.hs, a.hop, a.frames);
-  return launch_status();
-}
-
-template <int N>
-int stream_mfcc_launch(const StreamArgs& a, const MfccTables& m, float* runmax, float* out) {
-  hipLaunchKernelGGL(stream_mfcc_kernel<N>, dim3((unsigned)a.B), dim3(kPoints<N> / 16), 0, S(a.stream), a.x, m.start,
-                     m.count, m.w, m.n_w, m.dct, out, a.counter, a.ring, runmax, a.n, a.len, a.hs, a.hop, a.frames,
-                     m.n_mels, m.n_mfcc, m.top_db);
-  return launch_status();
-}
-
-int stream_loudness_dispatch(const StreamArgs& a, int64_t n_fft, const float* w, float* out) {
-#define DDSP_CALL(N) stream_loudness_launch<N>(a, w, out)
-  DDSP_FOR_N_FFT(n_fft, DDSP_CALL)
-#undef DDSP_CALL
-}
-
-int stream_mfcc_dispatch(const StreamArgs& a, int64_t n_fft, const MfccTables& m, float* runmax, float* out) {
-#define DDSP_CALL(N) stream_mfcc_launch<N>(a, m, runmax, out)
-  DDSP_FOR_N_FFT(n_fft, DDSP_CALL)
-#undef DDSP_CALL
+int launch_stream_mfcc(const StreamArgs& a, int64_t n_fft, const MfccTables& m, float* runmax, float* out) {
+  return for_frame_length<16>(n_fft, [&](auto size) {
+    constexpr int N = decltype(size)::value;
+    hipLaunchKernelGGL(stream_mfcc_kernel<N>, dim3((unsigned)a.B), dim3(kPoints<N> / 16), 0, S(a.stream), a.x,
+                       m.start, m.count, m.w, m.n_w, m.dct, out, a.counter, a.ring, runmax, a.n, a.len, a.hs, a.hop,
+                       a.frames, m.n_mels, m.n_mfcc, m.top_db);
+    return launch_status();
+  });
 }
 
 }  // namespace
@@ -326,7 +247,7 @@ int ddsp_hip_loudness(const float* x, const float* weights, float* out, int64_t 
   if (!x || !out) return DDSP_HIP_EINVAL;
   const int frames = (int)(n_samples / hop);
   if (frames == 0) return DDSP_HIP_OK;
-  return loudness_dispatch(x, weights, out, batch, n_samples, n_fft, (int)hop, frames, stream);
+  return launch_loudness(x, weights, out, batch, n_samples, n_fft, (int)hop, frames, stream);
 }
 
 size_t ddsp_hip_mfcc_workspace_size(int64_t batch, int64_t n_samples, int64_t n_fft, int64_t hop, int64_t n_mels) {
@@ -340,9 +261,10 @@ int ddsp_hip_mfcc(const float* x, const int32_t* band_start, const int32_t* band
                   int64_t n_band_weights, const float* dct, float* out, int64_t batch, int64_t n_samples,
                   int64_t n_fft, int64_t hop, int64_t n_mels, int64_t n_mfcc, float top_db, void* workspace,
                   size_t workspace_bytes, void* stream) {
-  if (n_band_weights < 0 || n_band_weights > INT32_MAX || !(top_db >= 0.0f)) return DDSP_HIP_EINVAL;
-  int st = check_mfcc(batch, n_samples, n_fft, hop, n_mels, n_mfcc);
+  if (mfcc_params_invalid(n_band_weights, n_mels, n_mfcc, top_db)) return DDSP_HIP_EINVAL;
+  int st = check_features(batch, n_samples, n_fft, hop);
   if (st) return st;
+  if (n_mels > kMaxMels) return DDSP_HIP_ERANGE;  // after the envelope, as in ddsp_hip_stream_mfcc
   if (batch == 0) return DDSP_HIP_OK;
   if (!x || !band_start || !band_count || !band_weights || !dct || !out) return DDSP_HIP_EINVAL;
   if (!workspace || workspace_bytes < ddsp_hip_mfcc_workspace_size(batch, n_samples, n_fft, hop, n_mels))
@@ -351,8 +273,8 @@ int ddsp_hip_mfcc(const float* x, const int32_t* band_start, const int32_t* band
   const unsigned nblk = frame_blocks(n_fft, frames);
   float* D = reinterpret_cast<float*>(workspace);
   float* wgmax = D + (size_t)batch * (size_t)frames * (size_t)n_mels;
-  st = mel_db_dispatch(x, band_start, band_count, band_weights, (int)n_band_weights, (int)n_mels, D, wgmax, batch,
-                       n_samples, n_fft, (int)hop, frames, stream);
+  st = launch_mel_db(x, band_start, band_count, band_weights, (int)n_band_weights, (int)n_mels, D, wgmax, batch,
+                     n_samples, n_fft, (int)hop, frames, stream);
   if (st) return st;
   const unsigned gx = (unsigned)((frames + kDctFrames - 1) / kDctFrames);
   hipLaunchKernelGGL(mfcc_dct_kernel, dim3(gx, (unsigned)batch), dim3(256), 0, S(stream), D, wgmax, (int)nblk, frames,
@@ -375,8 +297,8 @@ int ddsp_hip_stream_loudness(const float* x, const float* weights, float* out, c
   if (batch == 0) return DDSP_HIP_OK;
   if (!x || !out || !counter || !state) return DDSP_HIP_EINVAL;
   if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
-  return stream_loudness_dispatch(stream_args(x, counter, state, batch, call_samples, hop, sz, stream), n_fft, weights,
-                                  out);
+  return launch_stream_loudness(stream_args(x, counter, state, batch, call_samples, hop, sz, stream), n_fft, weights,
+                                out);
 }
 
 int ddsp_hip_stream_mfcc(const float* x, const int32_t* band_start, const int32_t* band_count,
@@ -384,18 +306,19 @@ int ddsp_hip_stream_mfcc(const float* x, const int32_t* band_start, const int32_
                          const uint64_t* counter, void* state, size_t state_bytes, int64_t batch,
                          int64_t call_samples, int64_t n_fft, int64_t hop, int64_t n_mels, int64_t n_mfcc, float top_db,
                          void* stream) {
-  if (n_band_weights < 0 || n_band_weights > INT32_MAX || !(top_db >= 0.0f)) return DDSP_HIP_EINVAL;
-  if (n_mels < 1 || n_mfcc < 1 || n_mfcc > n_mels) return DDSP_HIP_EINVAL;
+  if (mfcc_params_invalid(n_band_weights, n_mels, n_mfcc, top_db)) return DDSP_HIP_EINVAL;
   StreamSizes sz;
   const int st = check_stream_features(batch, call_samples, n_fft, hop, &sz);
   if (st) return st;
+  // not check_stream_mfcc_params: the n_mels cap is tested after the envelope here, and a call that breaks both
+  // reports the envelope's status
   if (n_mels > kMaxMels) return DDSP_HIP_ERANGE;
   if (batch == 0) return DDSP_HIP_OK;
   if (!x || !band_start || !band_count || !band_weights || !dct || !out || !counter || !state) return DDSP_HIP_EINVAL;
   if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
   const StreamArgs a = stream_args(x, counter, state, batch, call_samples, hop, sz, stream);
   const MfccTables m{band_start, band_count, band_weights, (int)n_band_weights, dct, (int)n_mels, (int)n_mfcc, top_db};
-  return stream_mfcc_dispatch(a, n_fft, m, a.ring + (size_t)batch * (size_t)sz.len, out);
+  return launch_stream_mfcc(a, n_fft, m, a.ring + (size_t)batch * (size_t)sz.len, out);
 }
 
 }  // extern "C"

@@ -22,7 +22,8 @@
 // A workgroup holds kPoints<N> points as features.hip does: 2048 (128 threads, 2048/N frames) or, for N = 4096, one
 // frame of 4096 (256 threads); 34 KB / 68 KB of LDS, used in turn by the transforms, the two scans and d'.  Nothing
 // but the transform's own registers lives across the transforms (230 VGPRs at N = 2048: two waves per SIMD).
-// The per-frame body (yin_frame and its helpers) is in analysis_bodies.h, shared with stream_analysis.hip.
+// Both kernels are shells around pitch_role (analysis_bodies.h: yin_frame and its helpers), which stream_analysis.hip
+// and stream_analysis_mfcc.hip run too.
 #include <hip/hip_runtime.h>
 
 #include "analysis_bodies.h"
@@ -36,15 +37,13 @@ __global__ void __launch_bounds__(kPoints<N> / 16) pitch_kernel(const float* __r
                                                                 int frames, PitchParams p, float* __restrict__ f0,
                                                                 float* __restrict__ conf,
                                                                 int32_t* __restrict__ period) {
-  constexpr int Q = N / 16, TPW = kPoints<N> / N;
+  constexpr int TPW = kPoints<N> / N;
   __shared__ double2 lds_all[TPW * (N + N / 16)];
   __shared__ double wsum[4];
   __shared__ int rint[8];
-  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;
   const int b = blockIdx.y;
-  const int f = blockIdx.x * TPW + tr;
-  yin_frame<N>(ReflectFetch<N>{x + (int64_t)b * T, T, hop, frames}, f, t, lds_all + tr * (N + N / 16), wsum, rint, p,
-               f < frames, (int64_t)b * frames + f, f0, conf, period);
+  pitch_role<N>(ReflectFetch<N>{x + (int64_t)b * T, T, hop, frames}, blockIdx.x, lds_all, wsum, rint, p, b, f0, conf,
+                period);
 }
 
 // grid (ceil(frames / (kPoints/N)), B), kPoints/16 threads; outputs [B, frames].  The item's workgroups share the
@@ -57,48 +56,34 @@ __global__ void __launch_bounds__(kPoints<N> / 16) stream_pitch_kernel(const flo
                                                                        float* __restrict__ f0,
                                                                        float* __restrict__ conf,
                                                                        int32_t* __restrict__ period) {
-  constexpr int Q = N / 16, TPW = kPoints<N> / N;
+  constexpr int TPW = kPoints<N> / N;
   __shared__ double2 lds_all[TPW * (N + N / 16)];
   __shared__ double wsum[4];
   __shared__ int rint[8];
-  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;
   const int b = blockIdx.y;
-  const int j = blockIdx.x * TPW + tr;
-  const StreamCall call{*counter, n, len, hs, hop, frames};
-  float* rb = ring + (int64_t)b * len;
-  const float* xb = x + (int64_t)b * n;
-  call.store(rb, xb, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
-  yin_frame<N>(call.fetch(rb, xb), j, t, lds_all + tr * (N + N / 16), wsum, rint, p, j < frames,
-               (int64_t)b * frames + j, f0, conf, period);
+  const StreamFetch fetch = open_stream_call(*counter, ring, x, n, len, hs, hop, frames, b,
+                                             blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  pitch_role<N>(fetch, blockIdx.x, lds_all, wsum, rint, p, b, f0, conf, period);
 }
 
-template <int N>
-int pitch_launch(const float* x, int64_t B, int64_t T, int hop, int frames, const PitchParams& p, float* f0,
-                 float* conf, int32_t* period, void* stream) {
-  hipLaunchKernelGGL(pitch_kernel<N>, dim3(pitch_blocks(N, frames), (unsigned)B), dim3(kPoints<N> / 16), 0, S(stream),
-                     x, T, hop, frames, p, f0, conf, period);
-  return launch_status();
+int launch_pitch(const float* x, int64_t B, int64_t T, int64_t L, int hop, int frames, const PitchParams& p,
+                 float* f0, float* conf, int32_t* period, void* stream) {
+  return for_frame_length<kPitchMinFrame>(L, [&](auto size) {
+    constexpr int N = decltype(size)::value;
+    hipLaunchKernelGGL(pitch_kernel<N>, dim3(pitch_blocks(N, frames), (unsigned)B), dim3(kPoints<N> / 16), 0,
+                       S(stream), x, T, hop, frames, p, f0, conf, period);
+    return launch_status();
+  });
 }
 
-template <int N>
-int stream_pitch_launch(const StreamArgs& a, const PitchParams& p, float* f0, float* conf, int32_t* period) {
-  hipLaunchKernelGGL(stream_pitch_kernel<N>, dim3(pitch_blocks(N, a.frames), (unsigned)a.B), dim3(kPoints<N> / 16), 0,
-                     S(a.stream), a.x, a.counter, a.ring, a.n, a.len, a.hs, a.hop, a.frames, p, f0, conf, period);
-  return launch_status();
-}
-
-int pitch_dispatch(const float* x, int64_t B, int64_t T, int64_t L, int hop, int frames, const PitchParams& p,
-                   float* f0, float* conf, int32_t* period, void* stream) {
-#define DDSP_CALL(N) pitch_launch<N>(x, B, T, hop, frames, p, f0, conf, period, stream)
-  DDSP_FOR_FRAME_LENGTH(L, DDSP_CALL)
-#undef DDSP_CALL
-}
-
-int stream_pitch_dispatch(const StreamArgs& a, int64_t L, const PitchParams& p, float* f0, float* conf,
-                          int32_t* period) {
-#define DDSP_CALL(N) stream_pitch_launch<N>(a, p, f0, conf, period)
-  DDSP_FOR_FRAME_LENGTH(L, DDSP_CALL)
-#undef DDSP_CALL
+int launch_stream_pitch(const StreamArgs& a, int64_t L, const PitchParams& p, float* f0, float* conf,
+                        int32_t* period) {
+  return for_frame_length<kPitchMinFrame>(L, [&](auto size) {
+    constexpr int N = decltype(size)::value;
+    hipLaunchKernelGGL(stream_pitch_kernel<N>, dim3(pitch_blocks(N, a.frames), (unsigned)a.B), dim3(kPoints<N> / 16),
+                       0, S(a.stream), a.x, a.counter, a.ring, a.n, a.len, a.hs, a.hop, a.frames, p, f0, conf, period);
+    return launch_status();
+  });
 }
 
 }  // namespace
@@ -120,8 +105,8 @@ int ddsp_hip_pitch(const float* x, float* f0, float* confidence, int32_t* period
   if (!x || !f0) return DDSP_HIP_EINVAL;
   const int frames = (int)(n_samples / hop);
   if (frames == 0) return DDSP_HIP_OK;
-  const PitchParams p{(int)tau_min, (int)tau_max, sample_rate, threshold};
-  return pitch_dispatch(x, batch, n_samples, frame_length, (int)hop, frames, p, f0, confidence, period, stream);
+  return launch_pitch(x, batch, n_samples, frame_length, (int)hop, frames,
+                      pitch_params(tau_min, tau_max, sample_rate, threshold), f0, confidence, period, stream);
 }
 
 int ddsp_hip_stream_pitch(const float* x, float* f0, float* confidence, int32_t* period, const uint64_t* counter,
@@ -137,8 +122,8 @@ int ddsp_hip_stream_pitch(const float* x, float* f0, float* confidence, int32_t*
   if (!x || !f0 || !counter || !state) return DDSP_HIP_EINVAL;
   if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
   const StreamArgs a = stream_args(x, counter, state, batch, call_samples, hop, sz, stream);
-  const PitchParams p{(int)tau_min, (int)tau_max, sample_rate, threshold};
-  return stream_pitch_dispatch(a, frame_length, p, f0, confidence, period);
+  return launch_stream_pitch(a, frame_length, pitch_params(tau_min, tau_max, sample_rate, threshold), f0, confidence,
+                             period);
 }
 
 }  // extern "C"

@@ -2,12 +2,14 @@
 // decode over time (one launch).  include/ddsp_hip.h ("pitch_viterbi") holds the definition; tests/viterbi_ref.py
 // restates it in numpy.
 //
-// Salience: pitch_kernel's grid and workgroup; the frame's d' by yin_dprime (analysis_bodies.h, the first part of
-// yin_frame), then the transform's Q threads take bins t, t + Q, ..., each scanning its few lags of d' in LDS and
-// finishing the parabola.  With the raw outputs asked for, yin_pick runs on the same d': ddsp_hip_pitch's bits.
+// Salience: pitch_kernel's grid and workgroup around salience_role (analysis_bodies.h): the frame's d' by yin_dprime
+// (the first part of yin_frame), then the transform's Q threads take bins t, t + Q, ..., each scanning its few lags of
+// d' in LDS and finishing the parabola.  With the raw outputs asked for, yin_pick runs on the same d': ddsp_hip_pitch's
+// bits.
 //
 // Decode: one workgroup per item, one thread per bin.  delta lives in LDS as two fp64 rows with R entries of +inf
-// on each side (no bounds branch in the neighbour loop), written in turn: one barrier per frame.  The next frame's
+// on each side (viterbi_rows; no bounds branch in the neighbour loop), written in turn: one barrier per frame;
+// the rows' set-up (viterbi_rows) is analysis_bodies.h's, shared with stream_pitch_viterbi.hip.  The next frame's
 // cost is loaded before the barrier, off the dependent chain.  Back-offsets i - j go to the workspace as int8; the
 // backtrack stages them into LDS in chunks of viterbi_chunk_frames(n_bins) frames (coalesced), one thread walks the
 // chunk in LDS, and all threads gather and store the chunk's path, f0 and confidence.  Fixed orders, no atomics.
@@ -35,27 +37,20 @@ __global__ void __launch_bounds__(kPoints<N> / 16) pitch_salience_kernel(
     const float* __restrict__ x, int64_t T, int hop, int frames, PitchParams p, const int32_t* __restrict__ lo,
     const int32_t* __restrict__ hi, int n_bins, float* __restrict__ cost, float* __restrict__ f0c,
     int32_t* __restrict__ lag, float* __restrict__ f0, float* __restrict__ conf, int32_t* __restrict__ period) {
-  constexpr int Q = N / 16, TPW = kPoints<N> / N;
+  constexpr int TPW = kPoints<N> / N;
   __shared__ double2 lds_all[TPW * (N + N / 16)];
   __shared__ double wsum[4];
   __shared__ int rint[8];
-  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;
   const int b = blockIdx.y;
-  const int f = blockIdx.x * TPW + tr;
-  double2* lds = lds_all + tr * (N + N / 16);
-  double dn[9];
-  yin_dprime<N>(ReflectFetch<N>{x + (int64_t)b * T, T, hop, frames}, f, t, lds, wsum, p, dn);
-  const int64_t o = (int64_t)b * frames + f;
-  if (f < frames) salience_bins<N>(yin_dp<N>(lds), t, p, lo, hi, n_bins, o * n_bins, cost, f0c, lag);
-  if (f0) yin_pick<N>(dn, t, lds, wsum, rint, p, f < frames, o, f0, conf, period);  // (uniform: its barrier)
+  salience_role<N>(ReflectFetch<N>{x + (int64_t)b * T, T, hop, frames}, blockIdx.x, lds_all, wsum, rint, p, b, lo, hi,
+                   n_bins, cost, f0c, lag, f0, conf, period);
 }
 
 // grid B, n_bins rounded up to whole waves; ws [B, frames, n_bins] int8
 __global__ void __launch_bounds__(kMaxBins) pitch_viterbi_kernel(
     const float* __restrict__ cost, const float* __restrict__ f0c, float* __restrict__ f0, float* __restrict__ conf,
     int32_t* __restrict__ path, int8_t* ws, int frames, int NB, int R, float transition) {
-  constexpr int STRIDE = kMaxBins + 2 * kMaxJump;
-  __shared__ double rows[2 * STRIDE];
+  __shared__ double rows[2 * kViterbiStride];
   __shared__ int8_t chunk[kViterbiChunkBytes];
   __shared__ int32_t cpath[kViterbiMaxChunk];
   __shared__ double rbest[kMaxBins / 64];
@@ -67,10 +62,8 @@ __global__ void __launch_bounds__(kMaxBins) pitch_viterbi_kernel(
   int8_t* wb = ws + base * NB;
   const double lam = (double)transition;
 
-  for (int i = j; i < 2 * STRIDE; i += nt) rows[i] = INFINITY;
-  __syncthreads();
-  double* prev = rows + R;            // delta(i) at prev[i]; prev[-R .. -1] and prev[NB .. NB + R - 1] stay +inf
-  double* cur = rows + STRIDE + R;
+  double* prev = viterbi_rows(rows, j, nt, R);
+  double* cur = prev + kViterbiStride;
   float c = 0.0f;
   if (active) {
     prev[j] = (double)cb[j];
@@ -101,7 +94,10 @@ __global__ void __launch_bounds__(kMaxBins) pitch_viterbi_kernel(
     c = cn;
   }
 
-  // path(F-1): the smallest argmin of the last row, a fixed-order reduction
+  // path(F-1): the smallest argmin of the last row, a fixed-order reduction.  wave_argmin<64>'s loop and the fold of
+  // the waves' pairs, written out: through the functions this one-off code came out one instruction longer, the
+  // backtrack's loops below moved by four bytes, and the decode measured 0.4 % slower on gfx950 (per frame, so the
+  // walk); written out, the kernel's code is what it was before the pieces were shared.
   double best = active ? prev[j] : INFINITY;
   int besti = active ? j : INT_MAX;
 #pragma unroll
@@ -146,22 +142,15 @@ __global__ void __launch_bounds__(kMaxBins) pitch_viterbi_kernel(
   }
 }
 
-template <int N>
-int salience_launch(const float* x, int64_t B, int64_t T, int hop, int frames, const PitchParams& p,
+int launch_salience(const float* x, int64_t B, int64_t T, int64_t L, int hop, int frames, const PitchParams& p,
                     const int32_t* lo, const int32_t* hi, int n_bins, float* cost, float* f0c, int32_t* lag,
                     float* f0, float* conf, int32_t* period, void* stream) {
-  hipLaunchKernelGGL(pitch_salience_kernel<N>, dim3(pitch_blocks(N, frames), (unsigned)B), dim3(kPoints<N> / 16), 0,
-                     S(stream), x, T, hop, frames, p, lo, hi, n_bins, cost, f0c, lag, f0, conf, period);
-  return launch_status();
-}
-
-int salience_dispatch(const float* x, int64_t B, int64_t T, int64_t L, int hop, int frames, const PitchParams& p,
-                      const int32_t* lo, const int32_t* hi, int n_bins, float* cost, float* f0c, int32_t* lag,
-                      float* f0, float* conf, int32_t* period, void* stream) {
-#define DDSP_CALL(N) \
-  salience_launch<N>(x, B, T, hop, frames, p, lo, hi, n_bins, cost, f0c, lag, f0, conf, period, stream)
-  DDSP_FOR_FRAME_LENGTH(L, DDSP_CALL)
-#undef DDSP_CALL
+  return for_frame_length<kPitchMinFrame>(L, [&](auto size) {
+    constexpr int N = decltype(size)::value;
+    hipLaunchKernelGGL(pitch_salience_kernel<N>, dim3(pitch_blocks(N, frames), (unsigned)B), dim3(kPoints<N> / 16), 0,
+                       S(stream), x, T, hop, frames, p, lo, hi, n_bins, cost, f0c, lag, f0, conf, period);
+    return launch_status();
+  });
 }
 
 // The decode's sizes (include/ddsp_hip.h), checked before any HIP call.
@@ -192,9 +181,9 @@ int ddsp_hip_pitch_salience(const float* x, const int32_t* lo, const int32_t* hi
   if (!x || !lo || !hi || !cost || !f0c) return DDSP_HIP_EINVAL;
   const int frames = (int)(n_samples / hop);
   if (frames == 0) return DDSP_HIP_OK;
-  const PitchParams p{(int)tau_min, (int)tau_max, sample_rate, threshold};
-  return salience_dispatch(x, batch, n_samples, frame_length, (int)hop, frames, p, lo, hi, (int)n_bins, cost, f0c,
-                           lag, f0, confidence, period, stream);
+  return launch_salience(x, batch, n_samples, frame_length, (int)hop, frames,
+                         pitch_params(tau_min, tau_max, sample_rate, threshold), lo, hi, (int)n_bins, cost, f0c, lag,
+                         f0, confidence, period, stream);
 }
 
 size_t ddsp_hip_pitch_viterbi_workspace_bytes(int64_t batch, int64_t frames, int64_t n_bins) {

@@ -5,9 +5,9 @@
 // one shared ring, instead of two launches each with a ring and a copy of the call of its own.
 //
 // grid (pitch_blocks + frame_blocks, B), kPoints<L>/16 threads.  The first pitch_blocks(L, R) workgroups of an item
-// run yin_frame<L> (one frame per transform: the longer chain, dispatched first), the remaining
-// frame_blocks(L, R) run packed_spectrum + loudness_sums (two frames per transform).  The bodies are those of
-// pitch.hip's and features.hip's kernels (analysis_bodies.h), so the bits are the separate launches'.  The role branch
+// run pitch_role<L> (one frame per transform: the longer chain, dispatched first), the remaining
+// frame_blocks(L, R) run loudness_role<L> (two frames per transform).  The roles are the ones pitch.hip's and
+// features.hip's kernels shell (analysis_bodies.h), so the bits are the separate launches'.  The role branch
 // is uniform per workgroup and there is no loop over passes.  Every workgroup copies its strided share of the call
 // into the ring; no workgroup reads what another writes (analysis_frames.h), whatever its role.  One lds_all serves
 // both roles.  (stream_analysis_mfcc.hip adds the streamed MFCC of the same frames as a third role.)
@@ -23,47 +23,30 @@ __global__ void __launch_bounds__(kPoints<N> / 16) stream_analysis_kernel(
     const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ loud,
     const uint64_t* __restrict__ counter, float* ring, int n, int len, int hs, int hop, int frames, int pblocks,
     PitchParams p, float* __restrict__ f0, float* __restrict__ conf, int32_t* __restrict__ period) {
-  constexpr int Q = N / 16, TPW = kPoints<N> / N, BINS = N / 2 + 1;
+  constexpr int TPW = kPoints<N> / N;
   __shared__ double2 lds_all[TPW * (N + N / 16)];
   __shared__ double red[8];  // the loudness's wave sums; the pitch's wsum (its first four)
   __shared__ int rint[8];
-  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;
-  double2* lds = lds_all + tr * (N + N / 16);
   const int b = blockIdx.y;
-  const StreamCall call{*counter, n, len, hs, hop, frames};
-  float* rb = ring + (int64_t)b * len;
-  const float* xb = x + (int64_t)b * n;
-  call.store(rb, xb, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  const StreamFetch fetch = open_stream_call(*counter, ring, x, n, len, hs, hop, frames, b,
+                                             blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
   if ((int)blockIdx.x < pblocks) {
-    const int j = blockIdx.x * TPW + tr;
-    yin_frame<N>(call.fetch(rb, xb), j, t, lds, red, rint, p, j < frames, (int64_t)b * frames + j, f0, conf, period);
+    pitch_role<N>(fetch, blockIdx.x, lds_all, red, rint, p, b, f0, conf, period);
     return;
   }
-  const int fa = 2 * ((blockIdx.x - pblocks) * TPW + tr);
-  packed_spectrum<N>(call.fetch(rb, xb), fa, t, lds);
-  double sa, sb;
-  loudness_sums<N>(lds, w, t, tr, red, sa, sb);
-  if (t != 0 || fa >= frames) return;
-  float* o = loud + (int64_t)b * frames + fa;
-  o[0] = (float)(sa / (double)BINS);
-  if (fa + 1 < frames) o[1] = (float)(sb / (double)BINS);
+  loudness_role<N>(fetch, blockIdx.x - pblocks, w, lds_all, red, loud, b);
 }
 
-template <int N>
-int stream_analysis_launch(const StreamArgs& a, const float* w, float* loud, const PitchParams& p, float* f0,
-                           float* conf, int32_t* period) {
-  const unsigned pb = pitch_blocks(N, a.frames);
-  hipLaunchKernelGGL(stream_analysis_kernel<N>, dim3(pb + frame_blocks(N, a.frames), (unsigned)a.B),
-                     dim3(kPoints<N> / 16), 0, S(a.stream), a.x, w, loud, a.counter, a.ring, a.n, a.len, a.hs, a.hop,
-                     a.frames, (int)pb, p, f0, conf, period);
-  return launch_status();
-}
-
-int stream_analysis_dispatch(const StreamArgs& a, int64_t L, const float* w, float* loud, const PitchParams& p,
-                             float* f0, float* conf, int32_t* period) {
-#define DDSP_CALL(N) stream_analysis_launch<N>(a, w, loud, p, f0, conf, period)
-  DDSP_FOR_FRAME_LENGTH(L, DDSP_CALL)
-#undef DDSP_CALL
+int launch_stream_analysis(const StreamArgs& a, int64_t L, const float* w, float* loud, const PitchParams& p,
+                           float* f0, float* conf, int32_t* period) {
+  return for_frame_length<kPitchMinFrame>(L, [&](auto size) {
+    constexpr int N = decltype(size)::value;
+    const unsigned pb = pitch_blocks(N, a.frames);
+    hipLaunchKernelGGL(stream_analysis_kernel<N>, dim3(pb + frame_blocks(N, a.frames), (unsigned)a.B),
+                       dim3(kPoints<N> / 16), 0, S(a.stream), a.x, w, loud, a.counter, a.ring, a.n, a.len, a.hs,
+                       a.hop, a.frames, (int)pb, p, f0, conf, period);
+    return launch_status();
+  });
 }
 
 }  // namespace
@@ -86,8 +69,8 @@ int ddsp_hip_stream_analysis(const float* x, const float* weights, float* loudne
   if (!x || !loudness_out || !f0 || !counter || !state) return DDSP_HIP_EINVAL;
   if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
   const StreamArgs a = stream_args(x, counter, state, batch, call_samples, hop, sz, stream);
-  const PitchParams p{(int)tau_min, (int)tau_max, sample_rate, threshold};
-  return stream_analysis_dispatch(a, frame_length, weights, loudness_out, p, f0, confidence, period);
+  return launch_stream_analysis(a, frame_length, weights, loudness_out,
+                                pitch_params(tau_min, tau_max, sample_rate, threshold), f0, confidence, period);
 }
 
 }  // extern "C"

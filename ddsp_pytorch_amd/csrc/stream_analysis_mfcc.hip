@@ -12,7 +12,7 @@ namespace ddsp {
 namespace {
 
 // grid (pitch_blocks + frame_blocks + 1, B), kPoints<N>/16 threads.  Per item the pitch and the loudness workgroups are
-// stream_analysis_kernel's (the same bodies, so the same bits); the item's last workgroup runs
+// stream_analysis_kernel's (pitch_role and loudness_role, so the same bits); the item's last workgroup runs
 // stream_mfcc_body<M> over the same ring with each frame's M-sample window centred in the frame's L-sample window
 // (the fetch's rel0 moved by (L - M)/2, still inside [-hs, n)), so slot j of all three features is the same stream
 // frame.  pblocks == 0: no pitch role.  kPoints<L> == kPoints<M> == 2048: one workgroup shape and one lds_all for
@@ -23,7 +23,7 @@ __global__ void __launch_bounds__(kPoints<N> / 16) stream_analysis_mfcc_kernel(
     const uint64_t* __restrict__ counter, float* ring, float* runmax, int n, int len, int hs, int hop, int frames,
     int pblocks, PitchParams p, float* __restrict__ f0, float* __restrict__ conf, int32_t* __restrict__ period,
     MfccTables m, float* __restrict__ mfcc) {
-  constexpr int Q = N / 16, TPW = kPoints<N> / N, BINS = N / 2 + 1, WAVES = kPoints<N> / 1024;
+  constexpr int TPW = kPoints<N> / N, WAVES = kPoints<N> / 1024;
   static_assert(kPoints<N> == 2048 && kPoints<M> == 2048 && (M == N || 2 * M == N), "one workgroup shape");
   __shared__ double2 lds_all[TPW * (N + N / 16)];
   __shared__ double red[8];
@@ -35,32 +35,20 @@ __global__ void __launch_bounds__(kPoints<N> / 16) stream_analysis_mfcc_kernel(
   __shared__ float s_floor;
   const int b = blockIdx.y;
   const uint64_t k = *counter;
-  const StreamCall call{k, n, len, hs, hop, frames};
-  float* rb = ring + (int64_t)b * len;
-  const float* xb = x + (int64_t)b * n;
-  call.store(rb, xb, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  const StreamFetch fetch = open_stream_call(k, ring, x, n, len, hs, hop, frames, b,
+                                             blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
   if (blockIdx.x == gridDim.x - 1) {
-    StreamFetch fetch = call.fetch(rb, xb);
-    fetch.rel0 += (N - M) / 2;
-    stream_mfcc_body<M>(fetch, k != 0, lds_all, MfccLds{sD, s_start, s_count, s_off, s_wave, s_max, &s_floor}, m,
+    StreamFetch centred = fetch;
+    centred.rel0 += (N - M) / 2;
+    stream_mfcc_body<M>(centred, k != 0, lds_all, MfccLds{sD, s_start, s_count, s_off, s_wave, s_max, &s_floor}, m,
                         runmax + b, mfcc + (int64_t)b * frames * m.n_mfcc);
     return;
   }
-  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;
-  double2* lds = lds_all + tr * (N + N / 16);
   if ((int)blockIdx.x < pblocks) {
-    const int j = blockIdx.x * TPW + tr;
-    yin_frame<N>(call.fetch(rb, xb), j, t, lds, red, rint, p, j < frames, (int64_t)b * frames + j, f0, conf, period);
+    pitch_role<N>(fetch, blockIdx.x, lds_all, red, rint, p, b, f0, conf, period);
     return;
   }
-  const int fa = 2 * ((blockIdx.x - pblocks) * TPW + tr);
-  packed_spectrum<N>(call.fetch(rb, xb), fa, t, lds);
-  double sa, sb;
-  loudness_sums<N>(lds, w, t, tr, red, sa, sb);
-  if (t != 0 || fa >= frames) return;
-  float* o = loud + (int64_t)b * frames + fa;
-  o[0] = (float)(sa / (double)BINS);
-  if (fa + 1 < frames) o[1] = (float)(sb / (double)BINS);
+  loudness_role<N>(fetch, blockIdx.x - pblocks, w, lds_all, red, loud, b);
 }
 
 struct AnalysisMfccArgs {
@@ -73,27 +61,17 @@ struct AnalysisMfccArgs {
   float *runmax, *mfcc;
 };
 
-template <int N, int M>
-int stream_analysis_mfcc_launch(const StreamArgs& a, const AnalysisMfccArgs& g) {
-  const unsigned pb = g.f0 ? pitch_blocks(N, a.frames) : 0u;
-  hipLaunchKernelGGL((stream_analysis_mfcc_kernel<N, M>), dim3(pb + frame_blocks(N, a.frames) + 1, (unsigned)a.B),
-                     dim3(kPoints<N> / 16), 0, S(a.stream), a.x, g.w, g.loud, a.counter, a.ring, g.runmax, a.n, a.len,
-                     a.hs, a.hop, a.frames, (int)pb, g.p, g.f0, g.conf, g.period, g.m, g.mfcc);
-  return launch_status();
-}
-
-int stream_analysis_mfcc_dispatch(const StreamArgs& a, int64_t L, bool half, const AnalysisMfccArgs& g) {
-#define DDSP_CALL(N) \
-  (half ? stream_analysis_mfcc_launch<N, N / 2>(a, g) : stream_analysis_mfcc_launch<N, N>(a, g))
-  switch (L) {
-    case 64: return DDSP_CALL(64);
-    case 128: return DDSP_CALL(128);
-    case 256: return DDSP_CALL(256);
-    case 512: return DDSP_CALL(512);
-    case 1024: return DDSP_CALL(1024);
-    default: return DDSP_CALL(2048);
-  }
-#undef DDSP_CALL
+// half: the MFCC's window is L / 2 samples, else L
+int launch_stream_analysis_mfcc(const StreamArgs& a, int64_t L, bool half, const AnalysisMfccArgs& g) {
+  return for_frame_length<kPitchMinFrame, 2048>(L, [&](auto size) {
+    constexpr int N = decltype(size)::value;
+    const auto kernel = half ? stream_analysis_mfcc_kernel<N, N / 2> : stream_analysis_mfcc_kernel<N, N>;
+    const unsigned pb = g.f0 ? pitch_blocks(N, a.frames) : 0u;
+    hipLaunchKernelGGL(kernel, dim3(pb + frame_blocks(N, a.frames) + 1, (unsigned)a.B), dim3(kPoints<N> / 16), 0,
+                       S(a.stream), a.x, g.w, g.loud, a.counter, a.ring, g.runmax, a.n, a.len, a.hs, a.hop, a.frames,
+                       (int)pb, g.p, g.f0, g.conf, g.period, g.m, g.mfcc);
+    return launch_status();
+  });
 }
 
 }  // namespace
@@ -130,7 +108,7 @@ int ddsp_hip_stream_analysis_mfcc(const float* x, const float* weights, float* l
   const StreamArgs a = stream_args(x, counter, state, batch, call_samples, hop, sz, stream);
   const AnalysisMfccArgs g{weights,
                            loudness_out,
-                           PitchParams{(int)tau_min, (int)tau_max, sample_rate, threshold},
+                           pitch_params(tau_min, tau_max, sample_rate, threshold),
                            f0,
                            confidence,
                            period,
@@ -138,7 +116,7 @@ int ddsp_hip_stream_analysis_mfcc(const float* x, const float* weights, float* l
                                       (int)n_mfcc, top_db},
                            a.ring + (size_t)batch * (size_t)sz.len,
                            mfcc_out};
-  return stream_analysis_mfcc_dispatch(a, frame_length, mfcc_n_fft != frame_length, g);
+  return launch_stream_analysis_mfcc(a, frame_length, mfcc_n_fft != frame_length, g);
 }
 
 }  // extern "C"

@@ -2,11 +2,12 @@
 // with a fixed-lag decision (one launch).  include/ddsp_hip.h ("pitch_viterbi_stream") holds the definition;
 // tests/stream_viterbi_ref.py restates it in numpy.
 //
-// Salience: stream_pitch_kernel's grid, workgroup and ring copy; the frame's d' by yin_dprime over the call's
-// StreamFetch, then salience_bins (analysis_bodies.h, shared with pitch_viterbi.hip).  With the raw outputs asked
-// for, yin_pick runs on the same d': ddsp_hip_stream_pitch's bits.
+// Salience: stream_pitch_kernel's grid, workgroup and ring copy around salience_role (analysis_bodies.h, the role
+// pitch_viterbi.hip's kernel shells) over the call's StreamFetch.  With the raw outputs asked for, yin_pick runs on
+// the same d': ddsp_hip_stream_pitch's bits.
 //
-// Decode: one workgroup per item, one thread per bin, pitch_viterbi_kernel's recursion: delta in LDS as two padded
+// Decode: one workgroup per item, one thread per bin, pitch_viterbi_kernel's recursion out of the same pieces
+// (viterbi_rows and wave_argmin shared; the neighbour loop and the fold written out as there): delta in LDS as two padded
 // fp64 rows written in turn, one barrier per frame, the next frame's cost loaded ahead of it.  The row comes from
 // the state's delta[k & 1] and goes to delta[(k + 1) & 1]; the call's cost and f0c go into the ring before the
 // recursion starts (independent loads and stores), so the frame loop stores back-offsets alone.  Each frame's argmin
@@ -37,23 +38,14 @@ __global__ void __launch_bounds__(kPoints<N> / 16) stream_pitch_salience_kernel(
     int frames, PitchParams p, const int32_t* __restrict__ lo, const int32_t* __restrict__ hi, int n_bins,
     float* __restrict__ cost, float* __restrict__ f0c, int32_t* __restrict__ lag, float* __restrict__ f0,
     float* __restrict__ conf, int32_t* __restrict__ period) {
-  constexpr int Q = N / 16, TPW = kPoints<N> / N;
+  constexpr int TPW = kPoints<N> / N;
   __shared__ double2 lds_all[TPW * (N + N / 16)];
   __shared__ double wsum[4];
   __shared__ int rint[8];
-  const int tr = threadIdx.x / Q, t = threadIdx.x - tr * Q;
   const int b = blockIdx.y;
-  const int j = blockIdx.x * TPW + tr;
-  const StreamCall call{*counter, n, len, hs, hop, frames};
-  float* rb = ring + (int64_t)b * len;
-  const float* xb = x + (int64_t)b * n;
-  call.store(rb, xb, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
-  double2* lds = lds_all + tr * (N + N / 16);
-  double dn[9];
-  yin_dprime<N>(call.fetch(rb, xb), j, t, lds, wsum, p, dn);
-  const int64_t o = (int64_t)b * frames + j;
-  if (j < frames) salience_bins<N>(yin_dp<N>(lds), t, p, lo, hi, n_bins, o * n_bins, cost, f0c, lag);
-  if (f0) yin_pick<N>(dn, t, lds, wsum, rint, p, j < frames, o, f0, conf, period);  // (uniform: its barrier)
+  const StreamFetch fetch = open_stream_call(*counter, ring, x, n, len, hs, hop, frames, b,
+                                             blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  salience_role<N>(fetch, blockIdx.x, lds_all, wsum, rint, p, b, lo, hi, n_bins, cost, f0c, lag, f0, conf, period);
 }
 
 // The decode's state, per item: double delta[2][NB], then the ring of P = D + R frames as float f0c[P][NB],
@@ -73,8 +65,8 @@ __global__ void __launch_bounds__(kMaxBins) stream_pitch_viterbi_kernel(
     const float* __restrict__ cost, const float* __restrict__ f0c, const uint64_t* __restrict__ counter,
     unsigned char* state, size_t item_bytes, float* __restrict__ f0, float* __restrict__ conf,
     int32_t* __restrict__ path, int R, int NB, int J, int D, float transition) {
-  constexpr int STRIDE = kMaxBins + 2 * kMaxJump, WAVES = kMaxBins / 64;
-  __shared__ double rows[2 * STRIDE];
+  constexpr int WAVES = kMaxBins / 64;
+  __shared__ double rows[2 * kViterbiStride];
   __shared__ double rbest[kStreamMaxFrames * WAVES];
   __shared__ int rbesti[kStreamMaxFrames * WAVES];
   const int j = threadIdx.x, nt = blockDim.x;
@@ -102,10 +94,8 @@ __global__ void __launch_bounds__(kMaxBins) stream_pitch_viterbi_kernel(
       rf0c[o] = fb[jj * NB + j];
     }
   }
-  for (int i = j; i < 2 * STRIDE; i += nt) rows[i] = INFINITY;
-  __syncthreads();
-  double* prev = rows + J;  // delta(i) at prev[i]; prev[-J .. -1] and prev[NB .. NB + J - 1] stay +inf
-  double* cur = rows + STRIDE + J;
+  double* prev = viterbi_rows(rows, j, nt, J);
+  double* cur = prev + kViterbiStride;
   float c = 0.0f;
   if (active) {
     c = cb[j];
@@ -137,12 +127,7 @@ __global__ void __launch_bounds__(kMaxBins) stream_pitch_viterbi_kernel(
       rbp[((s0 + jj) % P) * NB + j] = (int8_t)bk;
     }
     // the frame's smallest argmin, this wave's share: a fixed-order reduction of the values just computed
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double ov = __shfl_down(v, o, 64);
-      const int oi = __shfl_down(vi, o, 64);
-      take_min(v, vi, ov, oi);
-    }
+    wave_argmin<64>(v, vi);
     if ((j & 63) == 0) {
       rbest[jj * WAVES + (j >> 6)] = v;
       rbesti[jj * WAVES + (j >> 6)] = vi;
@@ -176,22 +161,16 @@ __global__ void __launch_bounds__(kMaxBins) stream_pitch_viterbi_kernel(
   }
 }
 
-template <int N>
-int stream_salience_launch(const StreamArgs& a, const PitchParams& p, const int32_t* lo, const int32_t* hi,
-                           int n_bins, float* cost, float* f0c, int32_t* lag, float* f0, float* conf,
-                           int32_t* period) {
-  hipLaunchKernelGGL(stream_pitch_salience_kernel<N>, dim3(pitch_blocks(N, a.frames), (unsigned)a.B),
-                     dim3(kPoints<N> / 16), 0, S(a.stream), a.x, a.counter, a.ring, a.n, a.len, a.hs, a.hop, a.frames,
-                     p, lo, hi, n_bins, cost, f0c, lag, f0, conf, period);
-  return launch_status();
-}
-
-int stream_salience_dispatch(const StreamArgs& a, int64_t L, const PitchParams& p, const int32_t* lo,
-                             const int32_t* hi, int n_bins, float* cost, float* f0c, int32_t* lag, float* f0,
-                             float* conf, int32_t* period) {
-#define DDSP_CALL(N) stream_salience_launch<N>(a, p, lo, hi, n_bins, cost, f0c, lag, f0, conf, period)
-  DDSP_FOR_FRAME_LENGTH(L, DDSP_CALL)
-#undef DDSP_CALL
+int launch_stream_salience(const StreamArgs& a, int64_t L, const PitchParams& p, const int32_t* lo,
+                           const int32_t* hi, int n_bins, float* cost, float* f0c, int32_t* lag, float* f0,
+                           float* conf, int32_t* period) {
+  return for_frame_length<kPitchMinFrame>(L, [&](auto size) {
+    constexpr int N = decltype(size)::value;
+    hipLaunchKernelGGL(stream_pitch_salience_kernel<N>, dim3(pitch_blocks(N, a.frames), (unsigned)a.B),
+                       dim3(kPoints<N> / 16), 0, S(a.stream), a.x, a.counter, a.ring, a.n, a.len, a.hs, a.hop,
+                       a.frames, p, lo, hi, n_bins, cost, f0c, lag, f0, conf, period);
+    return launch_status();
+  });
 }
 
 // The carried decode's sizes (include/ddsp_hip.h), checked before any HIP call.
@@ -227,8 +206,8 @@ int ddsp_hip_stream_pitch_salience(const float* x, const int32_t* lo, const int3
   if (!x || !lo || !hi || !cost || !f0c || !counter || !state) return DDSP_HIP_EINVAL;
   if (state_bytes < stream_features_bytes(batch, sz)) return DDSP_HIP_EWORKSPACE;
   const StreamArgs a = stream_args(x, counter, state, batch, call_samples, hop, sz, stream);
-  const PitchParams p{(int)tau_min, (int)tau_max, sample_rate, threshold};
-  return stream_salience_dispatch(a, frame_length, p, lo, hi, (int)n_bins, cost, f0c, lag, f0, confidence, period);
+  return launch_stream_salience(a, frame_length, pitch_params(tau_min, tau_max, sample_rate, threshold), lo, hi,
+                                (int)n_bins, cost, f0c, lag, f0, confidence, period);
 }
 
 size_t ddsp_hip_stream_viterbi_state_bytes(int64_t batch, int64_t frames_per_call, int64_t n_bins, int64_t lag) {

@@ -391,63 +391,136 @@ __global__ void __launch_bounds__(kNT) upols_mac_ring_kernel(const float2* __res
     if (Dir::in_signal(b0 + d, nb)) Yp[(int64_t)(b0 + d) * kN] = Dir::output(acc[d], f);
 }
 
+// 16-byte access at byte offset voff of a descriptor over two consecutive spectrum rows (`bytes`
+// records: 2, 1 or 0 rows; what lies past them reads as zero and is not stored)
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+template <int AUX>
+__device__ __forceinline__ i32x4 row_pair_load(const float2* row, int bytes, int voff) {
+  const __amdgpu_buffer_rsrc_t r =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(row), (short)0, bytes, kBufferWord3);
+  return __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, AUX);
+}
+__device__ __forceinline__ void row_pair_store(float2* row, int bytes, int voff, i32x4 v) {
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(row, (short)0, bytes, kBufferWord3);
+  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, 0, 0);
+}
+// v_permlane32_swap_b32: lanes 32-63 of a change places with lanes 0-31 of b
+__device__ __forceinline__ void half_swap(int& a, int& b) {
+  const auto r = __builtin_amdgcn_permlane32_swap((unsigned)a, (unsigned)b, false, false);
+  a = (int)r[0];
+  b = (int)r[1];
+}
+// Two rows (m0, m0 + 1) of two adjacent bins between their memory image and their owners.  In memory
+// order (v of a 16-byte access) lanes 0-31 hold bins f0 + 2l, f0 + 2l + 1 of row m0 and lanes 32-63 the
+// same bins of row m0 + 1; owned, lane l holds bin f0 + 2l of both rows and lane l + 32 bin f0 + 2l + 1.
+// The exchange is its own inverse.
+__device__ __forceinline__ void rows_to_bins(i32x4 v, float2& a, float2& b) {
+  int ax = v.x, ay = v.y, bx = v.z, by = v.w;
+  half_swap(ax, bx);
+  half_swap(ay, by);
+  a = make_float2(__int_as_float(ax), __int_as_float(ay));
+  b = make_float2(__int_as_float(bx), __int_as_float(by));
+}
+__device__ __forceinline__ i32x4 bins_to_rows(float2 a, float2 b) {
+  int ax = __float_as_int(a.x), ay = __float_as_int(a.y), bx = __float_as_int(b.x), by = __float_as_int(b.y);
+  half_swap(ax, bx);
+  half_swap(ay, by);
+  return (i32x4){ax, ay, bx, by};
+}
+
 // The same sums for a whole pair row in one thread (nb == NBK, Q <= NQ): every operand block and G_q of
 // the bin is loaded once and stays in registers (the ring kernel's two 25-block chunks re-read ~1.5x of
 // them: 122 vs 104 MB of Z at config 2), and the outputs stream from the end the window starts at (the
-// forward from block 0 up, the adjoint from block NBK - 1 down) — step s issues the loads of step s + PF
-// (the next operand block, G_{s+PF}), then forms its output block from the s + 1 blocks and kernel
-// windows already in registers and stores it, so loads, products and stores overlap inside every wave
-// (166 VGPRs; grid N/256 x npairs: one round at 2 waves per SIMD).  Same-box A/Bs at config 2, forward
-// (profiles/r05_ab_mac_vjp.log): 24.5-24.8 us against 32.1-32.4 us for the ring kernel on boxes where the
-// ring runs 32 us (step -3.8 / -6.4 us), equal (25.0 vs 24.9-25.0 us) where the ring runs 25 us; adjoint:
-// 23.1-23.2 us against 29.8-29.9 for the ring kernel (tools/ab_prof.sh reverb_bwd).  The ring kernel
-// serves the other shapes.
+// forward from block 0 up, the adjoint from block NBK - 1 down): a step forms its output block from the
+// blocks and kernel windows already in registers and stores it while the loads of later steps are in
+// flight, so loads, products and stores overlap inside every wave (grid N/256 x npairs).  Same-box A/Bs
+// at config 2 of the 8-byte form of this kernel (one bin per lane in lane order, one block per step,
+// profiles/r05_ab_mac_vjp.log), forward: 24.5-24.8 us against 32.1-32.4 us for the ring kernel on boxes
+// where the ring runs 32 us (step -3.8 / -6.4 us), equal (25.0 vs 24.9-25.0 us) where the ring runs 25 us;
+// adjoint: 23.1-23.2 us against 29.8-29.9 (tools/ab_prof.sh reverb_bwd).  The ring kernel serves the
+// other shapes.
+//
+// The spectra move 16 bytes per lane: 38 buffer_load_dwordx4 + 25 buffer_store_dwordx4 per thread.  As
+// 75 + 50 dwordx2 the same sums in the same order ran 24.4-24.9 us in the bench step against 21.6-22.0,
+// forward, and 20.9-22.6 against 19.3-19.7, adjoint (the same bytes in half the memory
+// instructions; profiles/mac_wide_*.log).  A wave owns 64 consecutive bins f0 .. f0 + 63 of its
+// pair; lane l < 32 owns bin f0 + 2l and lane l + 32 bin f0 + 2l + 1 (a bin's sums depend on nothing but
+// the bin, so which lane owns it is free).  Rows go two at a time, (m0, m0 + 1) with m0 even, in one
+// access whose descriptor spans both: lanes 0-31 move bins f0 + 2l, f0 + 2l + 1 of row m0, lanes 32-63
+// the same bins of row m0 + 1 (their offset is one row further), and two v_permlane32_swap per access
+// trade the low lanes' second bin for the high lanes' first.  So the steps go in pairs of output blocks,
+// the forward's rows (2t, 2t + 1) ascending, the adjoint's (NBK - 2 - 2t, NBK - 1 - 2t) descending; step
+// pair t issues the loads of pair t + PF (two Z rows, G_{2(t+PF)} and G_{2(t+PF)+1}) and swaps its own
+// pair's rows where it first uses them (swapped where they are loaded, the wait sits behind the load and
+// the prefetch is gone).  Each output block's sum is the 8-byte form's, term for term (q ascending, even
+// q into acc, odd q into acc2, one final add), so Y is the same bits.  G pairs at or past Q have
+// descriptors over the rows that exist (1 or 0): the rest reads as zero without a select, and no cache
+// row past Q is read.  224-226 VGPRs: two waves per SIMD, which config 2's grid (2048 waves) fills in
+// one round.  The time does not move with PF (1, 2, 3: 20.6-21.9 us in tools/kernel_probe.py; 4:
+// 22.0-22.4 us).
 template <class Dir, int NBK, int NQ, int PF>
 __global__ void __launch_bounds__(kNT) upols_mac_stream_kernel(const float2* __restrict__ X,
                                                                const float2* __restrict__ Hs,
                                                                int64_t h_pair_stride, int nb, int Q,
                                                                float2* __restrict__ Y) {
+  static_assert(NBK % 2 == 0, "rows go in pairs");
   constexpr int kRow = kN * (int)sizeof(float2);
   constexpr int kStep = Dir::kStep;
+  constexpr int NP = NBK / 2, NG = (NQ + 1) / 2;
   constexpr auto block = [](int s) { return kStep < 0 ? s : NBK - 1 - s; };  // output block of step s
-  const int f = blockIdx.x * kNT + threadIdx.x;
+  constexpr auto even_row = [](int t) { return kStep < 0 ? 2 * t : NBK - 2 - 2 * t; };  // of step pair t
+  const int lane = threadIdx.x & 63, hi = lane >> 5;
+  const int f0 = blockIdx.x * kNT + (threadIdx.x & ~63);
+  const int f = f0 + 2 * (lane & 31) + hi;  // the bin this lane owns
+  const int voff = (f0 + 2 * (lane & 31)) * (int)sizeof(float2) + hi * kRow;
   const int pair = blockIdx.y;
   const float2* Xrow = X + (int64_t)pair * nb * kN;
   const float2* Hrow = Dir::kernel_rows(Hs, pair, h_pair_stride);
-  const int voff = f * (int)sizeof(float2);
-  float2 z[NBK], g[NQ];
-  auto zload = [&](int m) { z[m] = row_load<Dir::kZAux>(Xrow + (int64_t)m * kN, kRow, voff); };
-  auto gload = [&](int q) { g[q] = row_load<Dir::kGAux>(Hrow + (int64_t)min(q, Q - 1) * kN, q < Q ? kRow : 0, voff); };
+  float2* Yrow = Y + (int64_t)pair * nb * kN;
+  i32x4 zp[NP], gp[NG];
+  float2 z[NBK], g[2 * NG];
+  auto zload = [&](int t) { zp[t] = row_pair_load<Dir::kZAux>(Xrow + (int64_t)even_row(t) * kN, 2 * kRow, voff); };
+  auto gload = [&](int u) {
+    gp[u] = row_pair_load<Dir::kGAux>(Hrow + (int64_t)min(2 * u, Q - 1) * kN, min(max(Q - 2 * u, 0), 2) * kRow, voff);
+  };
 #pragma unroll
-  for (int s = 0; s < PF; ++s) {
-    if (s < NQ) gload(s);
-    zload(block(s));
+  for (int t = 0; t < PF; ++t) {
+    if (t < NG) gload(t);
+    zload(t);
   }
-  float2* Yp = Y + (int64_t)pair * nb * kN + f;
 #pragma unroll
-  for (int s = 0; s < NBK; ++s) {
-    const int b = block(s);
-    if (s + PF < NQ) gload(s + PF);
-    if (s + PF < NBK) zload(block(s + PF));
+  for (int t = 0; t < NP; ++t) {
+    const int m0 = even_row(t);
+    if (t + PF < NG) gload(t + PF);
+    if (t + PF < NP) zload(t + PF);
     __builtin_amdgcn_sched_barrier(0);
-    v2f acc = {0.f, 0.f}, acc2 = {0.f, 0.f};
+    rows_to_bins(zp[t], z[m0], z[m0 + 1]);
+    if (t < NG) rows_to_bins(gp[t], g[2 * t], g[2 * t + 1]);
+    float2 out[2];
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      if (q <= s) {
-        v2f hb, hr;
-        Dir::operand(g[q], hb, hr);
-        if (q & 1) cmac(acc2, z[b + kStep * q], hb, hr);
-        else cmac(acc, z[b + kStep * q], hb, hr);
+    for (int e = 0; e < 2; ++e) {
+      const int s = 2 * t + e, b = block(s);
+      v2f acc = {0.f, 0.f}, acc2 = {0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        if (q <= s) {
+          v2f hb, hr;
+          Dir::operand(g[q], hb, hr);
+          if (q & 1) cmac(acc2, z[b + kStep * q], hb, hr);
+          else cmac(acc, z[b + kStep * q], hb, hr);
+        }
       }
+      out[b - m0] = Dir::output((v2f){acc.x + acc2.x, acc.y + acc2.y}, f);
     }
-    Yp[(int64_t)b * kN] = Dir::output((v2f){acc.x + acc2.x, acc.y + acc2.y}, f);
+    row_pair_store(Yrow + (int64_t)m0 * kN, 2 * kRow, voff, bins_to_rows(out[0], out[1]));
     __builtin_amdgcn_sched_barrier(0);
   }
 }
 
 // The whole-row MAC form (upols_mac_stream_kernel, both directions) for the row length it
-// is built for: 50 blocks (config 2's 102400 samples), up to 25 kernel windows (a 1 s IR at 48 kHz)
-constexpr int kStreamNB = 50, kStreamNQ = 25, kStreamPF = 4;
+// is built for: 50 blocks (config 2's 102400 samples), up to 25 kernel windows (a 1 s IR at 48 kHz);
+// loads issued 2 step pairs (4 blocks) ahead
+constexpr int kStreamNB = 50, kStreamNQ = 25, kStreamPF = 2;
 
 // y[row][bP + n] = IFFT(Y_b)[P + n]; grid (nb, npairs)
 __global__ void __launch_bounds__(kNT) upols_inverse_kernel(const float2* __restrict__ Y, int nb,

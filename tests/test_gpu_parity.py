@@ -194,13 +194,18 @@ def test_noise_device_rng(dd):
 def test_fft_convolve_large(dd):
     rng = np.random.default_rng(5)
     s = rng.standard_normal((3, 9000)).astype(np.float32)
-    k = (rng.standard_normal((1, 9000)) * np.exp(-np.arange(9000) / 500.0)).astype(np.float32)
-    ref = no.fft_convolve(s, k)
+    k = (rng.standard_normal((3, 9000)) * np.exp(-np.arange(9000) / 500.0)).astype(np.float32)
+    ref = no.fft_convolve(s, k[:1])
+    # a kernel of its own per row
+    ref2 = np.concatenate([no.fft_convolve(s[r:r + 1], k[r:r + 1]) for r in range(3)])
     with torch.no_grad():
-        out = C(dd.core.fft_convolve(G(s), G(k)))
-        out2 = C(dd.core.fft_convolve(G(s), G(np.repeat(k, 3, 0))))
+        out = C(dd.core.fft_convolve(G(s), G(k[:1])))
+        out2 = C(dd.core.fft_convolve(G(s), G(k)))
     scale = np.sqrt(np.mean(ref.astype(np.float64) ** 2))
-    assert rms(out, ref) < 1e-6 * scale and rms(out2, ref) < 1e-6 * scale
+    assert rms(out, ref) < 1e-6 * scale
+    for r in range(3):
+        scale_r = np.sqrt(np.mean(ref2[r].astype(np.float64) ** 2))
+        assert rms(out2[r], ref2[r]) < 1e-6 * scale_r, r
 
 
 # ------------------------------------------------------------------ reverb
@@ -510,7 +515,9 @@ def test_noise_params_golden(dd):
 
 @pytest.mark.parametrize("nb_blocks,L", [(3, 300), (50, 48000), (50, 30000), (100, 48000), (50, 96000), (120, 250000)])
 def test_reverb_partitioned_shapes(dd, nb_blocks, L):
-    """UPOLS (LDS-tiled MAC and the global-memory MAC for very long IRs) vs fp64 convolution."""
+    """UPOLS vs fp64 convolution: 50 blocks with L = 48000 and 30000 (at most 25 kernel windows) run the whole-row
+    MAC (upols_mac_stream_kernel), every other shape the register-ring MAC (upols_mac_ring_kernel) in 1, 2, 4 and
+    5 chunks of 25 blocks.  Per block, with kernels that do not decay: tests/test_gpu_reverb_shapes.py."""
     T = nb_blocks * 2048 - 17
     rng = np.random.default_rng(L + T)
     x = (rng.standard_normal((3, T, 1)) * 0.3).astype(np.float32)

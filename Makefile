@@ -12,7 +12,7 @@ SRC := ddsp_pytorch_amd/csrc/synth.hip ddsp_pytorch_amd/csrc/noise.hip ddsp_pyto
        ddsp_pytorch_amd/csrc/stream_pitch_viterbi.hip
 HDR := include/ddsp_hip.h ddsp_pytorch_amd/csrc/common.h ddsp_pytorch_amd/csrc/upols.h ddsp_pytorch_amd/csrc/fft_radix.h \
        ddsp_pytorch_amd/csrc/noise_dsp.h ddsp_pytorch_amd/csrc/stream_state.h ddsp_pytorch_amd/csrc/stft_frames.h \
-       ddsp_pytorch_amd/csrc/fft_radix_f64.h ddsp_pytorch_amd/csrc/bf16x3.h ddsp_pytorch_amd/csrc/impulse.h \
+       ddsp_pytorch_amd/csrc/bf16x3.h ddsp_pytorch_amd/csrc/impulse.h \
        ddsp_pytorch_amd/csrc/analysis_frames.h ddsp_pytorch_amd/csrc/analysis_bodies.h
 LIB := ddsp_pytorch_amd/lib/libddsp_hip.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Iinclude -Ibuild -Wall -Wno-unused-result
@@ -39,6 +39,7 @@ build/twiddle4096_f64.inc: tools/gen_twiddles.py
 	@mkdir -p build
 	python3 tools/gen_twiddles.py 4096 f64 > $@
 
+# the fp64 table comes in through analysis_frames.h alone; the fp32 one through fft_radix.h and noise_dsp.h
 build/features.o build/pitch.o build/pitch_viterbi.o build/stream_pitch_viterbi.o build/stream_analysis.o build/stream_analysis_mfcc.o: build/twiddle4096_f64.inc
 
 build/upols.o build/noise.o build/synth_frame.o build/backward.o build/stft.o build/stream_reverb.o build/features.o build/pitch.o build/pitch_viterbi.o build/stream_pitch_viterbi.o build/stream_analysis.o build/stream_analysis_mfcc.o: build/twiddle4096.inc

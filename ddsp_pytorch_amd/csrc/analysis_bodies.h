@@ -197,7 +197,7 @@ __device__ __forceinline__ void yin_dprime(const Fetch& fetch, int f, int t, dou
     const double yr = (double)fetch(f, t + Q * r);
     v[r] = make_double2(r < 8 ? yr : 0.0, yr);
   }
-  fft_n_f64<N>(v, lds, t);
+  fft_n<N, false>(v, lds, t);
   __syncthreads();
 #pragma unroll
   for (int r = 0; r < 16; ++r) lds[lds_idx(t + Q * r)] = v[r];
@@ -209,7 +209,7 @@ __device__ __forceinline__ void yin_dprime(const Fetch& fetch, int f, int t, dou
     packed_split(v[r], lds[lds_idx((N - k) & (N - 1))], a, b);
     v[r] = make_double2(fma(a.x, b.x, a.y * b.y), -fma(a.x, b.y, -(a.y * b.x)));  // conj(conj(A) Y)
   }
-  fft_n_f64<N>(v, lds, t);  // (its entry barrier: Z is read)
+  fft_n<N, false>(v, lds, t);  // (its entry barrier: Z is read)
   double rc[9];             // r(tau) for this thread's lags tau = t + Q r (r <= 8: tau <= W)
 #pragma unroll
   for (int r = 0; r < 9; ++r) rc[r] = v[r].x * (1.0 / N);

@@ -1,21 +1,31 @@
 // What the analysis kernels share (features.hip: loudness, MFCC; pitch.hip: YIN f0): where a frame's samples come
 // from, offline (reflect padding) and per call of a stream (the carried ring), the call arithmetic of a stream and its
 // opening (open_stream_call), how a workgroup's threads split over its transforms, the identities
-// by which two real sequences ride one complex fp64 transform, and the launchers' dispatch on the transform size
-// (for_frame_length).  Written once, so that the features cannot disagree about a frame.  (analysis_bodies.h holds
-// what is computed per frame: the workgroup roles.)
+// by which two real sequences ride one complex fp64 transform, and that transform's twiddle table.  Written once, so
+// that the features cannot disagree about a frame.  (analysis_bodies.h holds what is computed per frame: the
+// workgroup roles.)
+//
+// Why fft_n runs on double2 here ("Why the transform is fp64"): the features take the LOG of single bins,
+// so a bin near a spectral zero multiplies the transform's absolute error by 1/|X|, and reflect padding makes such
+// bins common.  In fp64 the transform's error vanishes beside the fp32 input's; MI355X issues fp64 FMAs at the rate
+// of unpacked fp32 ones, so the cost is LDS traffic (16-byte elements) and registers, not arithmetic.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "common.h"
-#include "fft_radix_f64.h"
+#include "fft_radix.h"
 #include "stft_frames.h"
+#include "twiddle4096_f64.inc"
 
 namespace ddsp {
 namespace {
+
+// W_4096^m in fp64 (tools/gen_twiddles.py 4096 f64), each twiddle read from the table
+template <>
+struct TwiddleTable<double2> {
+  static __device__ __forceinline__ const double2* data() { return reinterpret_cast<const double2*>(kTwiddle4096D); }
+};
 
 template <int N>
 constexpr int kPoints = N == 4096 ? 4096 : 2048;  // points per workgroup; threads = points / 16
@@ -72,7 +82,7 @@ __device__ __forceinline__ void packed_spectrum(const Fetch& fetch, int fa, int 
     const double b = (double)fetch(fa + 1, m) * w;
     v[r] = make_double2(a, b);
   }
-  fft_n_f64<N, false>(v, lds, t);  // lds untouched so far
+  fft_n<N, false, false>(v, lds, t);  // lds untouched so far
   __syncthreads();
 #pragma unroll
   for (int r = 0; r < 16; ++r) lds[lds_idx(t + Q * r)] = v[r];
@@ -173,17 +183,6 @@ inline StreamArgs stream_args(const float* x, const uint64_t* counter, void* sta
                               const StreamSizes& sz, void* stream) {
   return {x, counter, reinterpret_cast<float*>(state), B, (int)n, (int)sz.len, (int)sz.hs, (int)hop, (int)sz.frames,
           stream};
-}
-
-// The launchers' one dispatch on the transform size: f(std::integral_constant<int, L>{}) for a power of two L in
-// [N, MAX), f(<MAX>) for anything else (the entry points have checked L against their envelopes).
-template <int N, int MAX = 4096, class F>
-inline int for_frame_length(int64_t L, const F& f) {
-  if constexpr (N < MAX) {
-    return L == N ? f(std::integral_constant<int, N>{}) : for_frame_length<2 * N, MAX>(L, f);
-  } else {
-    return f(std::integral_constant<int, MAX>{});
-  }
 }
 
 }  // namespace

@@ -7,7 +7,7 @@
 //
 // Both use librosa.stft's frames (center=True, pad_mode='reflect', periodic Hann(n_fft), an UNNORMALISED
 // FFT): stft_frames.h's reflect indexing, two real frames per LDS-resident complex FFT, split by
-// Z[k] +- conj(Z[N-k]) as in stft.hip — with the transform in fp64 (fft_radix_f64.h says why: the log of a
+// Z[k] +- conj(Z[N-k]) as in stft.hip — with the transform in fp64 (analysis_frames.h says why: the log of a
 // single bin near a spectral zero multiplies the transform's absolute error by 1/|X|).  No spectrogram
 // reaches HBM: the loudness kernel reduces a frame's bins in its epilogue; the MFCC's first launch overwrites
 // the spectrum in LDS with both frames' power (P_a[k], P_b[k]) and takes the mel rows' short dot products out

@@ -139,24 +139,15 @@ __global__ void stft_overlap_add_kernel(const float* __restrict__ dF, int64_t T,
   }
 }
 
-template <int N>
-int stft_mag_launch(const float* x, int64_t B, int64_t T, int hop, int frames, float scale, float* M,
-                    void* stream) {
-  constexpr int TPW = 4096 / N;
-  const unsigned gx = (unsigned)((frames + 2 * TPW - 1) / (2 * TPW));
-  hipLaunchKernelGGL(stft_mag_kernel<N>, dim3(gx, (unsigned)B), dim3(256), 0, S(stream), x, T, hop, frames, scale,
-                     M);
-  return launch_status();
+// The grid of the three frame-pair kernels: a workgroup takes TPW = 4096/n_fft transforms of two frames each, so
+// ceil(frames / (2 TPW)) workgroups along x for each of the B rows along y.
+int64_t frame_pair_blocks(int64_t n_fft, int64_t frames) {
+  const int64_t tpw = 4096 / n_fft;
+  return (frames + 2 * tpw - 1) / (2 * tpw);
 }
 
-template <int N>
-int stft_bwd_launch(const float* x, int64_t B, int64_t T, int hop, int frames, float scale, const float* gM,
-                    float* dF, void* stream) {
-  constexpr int TPW = 4096 / N;
-  const unsigned gx = (unsigned)((frames + 2 * TPW - 1) / (2 * TPW));
-  hipLaunchKernelGGL(stft_mag_backward_kernel<N>, dim3(gx, (unsigned)B), dim3(256), 0, S(stream), x, T, hop,
-                     frames, scale, gM, dF);
-  return launch_status();
+dim3 frame_pair_grid(int64_t n_fft, int64_t frames, int64_t B) {
+  return dim3((unsigned)frame_pair_blocks(n_fft, frames), (unsigned)B);
 }
 
 int check_stft(int64_t B, int64_t T, int64_t n_fft, int64_t hop) {
@@ -299,19 +290,12 @@ __global__ void spectral_loss_finish_kernel(const double* __restrict__ partials,
   if (threadIdx.x == 0) loss[0] = (float)acc;
 }
 
-template <int N>
-int spectral_loss_launch(const float* xt, const float* xr, int64_t B, int64_t T, int hop, int frames,
-                         float scale, float inv_count, bool grad, double* partials, float* dF, void* stream) {
-  constexpr int TPW = 4096 / N;
-  const unsigned gx = (unsigned)((frames + 2 * TPW - 1) / (2 * TPW));
-  hipLaunchKernelGGL(spectral_loss_kernel<N>, dim3(gx, (unsigned)B), dim3(256), 0, S(stream), xt, xr, T, hop, frames,
-                     scale, inv_count, (int)grad, partials, dF);
-  return launch_status();
-}
+int64_t loss_blocks(int64_t n_fft, int64_t frames, int64_t B) { return frame_pair_blocks(n_fft, frames) * B; }
 
-int64_t loss_blocks(int64_t n_fft, int64_t frames, int64_t B) {
-  const int64_t tpw = 4096 / n_fft;
-  return ((frames + 2 * tpw - 1) / (2 * tpw)) * B;
+// the loss workspace's head: partials (2 doubles per block, all scales) | block offsets | 1/count, padded to 256
+size_t loss_head_bytes(size_t blocks, int n_scales) {
+  return ((2 * sizeof(double) * blocks + sizeof(int64_t) * (n_scales + 1) + sizeof(double) * n_scales) + 255) &
+         ~(size_t)255;
 }
 
 }  // namespace
@@ -331,17 +315,11 @@ int ddsp_hip_stft_magnitude(const float* x, float* magnitudes, int64_t batch, in
   if (!x || !magnitudes) return DDSP_HIP_EINVAL;
   const int frames = (int)(n_samples / hop + 1);
   const float scale = (float)(1.0 / std::sqrt((double)n_fft));
-  switch (n_fft) {
-    case 16: return stft_mag_launch<16>(x, batch, n_samples, (int)hop, frames, scale, magnitudes, stream);
-    case 32: return stft_mag_launch<32>(x, batch, n_samples, (int)hop, frames, scale, magnitudes, stream);
-    case 64: return stft_mag_launch<64>(x, batch, n_samples, (int)hop, frames, scale, magnitudes, stream);
-    case 128: return stft_mag_launch<128>(x, batch, n_samples, (int)hop, frames, scale, magnitudes, stream);
-    case 256: return stft_mag_launch<256>(x, batch, n_samples, (int)hop, frames, scale, magnitudes, stream);
-    case 512: return stft_mag_launch<512>(x, batch, n_samples, (int)hop, frames, scale, magnitudes, stream);
-    case 1024: return stft_mag_launch<1024>(x, batch, n_samples, (int)hop, frames, scale, magnitudes, stream);
-    case 2048: return stft_mag_launch<2048>(x, batch, n_samples, (int)hop, frames, scale, magnitudes, stream);
-    default: return stft_mag_launch<4096>(x, batch, n_samples, (int)hop, frames, scale, magnitudes, stream);
-  }
+  return for_frame_length<16>(n_fft, [&](auto size) {
+    hipLaunchKernelGGL(stft_mag_kernel<decltype(size)::value>, frame_pair_grid(n_fft, frames, batch), dim3(256), 0,
+                       S(stream), x, n_samples, (int)hop, frames, scale, magnitudes);
+    return launch_status();
+  });
 }
 
 size_t ddsp_hip_stft_backward_workspace_size(int64_t batch, int64_t n_samples, int64_t n_fft, int64_t hop) {
@@ -362,17 +340,11 @@ int ddsp_hip_stft_magnitude_backward(const float* x, const float* grad_magnitude
   const float scale = (float)(1.0 / std::sqrt((double)n_fft));
   float* dF = reinterpret_cast<float*>(workspace);
   const int h = (int)hop;
-  switch (n_fft) {
-    case 16: st = stft_bwd_launch<16>(x, batch, n_samples, h, frames, scale, grad_magnitudes, dF, stream); break;
-    case 32: st = stft_bwd_launch<32>(x, batch, n_samples, h, frames, scale, grad_magnitudes, dF, stream); break;
-    case 64: st = stft_bwd_launch<64>(x, batch, n_samples, h, frames, scale, grad_magnitudes, dF, stream); break;
-    case 128: st = stft_bwd_launch<128>(x, batch, n_samples, h, frames, scale, grad_magnitudes, dF, stream); break;
-    case 256: st = stft_bwd_launch<256>(x, batch, n_samples, h, frames, scale, grad_magnitudes, dF, stream); break;
-    case 512: st = stft_bwd_launch<512>(x, batch, n_samples, h, frames, scale, grad_magnitudes, dF, stream); break;
-    case 1024: st = stft_bwd_launch<1024>(x, batch, n_samples, h, frames, scale, grad_magnitudes, dF, stream); break;
-    case 2048: st = stft_bwd_launch<2048>(x, batch, n_samples, h, frames, scale, grad_magnitudes, dF, stream); break;
-    default: st = stft_bwd_launch<4096>(x, batch, n_samples, h, frames, scale, grad_magnitudes, dF, stream); break;
-  }
+  st = for_frame_length<16>(n_fft, [&](auto size) {
+    hipLaunchKernelGGL(stft_mag_backward_kernel<decltype(size)::value>, frame_pair_grid(n_fft, frames, batch),
+                       dim3(256), 0, S(stream), x, n_samples, h, frames, scale, grad_magnitudes, dF);
+    return launch_status();
+  });
   if (st) return st;
   const int64_t total = batch * n_samples;
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20);
@@ -391,9 +363,7 @@ size_t ddsp_hip_spectral_loss_workspace_size(int64_t batch, int64_t n_samples, c
     blocks += (size_t)loss_blocks(n_ffts[i], frames, batch);
     dF = std::max(dF, sizeof(float) * (size_t)batch * frames * n_ffts[i]);
   }
-  const size_t head = ((2 * sizeof(double) * blocks + sizeof(int64_t) * (n_scales + 1) +
-                        sizeof(double) * n_scales) + 255) & ~(size_t)255;
-  return head + dF;
+  return loss_head_bytes(blocks, n_scales) + dF;
 }
 
 int ddsp_hip_spectral_loss(const float* target, const float* recon, int64_t batch, int64_t n_samples,
@@ -407,7 +377,7 @@ int ddsp_hip_spectral_loss(const float* target, const float* recon, int64_t batc
   if (!target || !recon) return DDSP_HIP_EINVAL;
   const size_t need = ddsp_hip_spectral_loss_workspace_size(batch, n_samples, n_ffts, hops, n_scales);
   if (!workspace || workspace_bytes < need) return DDSP_HIP_EWORKSPACE;
-  // workspace: partials (2 doubles per block, all scales) | block offsets | 1/count | dF
+  // workspace: the head (loss_head_bytes) | dF
   size_t blocks = 0;
   int64_t offs[65];
   double inv_counts[64];
@@ -423,9 +393,7 @@ int ddsp_hip_spectral_loss(const float* target, const float* recon, int64_t batc
   double* partials = reinterpret_cast<double*>(w);
   int64_t* d_offs = reinterpret_cast<int64_t*>(w + 2 * sizeof(double) * blocks);
   double* d_inv = reinterpret_cast<double*>(d_offs + n_scales + 1);
-  const size_t head = ((2 * sizeof(double) * blocks + sizeof(int64_t) * (n_scales + 1) +
-                        sizeof(double) * n_scales) + 255) & ~(size_t)255;
-  float* dF = reinterpret_cast<float*>(w + head);
+  float* dF = reinterpret_cast<float*>(w + loss_head_bytes(blocks, n_scales));
   if (hipMemcpyAsync(d_offs, offs, sizeof(int64_t) * (n_scales + 1), hipMemcpyHostToDevice, S(stream)) != hipSuccess ||
       hipMemcpyAsync(d_inv, inv_counts, sizeof(double) * n_scales, hipMemcpyHostToDevice, S(stream)) != hipSuccess)
     return DDSP_HIP_ELAUNCH;
@@ -439,18 +407,11 @@ int ddsp_hip_spectral_loss(const float* target, const float* recon, int64_t batc
     const float inv_count = (float)inv_counts[i];
     double* part = partials + 2 * offs[i];
     const bool g = grad_recon != nullptr;
-    int st;
-    switch (n) {
-      case 16: st = spectral_loss_launch<16>(target, recon, batch, n_samples, h, frames, scale, inv_count, g, part, dF, stream); break;
-      case 32: st = spectral_loss_launch<32>(target, recon, batch, n_samples, h, frames, scale, inv_count, g, part, dF, stream); break;
-      case 64: st = spectral_loss_launch<64>(target, recon, batch, n_samples, h, frames, scale, inv_count, g, part, dF, stream); break;
-      case 128: st = spectral_loss_launch<128>(target, recon, batch, n_samples, h, frames, scale, inv_count, g, part, dF, stream); break;
-      case 256: st = spectral_loss_launch<256>(target, recon, batch, n_samples, h, frames, scale, inv_count, g, part, dF, stream); break;
-      case 512: st = spectral_loss_launch<512>(target, recon, batch, n_samples, h, frames, scale, inv_count, g, part, dF, stream); break;
-      case 1024: st = spectral_loss_launch<1024>(target, recon, batch, n_samples, h, frames, scale, inv_count, g, part, dF, stream); break;
-      case 2048: st = spectral_loss_launch<2048>(target, recon, batch, n_samples, h, frames, scale, inv_count, g, part, dF, stream); break;
-      default: st = spectral_loss_launch<4096>(target, recon, batch, n_samples, h, frames, scale, inv_count, g, part, dF, stream); break;
-    }
+    int st = for_frame_length<16>(n, [&](auto size) {
+      hipLaunchKernelGGL(spectral_loss_kernel<decltype(size)::value>, frame_pair_grid(n, frames, batch), dim3(256), 0,
+                         S(stream), target, recon, n_samples, h, frames, scale, inv_count, (int)g, part, dF);
+      return launch_status();
+    });
     if (st) return st;
     if (g) {
       hipLaunchKernelGGL(stft_overlap_add_kernel, dim3(ola_grid), dim3(256), 0, S(stream), dF, n_samples, (int)n, h,

@@ -164,16 +164,6 @@ int64_t stream_partitions(int64_t N, int64_t L) { return (L + N - 1) / N; }
 
 using namespace ddsp;
 
-#define DDSP_STREAM_DISPATCH(N_, CALL)  \
-  switch (N_) {                         \
-    case 64: CALL(128); break;          \
-    case 128: CALL(256); break;         \
-    case 256: CALL(512); break;         \
-    case 512: CALL(1024); break;        \
-    case 1024: CALL(2048); break;       \
-    default: CALL(4096); break;         \
-  }
-
 extern "C" {
 
 size_t ddsp_hip_stream_state_bytes(int64_t batch, int64_t call_samples, int64_t ir_length) {
@@ -194,13 +184,13 @@ int ddsp_hip_stream_spectrum(const float* impulse, int64_t ir_length, int64_t ca
   const int64_t P = stream_partitions(call_samples, ir_length);
   if (P > INT32_MAX) return DDSP_HIP_ERANGE;
   if (spectrum_floats < ddsp_hip_stream_spectrum_floats(call_samples, ir_length)) return DDSP_HIP_EWORKSPACE;
-#define DDSP_STREAM_SPECTRUM(N2_)                                                                              \
-  hipLaunchKernelGGL(stream_spectrum_kernel<N2_>, dim3((unsigned)P),                                           \
-                     dim3(StreamShape<N2_>::Q < 64 ? 64 : StreamShape<N2_>::Q), 0, S(stream), impulse, ir_length, \
-                     reinterpret_cast<float2*>(spectrum))
-  DDSP_STREAM_DISPATCH(call_samples, DDSP_STREAM_SPECTRUM)
-#undef DDSP_STREAM_SPECTRUM
-  return launch_status();
+  return for_frame_length<128>(2 * call_samples, [&](auto size) {  // the transform: two calls long
+    constexpr int N2 = decltype(size)::value;
+    hipLaunchKernelGGL(stream_spectrum_kernel<N2>, dim3((unsigned)P),
+                       dim3(StreamShape<N2>::Q < 64 ? 64 : StreamShape<N2>::Q), 0, S(stream), impulse, ir_length,
+                       reinterpret_cast<float2*>(spectrum));
+    return launch_status();
+  });
 }
 
 int ddsp_hip_stream_reverb(const float* x, const float* spectrum, size_t spectrum_floats, const uint64_t* counter,
@@ -215,13 +205,13 @@ int ddsp_hip_stream_reverb(const float* x, const float* spectrum, size_t spectru
   if (state_bytes < lay.bytes || spectrum_floats < ddsp_hip_stream_spectrum_floats(call_samples, ir_length))
     return DDSP_HIP_EWORKSPACE;
   char* st = reinterpret_cast<char*>(state);
-#define DDSP_STREAM_REVERB(N2_)                                                                                  \
-  hipLaunchKernelGGL(stream_reverb_kernel<N2_>, dim3((unsigned)batch), dim3(StreamShape<N2_>::NT), 0, S(stream), x, \
-                     reinterpret_cast<const float2*>(spectrum), counter, reinterpret_cast<float*>(st + lay.hist), \
-                     reinterpret_cast<float2*>(st + lay.ring), y, (int)lay.P)
-  DDSP_STREAM_DISPATCH(call_samples, DDSP_STREAM_REVERB)
-#undef DDSP_STREAM_REVERB
-  return launch_status();
+  return for_frame_length<128>(2 * call_samples, [&](auto size) {
+    constexpr int N2 = decltype(size)::value;
+    hipLaunchKernelGGL(stream_reverb_kernel<N2>, dim3((unsigned)batch), dim3(StreamShape<N2>::NT), 0, S(stream), x,
+                       reinterpret_cast<const float2*>(spectrum), counter, reinterpret_cast<float*>(st + lay.hist),
+                       reinterpret_cast<float2*>(st + lay.ring), y, (int)lay.P);
+    return launch_status();
+  });
 }
 
 }  // extern "C"

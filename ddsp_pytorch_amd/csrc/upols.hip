@@ -40,6 +40,8 @@ constexpr int kPad = kN + kN / 16;  // LDS float2 slots: one pad slot per 16 (ba
 
 // Full 4096-point transform (three radix-16 Stockham passes, Ns = 1, 16, 256):
 // v holds in[j + 256 r] on entry and out[j + 256 r] on exit.
+// fft_n<4096, INV, false> but for one barrier: the second sits after the read-back, not before the next store.  Kept:
+// with fft_n the uncached-IR step measured 185.3 / 185.6 us against 183.9 / 183.9 (profiles/fft_once_ab.txt).
 template <bool INV>
 __device__ __forceinline__ void fft4096(float2 (&v)[16], float2* lds, int j = threadIdx.x) {
   // pass twiddle steps: k * N/(Ns*16) with k = j mod Ns

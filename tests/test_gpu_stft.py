@@ -49,8 +49,8 @@ def test_stft_magnitude(dd, n, T, hop_div):
     assert relerr(got, ref) < 1e-5, relerr(got, ref)
 
 
-@pytest.mark.parametrize("n,T", [(16, 12000), (128, 12000), (512, 12000), (1024, 12000), (4096, 12000),
-                                 (128, 102400), (4096, 102400)])
+@pytest.mark.parametrize("n,T", [(16, 12000), (32, 12000), (64, 12000), (128, 12000), (256, 12000), (512, 12000),
+                                 (1024, 12000), (2048, 12000), (4096, 12000), (128, 102400), (4096, 102400)])
 def test_stft_magnitude_grad(dd, n, T):
     hop = n // 4
     g = torch.Generator().manual_seed(n)
@@ -137,6 +137,30 @@ def test_fused_spectral_loss_matches_unfused(dd):
     r2 = s2 + 0.05 * torch.randn(4, 102400, generator=gg)
     lc = tr.multiscale_spec_loss(tr.multiscale_fft(s2, scales, 0.75), tr.multiscale_fft(r2, scales, 0.75))
     assert relerr(L.spectral_loss(s2.cuda(), r2.cuda()), lc) < 1e-5
+
+
+def test_fused_spectral_loss_small_scales(dd):
+    """The fused loss at the transform sizes below 128 (one radix-16 pass alone, then a radix-2 and a radix-4
+    tail), an odd length and an odd frame count: the value against the oracle on the CPU, bit-equal with and
+    without a gradient, and the gradient against the spectrogram route on the same kernels."""
+    from ddsp_pytorch_amd import loss as L
+    scales, overlap = [64, 32, 16], 0.75
+    g = torch.Generator().manual_seed(3)
+    sig = torch.randn(2, 3001, generator=g) * 0.3
+    rec = sig + 0.05 * torch.randn(2, 3001, generator=g)
+    lc = tr.multiscale_spec_loss(tr.multiscale_fft(sig, scales, overlap), tr.multiscale_fft(rec, scales, overlap))
+    rf = rec.cuda().requires_grad_(True)
+    lf = L.spectral_loss(sig.cuda(), rf, scales, overlap)
+    lf.backward()
+    ru = rec.cuda().requires_grad_(True)
+    L.multiscale_spec_loss(dd.core.multiscale_fft(sig.cuda(), scales, overlap),
+                           dd.core.multiscale_fft(ru, scales, overlap)).backward()
+    print("small scales: value", relerr(lf, lc), "gradient", relerr(rf.grad, ru.grad))
+    assert relerr(lf, lc) < 1e-5, (float(lf), float(lc))
+    with torch.no_grad():
+        l0 = L.spectral_loss(sig.cuda(), rec.cuda(), scales, overlap)
+    assert torch.equal(l0, lf.detach())
+    assert relerr(rf.grad, ru.grad) < 1e-3, relerr(rf.grad, ru.grad)
 
 
 def test_spectral_loss_grad_well_conditioned_bins(dd):

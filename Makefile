@@ -9,7 +9,7 @@ SRC := ddsp_pytorch_amd/csrc/synth.hip ddsp_pytorch_amd/csrc/noise.hip ddsp_pyto
        ddsp_pytorch_amd/csrc/stream_reverb.hip ddsp_pytorch_amd/csrc/features.hip \
        ddsp_pytorch_amd/csrc/pitch.hip ddsp_pytorch_amd/csrc/stream_analysis.hip \
        ddsp_pytorch_amd/csrc/stream_analysis_mfcc.hip ddsp_pytorch_amd/csrc/pitch_viterbi.hip \
-       ddsp_pytorch_amd/csrc/stream_pitch_viterbi.hip
+       ddsp_pytorch_amd/csrc/stream_pitch_viterbi.hip ddsp_pytorch_amd/csrc/pitch_grad.hip
 HDR := include/ddsp_hip.h ddsp_pytorch_amd/csrc/common.h ddsp_pytorch_amd/csrc/upols.h ddsp_pytorch_amd/csrc/fft_radix.h \
        ddsp_pytorch_amd/csrc/noise_dsp.h ddsp_pytorch_amd/csrc/stream_state.h ddsp_pytorch_amd/csrc/stft_frames.h \
        ddsp_pytorch_amd/csrc/bf16x3.h ddsp_pytorch_amd/csrc/impulse.h \
@@ -20,6 +20,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Iincl
 HIPFLAGS_synth := -fno-slp-vectorize
 HIPFLAGS_synth_frame := -fno-slp-vectorize
 HIPFLAGS_backward := -fno-slp-vectorize
+HIPFLAGS_pitch_grad := -fno-slp-vectorize
 # packed f32 VALU beside MFMAs costs more than the scalar pair (MI355X_MICROARCH.md cycle constants)
 HIPFLAGS_dense := -fno-slp-vectorize
 OBJ := $(patsubst ddsp_pytorch_amd/csrc/%.hip,build/%.o,$(SRC))

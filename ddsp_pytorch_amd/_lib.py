@@ -144,7 +144,12 @@ SIGNATURES = {
     "ddsp_hip_harmonic_controls_backward": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _I64, _F, _P]),
     "ddsp_hip_harmonic_synth_frames_backward": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _P]),
     "ddsp_hip_harmonic_synth_params_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _P]),
-    "ddsp_hip_synth_frames_backward": (_I, [_P, _P, _P, _F, _P, _U64, _U64, _P, _P, _P, _P, _I64, _I64, _I64,
+    # pitch (f0) gradient of the frame-rate synthesis
+    "ddsp_hip_frame_pitch_grad_workspace_size": (_SZ, [_I64, _I64]),
+    "ddsp_hip_frame_pitch_grad_scan_chunk": (_I64, []),
+    "ddsp_hip_harmonic_synth_frames_pitch_grad": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _P, _SZ, _P]),
+    "ddsp_hip_harmonic_synth_params_pitch_grad": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _P, _SZ, _P]),
+    "ddsp_hip_synth_frames_backward": (_I,[_P, _P, _P, _F, _P, _U64, _U64, _P, _P, _P, _P, _I64, _I64, _I64,
                                             _I64, _I64, _F, _P]),
     "ddsp_hip_filtered_noise_backward": (_I, [_P, _P, _U64, _U64, _I, _F, _P, _P, _I64, _I64, _I64, _I64, _P]),
     "ddsp_hip_reverb_apply_transposed": (_I, [_P, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),

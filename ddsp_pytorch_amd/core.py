@@ -126,6 +126,7 @@ def harmonic_synth(f0, amplitudes, sample_rate):
     """ddsp/core.py:136-141  f0[B, T, 1], amplitudes[B, T, H] -> [B, T, 1]."""
     _dev(f0, amplitudes)
     if _wants_grad(f0, amplitudes):
+        # per-sample f0: its gradient is a reverse scan over T, not built (the frame-rate ops below have one)
         _grad.refuse_f0_grad(f0, "harmonic_synth")
         return _grad.HarmonicSynthFn.apply(f0, amplitudes, sample_rate)
     if amplitudes.dim() != 3 or f0.dim() != 3 or f0.shape[-1] != 1:
@@ -214,7 +215,6 @@ def harmonic_controls(amplitudes, harmonic_distribution, f0, sample_rate):
     """modules.py:44-67 HarmonicSynth.get_controls, fused: returns (amplitudes, distribution)."""
     _dev(amplitudes, harmonic_distribution, f0)
     if _wants_grad(amplitudes, harmonic_distribution, f0):
-        _grad.refuse_f0_grad(f0, "harmonic_controls")
         return _grad.ControlsFn.apply(amplitudes, harmonic_distribution, f0, sample_rate)
     B, F, H = harmonic_distribution.shape
     if amplitudes.shape != (B, F, 1) or f0.shape != (B, F, 1):
@@ -238,10 +238,11 @@ def harmonic_synth_frames(f0, amplitudes, harmonic_distribution, block_size, sam
     Returns audio [B, F*block_size, 1].  With ``write_back`` the distribution is multiplied
     by the amplitudes in place, exactly like ``harmonic_distribution *= amplitudes``
     (modules.py:73), which the reference's caller sees through its controls dict.
+    Differentiable in the controls and in f0 (grad.SynthFramesHarmonicFn; the pitch gradient, what the
+    reference's autograd sends through cumsum and sin, from csrc/pitch_grad.hip).
     """
     _dev(f0, amplitudes, harmonic_distribution)
     if _wants_grad(f0, amplitudes, harmonic_distribution):
-        _grad.refuse_f0_grad(f0, "harmonic_synth_frames")
         out = _grad.SynthFramesHarmonicFn.apply(f0, amplitudes, harmonic_distribution, block_size, sample_rate)
         if write_back:  # modules.py:73, recorded by autograd like the reference's in-place multiply
             harmonic_distribution.mul_(amplitudes)
@@ -283,10 +284,10 @@ def set_noise_seed(seed):
 def harmonic_synth_params(f0, param, block_size, sample_rate):
     """decoder.py:106-113 + modules.py:44-80 in one kernel: raw harmonic projection
     param[B, F, H+1] (column 0 amplitude, 1..H distribution) and f0 [B, F, 1] -> audio
-    [B, F*block_size, 1].  The controls (scale, Nyquist mask, normalisation) never reach HBM."""
+    [B, F*block_size, 1].  The controls (scale, Nyquist mask, normalisation) never reach HBM.
+    Differentiable in param and in f0 (grad.HarmonicParamsFn; the pitch gradient from csrc/pitch_grad.hip)."""
     _dev(f0, param)
     if _wants_grad(f0, param):
-        _grad.refuse_f0_grad(f0, "harmonic_synth_params")
         return _grad.HarmonicParamsFn.apply(f0, param, block_size, sample_rate)
     B, F, H1 = param.shape
     if f0.shape != (B, F, 1) or H1 < 2:
@@ -393,7 +394,6 @@ def synth_frames(f0, param, mags, block_size, sample_rate, bias=-5.0, noise=None
     if not synth_frames_in_envelope(H, NB, bs, B):
         return None
     if _wants_grad(f0, param, mags):
-        _grad.refuse_f0_grad(f0, "synth_frames")
         outs = _grad.SynthFramesFn.apply(f0, param, mags, bs, float(sample_rate), float(bias), noise,
                                          bool(parts))
         if not controls:

@@ -15,8 +15,8 @@
 //     dh[j] = sum_{i>=j} g_i x_{i-j},  dA_k = (c_k/n) (-1)^k sum_q dh[j(q)] hann[q] cos(2 pi q k/n),
 //     c_0 = c_{n/2} = 1, else 2;  raw magnitudes: dm_k = dA_k scale_fn'(m_k + bias).
 //
-// f0 is an input feature in the reference's training loop (train.py:84-99: batch['pitch']),
-// so no gradient flows to it; the host layer refuses f0 that requires grad.
+// f0 is an input feature in the reference's training loop (train.py:84-99: batch['pitch']); these kernels
+// return no gradient for it.  Where a frame-rate f0 requires grad, pitch_grad.hip's two launches run beside them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

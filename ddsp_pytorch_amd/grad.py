@@ -6,10 +6,16 @@ The reference trains by back-propagating a multiscale spectral loss through
 runs the forward kernel and, in ``backward``, the matching vector-Jacobian kernel of
 ``csrc/backward.hip`` / ``csrc/upols.hip`` through the C-ABI (include/ddsp_hip.h).
 
-Pitch (f0) is an input feature in the reference's training loop (``batch['pitch']``,
-train.py:84-99): no gradient flows to it.  ``remove_above_nyquist`` gives f0 the zero
-gradient the reference's comparison gives; the oscillator ops refuse an f0 that
-requires grad rather than silently returning a wrong (zero) gradient.
+Pitch (f0): the reference's autograd back-propagates into f0 through ``torch.cumsum`` and ``torch.sin``
+(ddsp/core.py:136-141) and ``upsample``; only ``remove_above_nyquist``, a comparison, gives it a zero
+gradient.  The frame-rate synthesis ops (``harmonic_synth_frames``, ``harmonic_synth_params``,
+``synth_frames`` / ``synth_signal``) return that gradient when f0 requires grad, from two launches of
+``csrc/pitch_grad.hip`` (per frame Q_f = sum_j q_j and R_f = sum_j (j+1) q_j with q_j = g_j sum_k k A_k
+cos(fl32(omega_j k)), then d f0_f = (2 pi / sr) (R_f + bs sum_{f'>f} Q_{f'}) by a reverse scan over the
+frames); a pitch that is a plain input issues no such launch.  ``ControlsFn`` and ``NyquistFn`` return
+None for f0: the comparison's zero.  The per-sample op ``core.harmonic_synth`` (f0 [B,T,1]) still refuses
+an f0 that requires grad rather than silently returning a wrong (zero) gradient: its gradient is a scan
+over T samples, a different kernel (pass frame-rate pitch to the ops above, or ``f0.detach()``).
 
 First order only: every ``backward`` is ``once_differentiable`` (the vector-Jacobian kernels write
 into fresh buffers that autograd cannot see through), so a double backward (``create_graph=True``,
@@ -32,10 +38,35 @@ def _g(t):
 
 
 def refuse_f0_grad(f0, name):
+    """The per-sample oscillator op only (core.harmonic_synth, f0 [B,T,1]): the frame-rate ops have an f0
+    gradient (frames_pitch_grad / params_pitch_grad below); per sample it is a reverse scan over T."""
     if torch.is_grad_enabled() and f0.requires_grad:
         raise NotImplementedError(
-            f"ddsp_hip {name}: no gradient w.r.t. f0 (pitch is an input feature in the reference's "
-            "training loop, train.py:84-99); pass f0.detach()")
+            f"ddsp_hip {name}: no gradient w.r.t. a per-sample f0 (a reverse scan over the samples, not "
+            "built); use the frame-rate ops (harmonic_synth_frames, harmonic_synth_params, synth_frames) "
+            "or pass f0.detach()")
+
+
+def _pitch_grad(entry, f0, operands, g, H, block_size, sample_rate):
+    B, F = f0.shape[0], f0.shape[1]
+    d = torch.empty(B, F, 1, dtype=torch.float32, device=g.device)
+    ws = core._workspace(_lib.query("frame_pitch_grad_workspace_size", B, F), g.device)
+    _lib.call(entry, _lib.ptr(core._c(f0)), *(_lib.ptr(core._c(t)) for t in operands), _lib.ptr(g), _lib.ptr(d),
+              B, F, int(H), int(block_size), float(sample_rate), _lib.ptr(ws), ws.numel(), _lib.stream_of(d))
+    return d
+
+
+def frames_pitch_grad(f0, amp, dist, g, block_size, sample_rate):
+    """d f0 [B,F,1] of harmonic_synth_frames for upstream g [B,F*bs,1]; ``dist`` is the normalised distribution
+    before the multiplication by ``amp`` (csrc/pitch_grad.hip)."""
+    return _pitch_grad("harmonic_synth_frames_pitch_grad", f0, (amp, dist), g, dist.shape[-1], block_size,
+                       sample_rate)
+
+
+def params_pitch_grad(f0, param, g, block_size, sample_rate):
+    """d f0 [B,F,1] of harmonic_synth_params (and of synth_frames' harmonic half) for upstream g [B,F*bs,1]."""
+    return _pitch_grad("harmonic_synth_params_pitch_grad", f0, (param,), g, param.shape[-1] - 1, block_size,
+                       sample_rate)
 
 
 # ------------------------------------------------------------------------------------------
@@ -214,7 +245,8 @@ class SynthFramesHarmonicFn(_F):
         _lib.call("harmonic_synth_frames_backward", _lib.ptr(core._c(ctx.f0)), _lib.ptr(ctx.amp),
                   _lib.ptr(ctx.dist), _lib.ptr(g), _lib.ptr(da), _lib.ptr(dd), B, F, H, ctx.bs, ctx.sr,
                   _lib.stream_of(g))
-        return None, da, dd, None, None
+        df0 = frames_pitch_grad(ctx.f0, ctx.amp, ctx.dist, g, ctx.bs, ctx.sr) if ctx.needs_input_grad[0] else None
+        return df0, da, dd, None, None
 
 
 def params_backward(f0, param, g, block_size, sample_rate):
@@ -248,7 +280,10 @@ class HarmonicParamsFn(_F):
     @once_differentiable
     def backward(ctx, g):
         f0, param = ctx.saved_tensors
-        return None, params_backward(f0.detach(), param.detach(), _g(g), ctx.bs, ctx.sr), None, None
+        f0, param, g = f0.detach(), param.detach(), _g(g)
+        dp = params_backward(f0, param, g, ctx.bs, ctx.sr)
+        df0 = params_pitch_grad(f0, param, g, ctx.bs, ctx.sr) if ctx.needs_input_grad[0] else None
+        return df0, dp, None, None
 
 
 class FilteredNoiseFn(_F):
@@ -279,7 +314,8 @@ class FilteredNoiseFn(_F):
 
 
 class SynthFramesFn(_F):
-    """decoder.py:106-121 in one kernel; backward = harmonic params + raw noise VJPs."""
+    """decoder.py:106-121 in one kernel; backward = harmonic params + raw noise VJPs, and the pitch gradient of
+    the harmonic half when f0 requires grad."""
 
     @staticmethod
     def forward(ctx, f0, param, mags, block_size, sample_rate, bias, noise, parts):
@@ -306,7 +342,8 @@ class SynthFramesFn(_F):
                   _lib.ptr(core._c(mags.detach())), ctx.bias, _lib.ptr(ctx.noise), ctx.seed, ctx.offset,
                   _lib.ptr(gh), _lib.ptr(gn), _lib.ptr(dp), _lib.ptr(dm), B, F, H1 - 1, NB, ctx.bs, ctx.sr,
                   _lib.stream_of(dp))
-        return (None, dp if ctx.needs_input_grad[1] else None, dm if ctx.needs_input_grad[2] else None,
+        df0 = params_pitch_grad(f0.detach(), param.detach(), gh, ctx.bs, ctx.sr) if ctx.needs_input_grad[0] else None
+        return (df0, dp if ctx.needs_input_grad[1] else None, dm if ctx.needs_input_grad[2] else None,
                 None, None, None, None, None)
 
 

@@ -52,23 +52,24 @@ class SynthPath(nn.Module):
             return _Null()
         return self.timer(name)
 
-    @torch.no_grad()
     def synthesize(self, f0, param, mags, noise=None):
         """decoder.py:106-121: harmonic + filtered noise (both synths, their controls and the sum)
-        in one kernel (outside its envelope two, core.synth_signal) — the path before the reverb."""
+        in one kernel (outside its envelope two, core.synth_signal) — the path before the reverb.
+        Recorded by autograd when one of f0, param, mags requires grad (the pitch included: its gradient comes
+        from csrc/pitch_grad.hip); inference otherwise, whatever the reverb's parameters say."""
         if self.noise_mode == "inject" and noise is None:
             raise ValueError("noise_mode='inject' needs a noise tensor")
         nz = noise if self.noise_mode == "inject" else None
-        with self._t("synth_frames"):
+        with torch.set_grad_enabled(core._wants_grad(f0, param, mags)), self._t("synth_frames"):
             return core.synth_signal(f0, param, mags, self.block_size, self.sample_rate,
                                      bias=self.initial_bias, noise=nz)
 
-    @torch.no_grad()
     def forward(self, f0, param, mags, noise=None):
-        signal = self.synthesize(f0, param, mags, noise)
-        if self.reverb is not None:
-            with self._t("reverb"):
-                signal = self.reverb(signal)
+        with torch.set_grad_enabled(core._wants_grad(f0, param, mags)):
+            signal = self.synthesize(f0, param, mags, noise)
+            if self.reverb is not None:
+                with self._t("reverb"):
+                    signal = self.reverb(signal)
         return signal
 
 

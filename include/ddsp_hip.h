@@ -511,6 +511,34 @@ int ddsp_hip_harmonic_synth_params_backward(const float* f0, const float* param,
                                             int64_t n_harmonic, int64_t block_size, float sample_rate,
                                             void* stream);
 
+/* The pitch (f0) gradient of the frame-rate harmonic synthesis, what the reference's autograd sends into f0
+ * through torch.cumsum and torch.sin (core.py:136-141; remove_above_nyquist, a comparison, contributes nothing):
+ *   grad_f0[b,f] = c (R_f + bs sum_{f'>f} Q_{f'}),  c = 2 pi / sample_rate,
+ *   Q_f = sum_j q_j, R_f = sum_j (j+1) q_j,  q_j = grad[f,j] sum_k k A_k cos(fl32(omega_{f,j} k)),
+ * with the frame kernels' phase omega_{f,j} and the frame's harmonic amplitudes A_k, formed either from the frame
+ * controls (ddsp_hip_harmonic_synth_frames_pitch_grad: amplitudes[B,F] and the normalised distribution[B,F,H]
+ * BEFORE the in-place multiplication, as ddsp_hip_harmonic_synth_frames_backward takes them) or from the raw
+ * projection (ddsp_hip_harmonic_synth_params_pitch_grad: param[B,F,H+1], also the harmonic half of
+ * ddsp_hip_synth_frames).  grad[B,F*bs] -> grad_f0[B,F].  Two launches (the per-frame sums as doubles in the
+ * workspace, then a reverse scan over each item's frames; past 512 frames per item a ddsp_hip_frame_phase_prefix
+ * launch ahead of them).  workspace: 8-byte aligned, ddsp_hip_frame_pitch_grad_workspace_size(batch, frames)
+ * bytes.  ddsp_hip_frame_pitch_grad_scan_chunk: the frames per step of the reverse scan (any frame count is
+ * valid; tests place frame counts around its multiples).
+ * Checked before any launch: negative batch / frames, block_size < 1, n_harmonic < 1, sample_rate not > 0, null
+ * buffers or workspace: DDSP_HIP_EINVAL; batch > 65535, n_harmonic > 4096, block_size > 8192: DDSP_HIP_ERANGE; a
+ * short workspace: DDSP_HIP_EWORKSPACE; batch == 0 or frames == 0: a no-op success.  The per-sample op
+ * (ddsp_hip_harmonic_synth, f0[B,T]) has no f0 gradient here: that is a scan over T, another kernel. */
+size_t ddsp_hip_frame_pitch_grad_workspace_size(int64_t batch, int64_t frames);
+int64_t ddsp_hip_frame_pitch_grad_scan_chunk(void);
+int ddsp_hip_harmonic_synth_frames_pitch_grad(const float* f0, const float* amplitudes, const float* distribution,
+                                              const float* grad, float* grad_f0, int64_t batch, int64_t frames,
+                                              int64_t n_harmonic, int64_t block_size, float sample_rate,
+                                              void* workspace, size_t workspace_bytes, void* stream);
+int ddsp_hip_harmonic_synth_params_pitch_grad(const float* f0, const float* param, const float* grad, float* grad_f0,
+                                              int64_t batch, int64_t frames, int64_t n_harmonic, int64_t block_size,
+                                              float sample_rate, void* workspace, size_t workspace_bytes,
+                                              void* stream);
+
 /* decoder.py:106-121 backward (ddsp_hip_synth_frames): grad_param[B,F,H+1] and grad_magnitudes[B,F,NB]
  * (raw projections) from the upstream gradient of the signal, as two launches (harmonic, noise); the noise
  * is `noise` or the forward's Philox (seed, offset).  grad_noise (nullable) is a separate upstream

@@ -1,6 +1,6 @@
 """Run one kernel of the synthesis path repeatedly at configuration 2 (for rocprofv3 PMC passes).
 
-    python tools/kernel_probe.py {fused,bwd,reverb_bwd,reverb_ir,gru,gru_train,harmonic,harmonic_frames,noise,reverb,op}
+    python tools/kernel_probe.py {fused,bwd,pitch_grad,reverb_bwd,reverb_ir,gru,gru_train,harmonic,harmonic_frames,noise,reverb,op}
                                  [reps] [frames]
 
 frames (default 200, configuration 2's): another signal length, e.g. 250 for the reverb's ring MAC kernels
@@ -29,6 +29,16 @@ def main():
         param = inp["param"].clone().requires_grad_(True)
         mags = inp["mags"].clone().requires_grad_(True)
         out = core.synth_frames(inp["f0"], param, mags, bs, sr)
+        g = torch.randn_like(out)
+        for _ in range(reps):
+            out.backward(g, retain_graph=True)
+        torch.cuda.synchronize()
+        return
+    if which == "pitch_grad":  # the harmonic VJP (frame_backward_kernel<2, 0, false>) and, beside it in the same
+        # backward, the pitch gradient's two launches (frame_pitch_grad_kernel<true>, pitch_grad_scan_kernel)
+        param = inp["param"].clone().requires_grad_(True)
+        f0 = inp["f0"].clone().requires_grad_(True)
+        out = core.harmonic_synth_params(f0, param, bs, sr)
         g = torch.randn_like(out)
         for _ in range(reps):
             out.backward(g, retain_graph=True)

@@ -62,6 +62,7 @@ SIGNATURES = {
     "ddsp_hip_synth_frames": (_I, [_P, _P, _P, _F, _P, _U64, _U64, _P, _P, _P, _I64, _I64, _I64, _I64,
                                    _I64, _F, _P]),
     "ddsp_hip_synth_frames_supported": (_I, [_I64, _I64, _I64, _I64]),
+    "ddsp_hip_synth_frames_route": (_I, [_I64, _I64, _I64, _I64, _I64, _I, ctypes.POINTER(_I)]),
     "ddsp_hip_synth_frames_controls_prefix": (_I, [_P, _P, _I64, _P, _I64, _F, _P, _U64, _U64, _P, _P, _P, _P, _P,
                                                    _I64, _I64, _I64, _I64, _I64, _F, _P]),
     "ddsp_hip_frame_phase_prefix": (_I, [_P, _I64, _I64, _I64, _F, _P, _P]),

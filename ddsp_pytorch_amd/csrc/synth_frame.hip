@@ -21,6 +21,44 @@
 namespace ddsp {
 namespace {
 
+// a frame's LDS layout (frame_synth): the FIR's first run [0, lo_end) and the wrapped taps from
+// tail_start, the zero padding ahead of the samples, and the floats of one frame buffer
+struct FrameShape {
+  int lo_end, tail_start, pad;
+  size_t floats;
+};
+constexpr FrameShape frame_shape(int64_t n_harmonic, int64_t n_bands, int bs) {
+  const int n = 2 * (int)(n_bands - 1), half = n / 2;
+  FrameShape fs{};
+  fs.lo_end = fs.tail_start = bs;  // one run over the whole frame, unless the FIR's two halves fit it apart
+  if (bs >= n && bs - half >= ((half + 3) & ~3)) {
+    fs.lo_end = (half + 3) & ~3;
+    fs.tail_start = bs - half;
+  }
+  fs.pad = (fs.lo_end + 4 + 3) & ~3;
+  const int H4 = ((int)n_harmonic + 3) & ~3, n4 = (n + 3) & ~3;
+  fs.floats = (size_t)2 * H4 + n4 + (((int)n_bands + 3) & ~3) + ((half + 4) & ~3) + bs + ((half + 3) & ~3) +
+              fs.pad + bs;
+  return fs;
+}
+// threads of one 4-samples-per-thread frame: whole waves
+constexpr int frame_threads(int bs) { return std::max(64, ((bs / 4 + 63) / 64) * 64); }
+
+// Where frame_synth takes a frame's shape from.  AnyShape: the launch's arguments, whatever frame_plan admits.
+// FixedShape: the one model shape the project ships (65 bands, block 512: bench configs 2, 4 and 5, DDSPDecoder,
+// train.py) as constants out of the same frame_shape(), so that the n == 128 filter design, the 64-tap tail and the
+// table read of fill_cos_table are the only paths left, the FIR's 16 tap quads unroll and no address or trip
+// count is computed from a kernel argument (registers 77 -> 61, 12 -> 16 workgroups per CU).
+struct AnyShape {
+  int NB, bs, lo_end, tail_start, pad, NT;
+};
+struct FixedShape {
+  static constexpr int NB = 65, bs = 512, NT = frame_threads(bs);
+  static constexpr int lo_end = frame_shape(1, NB, bs).lo_end, tail_start = frame_shape(1, NB, bs).tail_start,
+                       pad = frame_shape(1, NB, bs).pad;  // none of the three depends on n_harmonic
+  static_assert(NT == 128 && lo_end == 64 && tail_start == 448 && pad == 68, "the shape frame_synth's fast paths take");
+};
+
 // The oscillator bank over the (k+1, amplitude) table for 4 samples: acc[s] += A_k sin(fl32(w_s (k+1)))
 // in table order, which is descending k (frame_synth phase 2).  H4 % 4 == 0.  (A register double buffer of
 // the next 4 coefficients was re-rolled by the compiler into load-then-use; forced through inline assembly it
@@ -109,14 +147,17 @@ __device__ __forceinline__ float irfft128_tap32(const float* A) {
 // training / serving shapes run the code without the branch (1.9% of the kernel, same-box A/B).
 // CARRY: the item's phase at the start of the call (carry0, the realtime stream's running prefix) is added to
 // the frame's own prefix, so a stream of calls continues the oscillators of the call before.
-template <bool RNG, bool SPLIT, bool CTRL, bool PREFIX, bool CARRY = false>
+// Shape: AnyShape or FixedShape (above); the code below is the same for both, the fixed one folds its branches.
+template <bool RNG, bool SPLIT, bool CTRL, bool PREFIX, bool CARRY = false, class Shape>
 __device__ __forceinline__ bool frame_synth(
     const float* __restrict__ f0, const float* __restrict__ param, const float* __restrict__ mags,
     float bias, const float* __restrict__ noise, uint32_t k0, uint32_t k1, uint32_t off0, uint32_t off1,
-    const uint64_t* __restrict__ counter, float* __restrict__ ctrl_out, int B, int F, int H, int NB, int bs,
-    float sr, int lo_end, int tail_start, int pad, int f, int b, int tid, int NT, float4* smem4, double* red,
+    const uint64_t* __restrict__ counter, float* __restrict__ ctrl_out, int B, int F, int H, Shape shape,
+    float sr, int f, int b, int tid, float4* smem4, double* red,
     int w0, float (&acc)[4], float (&nz)[4], int& j0_out, int ldp, int ldm, const double* __restrict__ prefix,
     double carry0 = 0.0) {
+  const int NB = shape.NB, bs = shape.bs, lo_end = shape.lo_end, tail_start = shape.tail_start, pad = shape.pad,
+            NT = shape.NT;
   const int n = 2 * (NB - 1), half = n >> 1, n4 = (n + 3) & ~3;
   const int H4 = (H + 3) & ~3;
   float2* coef = reinterpret_cast<float2*>(smem4);       // [H4] (k+1, amplitude)
@@ -403,6 +444,33 @@ __device__ __forceinline__ bool frame_synth(
   return true;
 }
 
+// One workgroup's frame of a ddsp_hip_synth_frames* launch: frame_synth and the stores of its three outputs.
+template <bool RNG, bool SPLIT, bool CTRL, bool PREFIX, class Shape>
+__device__ __forceinline__ void synth_frame_workgroup(
+    const float* __restrict__ f0, const float* __restrict__ param, const float* __restrict__ mags,
+    float bias, const float* __restrict__ noise, uint32_t k0, uint32_t k1, uint32_t off0, uint32_t off1,
+    const uint64_t* __restrict__ counter, float* __restrict__ out, float* __restrict__ harm_out,
+    float* __restrict__ noise_out, float* __restrict__ ctrl_out, int F, int H, Shape shape, float sr, int ldp, int ldm,
+    const double* __restrict__ prefix) {
+  extern __shared__ float4 smem4[];
+  __shared__ double red[32];
+  float acc[4], nz[4];
+  int j0;
+  if (!frame_synth<RNG, SPLIT, CTRL, PREFIX>(f0, param, mags, bias, noise, k0, k1, off0, off1, counter, ctrl_out,
+                                             (int)gridDim.y, F, H, shape, sr, blockIdx.x, blockIdx.y, threadIdx.x,
+                                             smem4, red, 0, acc, nz, j0, ldp, ldm, prefix))
+    return;
+  const int64_t o = ((int64_t)blockIdx.y * F + blockIdx.x) * shape.bs + j0;
+  if (harm_out) *reinterpret_cast<float4*>(harm_out + o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  if (noise_out) *reinterpret_cast<float4*>(noise_out + o) = make_float4(nz[0], nz[1], nz[2], nz[3]);
+  *reinterpret_cast<float4*>(out + o) =
+      make_float4(acc[0] + nz[0], acc[1] + nz[1], acc[2] + nz[2], acc[3] + nz[3]);  // decoder.py:121
+}
+
+// The kernel of the shipped shape and the few-frame kernel.  SPLIT = false: FixedShape, launched by frame_plan
+// for 65 bands at block 512 with FixedShape::NT threads (the shape arguments are not read).  SPLIT = true: any
+// shape, G thread groups per frame.  (The names are the ones bench.py and tests/test_loop_align.py look up, so
+// the pinned non-split instantiations are the kernels the benchmark runs.)
 template <bool RNG, bool SPLIT, bool CTRL, bool PREFIX>
 __global__ void __launch_bounds__(256) synth_frame_kernel(
     const float* __restrict__ f0, const float* __restrict__ param, const float* __restrict__ mags,
@@ -410,20 +478,29 @@ __global__ void __launch_bounds__(256) synth_frame_kernel(
     const uint64_t* __restrict__ counter, float* __restrict__ out, float* __restrict__ harm_out,
     float* __restrict__ noise_out, float* __restrict__ ctrl_out, int F, int H,
     int NB, int bs, float sr, int lo_end, int tail_start, int pad, int ldp, int ldm, const double* __restrict__ prefix) {
-  extern __shared__ float4 smem4[];
-  __shared__ double red[32];
-  float acc[4], nz[4];
-  int j0;
-  if (!frame_synth<RNG, SPLIT, CTRL, PREFIX>(f0, param, mags, bias, noise, k0, k1, off0, off1, counter, ctrl_out,
-                                      (int)gridDim.y, F, H, NB, bs, sr, lo_end, tail_start, pad, blockIdx.x,
-                                      blockIdx.y, threadIdx.x, blockDim.x, smem4, red, 0, acc, nz, j0, ldp, ldm,
-                                      prefix))
-    return;
-  const int64_t o = ((int64_t)blockIdx.y * F + blockIdx.x) * bs + j0;
-  if (harm_out) *reinterpret_cast<float4*>(harm_out + o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-  if (noise_out) *reinterpret_cast<float4*>(noise_out + o) = make_float4(nz[0], nz[1], nz[2], nz[3]);
-  *reinterpret_cast<float4*>(out + o) =
-      make_float4(acc[0] + nz[0], acc[1] + nz[1], acc[2] + nz[2], acc[3] + nz[3]);  // decoder.py:121
+  if constexpr (SPLIT)
+    synth_frame_workgroup<RNG, true, CTRL, PREFIX>(f0, param, mags, bias, noise, k0, k1, off0, off1, counter, out,
+                                                   harm_out, noise_out, ctrl_out, F, H,
+                                                   AnyShape{NB, bs, lo_end, tail_start, pad, (int)blockDim.x}, sr, ldp,
+                                                   ldm, prefix);
+  else
+    synth_frame_workgroup<RNG, false, CTRL, PREFIX>(f0, param, mags, bias, noise, k0, k1, off0, off1, counter, out,
+                                                    harm_out, noise_out, ctrl_out, F, H, FixedShape{}, sr, ldp, ldm,
+                                                    prefix);
+}
+
+// Every other shape, four samples per thread.
+template <bool RNG, bool CTRL, bool PREFIX>
+__global__ void __launch_bounds__(256) synth_frame_any_kernel(
+    const float* __restrict__ f0, const float* __restrict__ param, const float* __restrict__ mags,
+    float bias, const float* __restrict__ noise, uint32_t k0, uint32_t k1, uint32_t off0, uint32_t off1,
+    const uint64_t* __restrict__ counter, float* __restrict__ out, float* __restrict__ harm_out,
+    float* __restrict__ noise_out, float* __restrict__ ctrl_out, int F, int H,
+    int NB, int bs, float sr, int lo_end, int tail_start, int pad, int ldp, int ldm, const double* __restrict__ prefix) {
+  synth_frame_workgroup<RNG, false, CTRL, PREFIX>(f0, param, mags, bias, noise, k0, k1, off0, off1, counter, out,
+                                                  harm_out, noise_out, ctrl_out, F, H,
+                                                  AnyShape{NB, bs, lo_end, tail_start, pad, (int)blockDim.x}, sr, ldp,
+                                                  ldm, prefix);
 }
 
 __global__ void counter_advance_kernel(uint64_t* counter) { *counter += 1; }
@@ -475,8 +552,9 @@ __global__ void __launch_bounds__(256) synth_stream_kernel(
   const double c = carry[blockIdx.y];
   const double c0 = wrap ? wrap_2pi(c) : c;
   if (!frame_synth<RNG, SPLIT, false, false, true>(f0, param, mags, bias, noise, k0, k1, 0u, 0u, counter, nullptr,
-                                                          (int)gridDim.y, F, H, NB, bs, sr, lo_end, tail_start, pad,
-                                                          blockIdx.x, blockIdx.y, threadIdx.x, blockDim.x, smem4, red, 0,
+                                                          (int)gridDim.y, F, H,
+                                                          AnyShape{NB, bs, lo_end, tail_start, pad, (int)blockDim.x}, sr,
+                                                          blockIdx.x, blockIdx.y, threadIdx.x, smem4, red, 0,
                                                           acc, nz, j0, H + 1, NB, nullptr, c0))
     return;
   const int64_t o = ((int64_t)blockIdx.y * F + blockIdx.x) * bs + j0;
@@ -506,33 +584,13 @@ __global__ void __launch_bounds__(256) stream_advance_kernel(const float* __rest
 
 using namespace ddsp;
 
-// a frame's LDS layout (frame_synth): the FIR's first run [0, lo_end) and the wrapped taps from
-// tail_start, the zero padding ahead of the samples, and the floats of one frame buffer
-struct FrameShape {
-  int lo_end, tail_start, pad;
-  size_t floats;
-};
-static FrameShape frame_shape(int64_t n_harmonic, int64_t n_bands, int bs) {
-  const int n = 2 * (int)(n_bands - 1), half = n / 2;
-  FrameShape fs;
-  fs.lo_end = fs.tail_start = bs;  // one run over the whole frame, unless the FIR's two halves fit it apart
-  if (bs >= n && bs - half >= ((half + 3) & ~3)) {
-    fs.lo_end = (half + 3) & ~3;
-    fs.tail_start = bs - half;
-  }
-  fs.pad = (fs.lo_end + 4 + 3) & ~3;
-  const int H4 = ((int)n_harmonic + 3) & ~3, n4 = (n + 3) & ~3;
-  fs.floats = (size_t)2 * H4 + n4 + (((int)n_bands + 3) & ~3) + ((half + 4) & ~3) + bs + ((half + 3) & ~3) +
-              fs.pad + bs;
-  return fs;
-}
-
 // The fused kernels' launch plan: the one place that decides which shapes they take (the envelope that
 // ddsp_hip_synth_frames_supported reports) and how a shape is launched.
 struct FramePlan {
   FrameShape fs;
   int nt;      // threads per frame and thread group
   int G;       // thread groups that share a frame's harmonics (the SPLIT kernels when > 1)
+  bool fixed;  // the shape is FixedShape's and not split: ddsp_hip_synth_frames* launch the fixed-shape kernel
   size_t shm;  // LDS bytes, the split buffer included
   dim3 grid, block;
   int status;  // DDSP_HIP_OK, or DDSP_HIP_ERANGE outside the envelope
@@ -550,10 +608,12 @@ static FramePlan frame_plan(int64_t batch, int64_t frames, int64_t n_harmonic, i
   // Cannot bind under the caps above: over every n_bands and block size at n_harmonic = 1024 a frame takes at
   // most 45,104 bytes, the split buffer included.  It guards a raised cap.
   if (sizeof(float) * p.fs.floats > lds_max) return p;
-  p.nt = std::max(64, ((bs / 4 + 63) / 64) * 64);
+  p.nt = frame_threads(bs);
   // few frames (far fewer workgroups than CUs): split each frame's harmonics over G thread groups
   p.G = split_allowed && batch * frames < 512 ? std::max(1, std::min(4, 256 / p.nt)) : 1;
   if (sizeof(float) * (p.fs.floats + (size_t)bs) > lds_max) p.G = 1;
+  // (the realtime stream's kernel has no fixed form: its launches are few frames, latency-bound)
+  p.fixed = p.G == 1 && n_bands == FixedShape::NB && bs == FixedShape::bs;
   p.shm = sizeof(float) * (p.fs.floats + (p.G > 1 ? (size_t)bs : 0));
   p.grid = dim3((unsigned)frames, (unsigned)batch);
   p.block = dim3((unsigned)(p.nt * p.G));
@@ -574,6 +634,15 @@ int ddsp_hip_synth_frames_supported(int64_t batch, int64_t n_harmonic, int64_t n
   return frame_plan(batch, 1, n_harmonic, n_bands, block_size, true).status == DDSP_HIP_OK;
 }
 
+int ddsp_hip_synth_frames_route(int64_t batch, int64_t frames, int64_t n_harmonic, int64_t n_bands,
+                                int64_t block_size, int with_prefix, int* route) {
+  if (!route || frame_sizes_invalid(batch, frames, n_harmonic, n_bands, block_size)) return DDSP_HIP_EINVAL;
+  const FramePlan p = frame_plan(batch, frames, n_harmonic, n_bands, block_size, !with_prefix);  // as the launch asks
+  if (p.status != DDSP_HIP_OK) return p.status;
+  *route = p.G > 1 ? DDSP_HIP_SYNTH_ROUTE_SPLIT : p.fixed ? DDSP_HIP_SYNTH_ROUTE_FIXED : DDSP_HIP_SYNTH_ROUTE_ANY;
+  return DDSP_HIP_OK;
+}
+
 static int synth_frames_launch(const float* f0, const float* param, const float* raw_magnitudes, float bias,
                                const float* noise, uint64_t seed, uint64_t offset, uint64_t* counter, float* out,
                                float* harmonic_out, float* noise_out, float* controls_out, int64_t batch, int64_t frames,
@@ -590,12 +659,14 @@ static int synth_frames_launch(const float* f0, const float* param, const float*
   const uint32_t o0 = (uint32_t)offset, o1 = (uint32_t)(offset >> 32);
 #define DDSP_SYNTH_FRAME_LAUNCH(RNG_, CTRL_)                                                               \
   do {                                                                                                   \
-    if (p.G > 1) DDSP_SYNTH_FRAME_LAUNCH_(RNG_, true, CTRL_, false);                                       \
-    else if (prefix) DDSP_SYNTH_FRAME_LAUNCH_(RNG_, false, CTRL_, true);                                   \
-    else DDSP_SYNTH_FRAME_LAUNCH_(RNG_, false, CTRL_, false);                                              \
+    if (p.G > 1) DDSP_SYNTH_FRAME_LAUNCH_((synth_frame_kernel<RNG_, true, CTRL_, false>), RNG_);            \
+    else if (p.fixed && prefix) DDSP_SYNTH_FRAME_LAUNCH_((synth_frame_kernel<RNG_, false, CTRL_, true>), RNG_);   \
+    else if (p.fixed) DDSP_SYNTH_FRAME_LAUNCH_((synth_frame_kernel<RNG_, false, CTRL_, false>), RNG_);      \
+    else if (prefix) DDSP_SYNTH_FRAME_LAUNCH_((synth_frame_any_kernel<RNG_, CTRL_, true>), RNG_);           \
+    else DDSP_SYNTH_FRAME_LAUNCH_((synth_frame_any_kernel<RNG_, CTRL_, false>), RNG_);                      \
   } while (0)
-#define DDSP_SYNTH_FRAME_LAUNCH_(RNG_, SPLIT_, CTRL_, PREFIX_)                                             \
-  hipLaunchKernelGGL((synth_frame_kernel<RNG_, SPLIT_, CTRL_, PREFIX_>), p.grid, p.block, p.shm, S(stream), f0, param, \
+#define DDSP_SYNTH_FRAME_LAUNCH_(KERNEL_, RNG_)                                                            \
+  hipLaunchKernelGGL(KERNEL_, p.grid, p.block, p.shm, S(stream), f0, param,                                \
                      raw_magnitudes, bias, RNG_ ? nullptr : noise, k0, k1, o0, o1, RNG_ ? counter : nullptr, out,  \
                      harmonic_out, noise_out, controls_out, (int)frames, (int)n_harmonic, (int)n_bands,            \
                      (int)block_size, sample_rate, p.fs.lo_end, p.fs.tail_start, p.fs.pad, (int)param_ld,          \

@@ -147,6 +147,19 @@ int ddsp_hip_synth_frames(const float* f0, const float* param, const float* raw_
  * bind under these caps).  Host only: no device is needed or touched. */
 int ddsp_hip_synth_frames_supported(int64_t batch, int64_t n_harmonic, int64_t n_bands, int64_t block_size);
 
+/* Which form of the fused frame kernel a launch of ddsp_hip_synth_frames, _controls_prefix (with_prefix != 0 when
+ * it is given a frame_prefix) or _counter takes, from the same plan the launch follows: *route receives
+ *   DDSP_HIP_SYNTH_ROUTE_SPLIT  few frames (batch * frames < 512, no prefix): a frame's harmonics over several
+ *                               thread groups, any shape;
+ *   DDSP_HIP_SYNTH_ROUTE_FIXED  n_bands == 65 and block_size == 512, not split: the kernel compiled for that shape
+ *                               alone (any n_harmonic and leading dimensions; same bits as the other forms);
+ *   DDSP_HIP_SYNTH_ROUTE_ANY    every other shape of the envelope, four samples per thread.
+ * DDSP_HIP_EINVAL for sizes no frame entry point takes or a null route, DDSP_HIP_ERANGE outside the envelope
+ * (*route untouched).  Host only: no device is needed or touched. */
+enum ddsp_hip_synth_route { DDSP_HIP_SYNTH_ROUTE_ANY = 0, DDSP_HIP_SYNTH_ROUTE_SPLIT = 1, DDSP_HIP_SYNTH_ROUTE_FIXED = 2 };
+int ddsp_hip_synth_frames_route(int64_t batch, int64_t frames, int64_t n_harmonic, int64_t n_bands,
+                                int64_t block_size, int with_prefix, int* route);
+
 /* ddsp_hip_synth_frames that also writes the controls DDSPDecoder.forward returns
  * (decoder.py:127-135: output['harmonic_ctrls'], output['noise_ctrls']) into controls_out (nullable),
  * laid out as [amplitudes B*F | harmonic_distribution B*F*H | magnitudes B*F*NB]: amplitudes =

@@ -51,9 +51,11 @@ PROBES = {
                "      g_probe_stamps[3 * i + 2] = ((uint64_t)xcc << 32) | hw;\n"
                "    }\n"
                "  }\n}\n"),
-              ("template <bool RNG, bool SPLIT, bool CTRL, bool PREFIX>\n__global__",
+              ("template <bool RNG, bool SPLIT, bool CTRL, bool PREFIX, class Shape>\n__device__ __forceinline__ void "
+               "synth_frame_workgroup(",
                "constexpr uint64_t kProbeWG = 65536;\n__device__ uint64_t g_probe_stamps[3 * kProbeWG];\n"
-               "template <bool RNG, bool SPLIT, bool CTRL, bool PREFIX>\n__global__"),
+               "template <bool RNG, bool SPLIT, bool CTRL, bool PREFIX, class Shape>\n__device__ __forceinline__ void "
+               "synth_frame_workgroup("),
               ("int ddsp_hip_frame_phase_prefix(",
                "int ddsp_probe_occupancy(int threads, int64_t shm) {\n"
                "  int n = -1;\n"

@@ -13,7 +13,8 @@ SRC := ddsp_pytorch_amd/csrc/synth.hip ddsp_pytorch_amd/csrc/noise.hip ddsp_pyto
 HDR := include/ddsp_hip.h ddsp_pytorch_amd/csrc/common.h ddsp_pytorch_amd/csrc/upols.h ddsp_pytorch_amd/csrc/fft_radix.h \
        ddsp_pytorch_amd/csrc/noise_dsp.h ddsp_pytorch_amd/csrc/stream_state.h ddsp_pytorch_amd/csrc/stft_frames.h \
        ddsp_pytorch_amd/csrc/bf16x3.h ddsp_pytorch_amd/csrc/impulse.h \
-       ddsp_pytorch_amd/csrc/analysis_frames.h ddsp_pytorch_amd/csrc/analysis_bodies.h
+       ddsp_pytorch_amd/csrc/analysis_frames.h ddsp_pytorch_amd/csrc/analysis_bodies.h \
+       ddsp_pytorch_amd/csrc/harmonic_frame.h
 LIB := ddsp_pytorch_amd/lib/libddsp_hip.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Iinclude -Ibuild -Wall -Wno-unused-result
 # packed-fp32 SLP vectorisation measured 10% slower on the oscillator loop (VALU-bound)

@@ -17,12 +17,17 @@
 //
 // f0 is an input feature in the reference's training loop (train.py:84-99: batch['pitch']); these kernels
 // return no gradient for it.  Where a frame-rate f0 requires grad, pitch_grad.hip's two launches run beside them.
+//
+// Per frame the synthesis section has three kernels here: harmonic_vjp_kernel (on the frame set-up it shares with
+// the pitch gradient, harmonic_frame.h), noise_vjp_kernel for any shape and noise_vjp_wave_kernel for the
+// reference's; one host launcher for the harmonic kernel and one for the two noise kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 
 #include "common.h"
+#include "harmonic_frame.h"
 #include "noise_dsp.h"
 
 namespace ddsp {
@@ -92,382 +97,315 @@ __global__ void __launch_bounds__(256) controls_backward_kernel(
 }
 
 // ---------------------------------------------------------------------------------------
-// Per-frame backward of the synthesis section, one workgroup per (item, frame).
-//
-// Harmonic part (HMODE 1: frame controls amp[B,F], normalised dist[B,F,H] -> d_amp, d_dist;
-// HMODE 2: raw projection param[B,F,H+1] -> d_param): item (kq, s) of the ceil(H/4) x NS grid
-// sums g_t sin(w_t (k+1)) for the 4 harmonics k = 4kq..4kq+3 over segment s of the frame's
-// samples — one LDS read of the (w_t, g_t) pair feeds 4 sine chains, and all lanes of a wave read
-// the same pair (broadcast).
-//
-// Noise part (NOISE 1: injected noise, 2: Philox regenerated with the forward's counters;
-// RAW: magnitudes are the raw projection, scale_function(m + bias) differentiated too):
+// sine-loop placement padding per instantiation of harmonic_vjp_kernel (tools/loop_align.py)
+template <bool PARAMS>
+constexpr bool kBwdLoopPad = false;
+
+// The harmonic VJP of one frame, one workgroup per (item, frame), on harmonic_frame.h's set-up (phases 1 and 2).
+// PARAMS: raw projection param[B,F,H+1] -> d_param; else frame controls amp[B,F], normalised dist[B,F,H] ->
+// d_amp, d_dist.  Item (kq, s) of the ceil(H/4) x NS grid sums g_t sin(w_t (k+1)) for the 4 harmonics
+// k = 4kq..4kq+3 over segment s of the frame's samples — one LDS read of the (w_t, g_t) pair feeds 4 sine
+// chains, and all lanes of a wave read the same pair (broadcast).
+template <bool PARAMS>
+__global__ void __launch_bounds__(512) harmonic_vjp_kernel(
+    const float* __restrict__ f0, const float* __restrict__ grad, const float* __restrict__ param,
+    const float* __restrict__ amp, const float* __restrict__ dist, float* __restrict__ d_param,
+    float* __restrict__ d_amp, float* __restrict__ d_dist, int F, int H, int bs, float sr, int NS) {
+  extern __shared__ float smem[];
+  __shared__ double red[32];
+  __shared__ double red2[32];
+  __shared__ int fast_s;
+  const int tid = threadIdx.x, NT = blockDim.x;
+  // the strided fp64 phase sum (no prefix launch for the VJP); part: [NS * H] dA_k per segment
+  const HarmonicFrame fr =
+      harmonic_frame_setup<PARAMS>(smem, red, NS * H, f0, grad, param, amp, dist, nullptr, F, H, bs, sr, NS);
+  const float2* wg = fr.wg;
+  float* part = fr.own;
+  const float* uk = fr.uk;
+  const int SL = fr.SL;
+  if (tid == 0) {
+    const float w0 = (float)(fr.S0 + fr.dinc), w1 = (float)(fr.S0 + (double)bs * fr.dinc);
+    // The hardware sine's error is absolute (3.2e-7: reduce_rev's revolutions carry 3e-8 at |y| ~ 0.5, the odd
+    // multiples of pi), harmless against a gradient of the size of g.  When the frame's arguments k omega_t
+    // spread over few periods, its sines are a smooth function of (t, k) with only about H bs inc / pi
+    // independent directions, and the frame's whole gradient can cancel to a few percent of its terms:
+    // omega_t near a multiple of pi puts every k omega_t near one, or g is nearly orthogonal to the one or two
+    // directions.  That happened twice in 600 frames at bs = 4, H = 8, and the sine's error was 1.1e-5 of those
+    // frames' gradients (tests/test_gpu_vjp_shapes.py, case 8).  Frames whose arguments spread over less than
+    // 16 rad take the general loop below: its polynomial sine on the pi-reduced argument keeps its relative
+    // accuracy at the zero crossings.  (At bs = 512, H = 100 these are pitches below 2.4 Hz.)
+    const bool wide = (float)H * (float)bs * fabsf((float)fr.dinc) >= 16.0f;
+    fast_s = wide && fmaxf(fabsf(w0), fabsf(w1)) * (float)H < kFastArgLimit;
+  }
+  __syncthreads();
+
+  // ---- phase 3: dA_k = sum_t g_t sin(w_t (k+1)) ----
+  const int KQ = (H + kKPT - 1) / kKPT;
+  for (int item = tid; item < KQ * NS; item += NT) {
+    const int s = item / KQ, kq = item - s * KQ;
+    const int j0 = s * SL, j1 = min(j0 + SL, bs);
+    float kf[kKPT], acc[kKPT];
+#pragma unroll
+    for (int c = 0; c < kKPT; ++c) {
+      kf[c] = (float)(kKPT * kq + c + 1);
+      acc[c] = 0.0f;
+    }
+    if (fast_s) {
+      float acc2[kKPT];
+#pragma unroll
+      for (int c = 0; c < kKPT; ++c) acc2[c] = 0.0f;
+      // loop placement (tools/loop_align.py, pinned by tests/test_loop_align.py): the
+      // 8-byte instructions at odd dword addresses; the alignment point makes the placement
+      // independent of the code laid out before the loop, the s_nop flips it per instantiation
+      if constexpr (kBwdLoopPad<PARAMS>) asm volatile(".p2align 3\n s_nop 0");
+      else asm volatile(".p2align 3");
+      const float2* wq = wg + j0;
+      for (int i = 0; i < SL; i += 2) {  // two samples per iteration: 8 independent sine chains
+        const float2 p = wq[i], p1 = wq[i + 1];
+        // the 8 chains written stage by stage so the scheduler keeps them interleaved (ILP 8)
+        float y[2 * kKPT];
+#pragma unroll
+        for (int c = 0; c < kKPT; ++c) {
+          y[c] = reduce_rev(p.x * kf[c]);
+          y[kKPT + c] = reduce_rev(p1.x * kf[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < kKPT; ++c) {
+          acc[c] = fmaf(p.y, sin_rev(y[c]), acc[c]);
+          acc2[c] = fmaf(p1.y, sin_rev(y[kKPT + c]), acc2[c]);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < kKPT; ++c) acc[c] += acc2[c];
+    } else {
+      for (int j = j0; j < j1; ++j) {
+        const float2 p = wg[j];
+#pragma unroll
+        for (int c = 0; c < kKPT; ++c) {
+          const float x = p.x * kf[c];
+          acc[c] = fmaf(p.y, fabsf(x) < kFastArgLimit ? sin_poly(x) : sin_slow(x), acc[c]);
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kKPT; ++c)
+      if (kKPT * kq + c < H) part[s * H + kKPT * kq + c] = acc[c];
+  }
+
+  // ---- phase 4: reductions and outputs ----
+  __syncthreads();
+  double da_part = 0.0;
+  for (int k = tid; k < H; k += NT) {
+    float dA = part[k];
+    for (int s = 1; s < NS; ++s) dA += part[s * H + k];
+    part[k] = dA;
+    da_part += (double)dA * (double)uk[k];
+  }
+  const float da = (float)block_sum_double(da_part, red2);  // barrier: part[0..H) complete
+  if (PARAMS) {
+    float* dp = d_param + fr.frame * (H + 1);
+    for (int k = tid; k < H; k += NT) {
+      const float mask = (fr.pitch0 * (float)(k + 1)) < fr.half_sr ? kOnePlusEps : kEps;
+      const float dv = fr.a * (part[k] - da) / fr.norm;
+      dp[1 + k] = dv * mask * scale_fn_grad(fr.prow[1 + k]);
+    }
+    if (tid == 0) dp[0] = da * scale_fn_grad(fr.prow[0]);
+  } else {
+    for (int k = tid; k < H; k += NT) d_dist[fr.frame * H + k] = part[k] * fr.a;
+    if (tid == 0) d_amp[fr.frame] = da;
+  }
+}
+
+// The noise VJP of one frame (FilteredNoise's backward, modules.py:116-128) at any shape, one workgroup per
+// (item, frame).  NOISE 1: injected noise, 2: Philox regenerated with the forward's counters; RAW: magnitudes are
+// the raw projection, scale_function(m + bias) differentiated too.
 //   dh at the n filter taps by direct correlation of g with the frame's noise — register-blocked
 //   4 taps x 4 lags per step when n/2 % 4 == 0 and n <= bs (the long taps j < n/2 split into
 //   NSEG lag segments, the short wrapped taps one segment each, so the work is even), else one
 //   tap per item; then the transposed filter design, a cosine transform of the windowed tap
 //   gradients folded by the even symmetry of the IR (two threads per band) with the Nyquist band
 //   from an alternating block sum.
-// With both parts (the backward of ddsp_hip_synth_frames) the noise's short LDS phases run beside
-// other workgroups' sine loops, as in the fused forward.
-constexpr int kKPT = 4;  // harmonics per thread
-
-// sine-loop placement padding per instantiation (tools/loop_align.py)
-template <int HMODE, int NOISE>
-constexpr bool kBwdLoopPad = false;
-
-template <int HMODE, int NOISE, bool RAW>
-__global__ void __launch_bounds__(512) frame_backward_kernel(
-    const float* __restrict__ f0, const float* __restrict__ grad, const float* __restrict__ param,
-    const float* __restrict__ amp, const float* __restrict__ dist, float* __restrict__ d_param,
-    float* __restrict__ d_amp, float* __restrict__ d_dist, int F, int H, int bs, float sr, int NS,
-    const float* __restrict__ mags, const float* __restrict__ noise, uint32_t k0, uint32_t k1, uint32_t off0,
-    uint32_t off1, float bias, float* __restrict__ d_mags, int NB, int NSEG) {
+template <int NOISE, bool RAW>
+__global__ void __launch_bounds__(512) noise_vjp_kernel(
+    const float* __restrict__ grad, const float* __restrict__ mags, const float* __restrict__ noise, uint32_t k0,
+    uint32_t k1, uint32_t off0, uint32_t off1, float bias, float* __restrict__ d_mags, int F, int bs, int NB,
+    int NSEG) {
   extern __shared__ float smem[];
-  __shared__ double red[32];
-  __shared__ double red2[32];
-  __shared__ int fast_s;
-  constexpr bool HARM = HMODE != 0;
-  constexpr bool PARAMS = HMODE == 2;
-  // LDS layout (mirrored by frame_backward_lds_floats): xl and gl start 16-B aligned
-  // the NS sample segments are SL samples each (even, NS * SL >= bs; (omega, g) = 0 past bs adds exact
-  // zeros), so every thread's sine loop has the same scalar trip count: no per-lane exit masks (4 VALU per
-  // 8 sines before; 152 -> 146.5-147.7 us at config 2, same box, tools/ab_prof.sh bwd)
-  const int SL = ((bs + NS - 1) / NS + 1) & ~1, WGN = NS * SL;
-  const int hfl = HARM ? 2 * WGN + NS * H + H : 0;
-  // (omega_t, g_t) per sample
-  float2* wg = reinterpret_cast<float2*>(smem);  // [WGN]
-  float* part = smem + 2 * WGN;                  // [NS * H]
-  float* uk = part + NS * H;                     // [H] u_k (PARAMS: v_k first)
-  const int n = NOISE ? 2 * (NB - 1) : 0, half = n >> 1;
+  __shared__ double red[16];
+  // LDS layout (mirrored by noise_vjp_lds_floats): xl and gl start 16-B aligned
+  const int n = 2 * (NB - 1), half = n >> 1;
   const int qmax = min(n, bs);
-  const bool quads = NOISE && (half % 4 == 0) && n <= bs && (bs % 4 == 0);
+  const bool quads = (half % 4 == 0) && n <= bs && (bs % 4 == 0);
   // quads: segment rows n + 4 floats apart, so the rows of one wave's segments start on different banks
   // (48.1-48.2 -> 47.2-47.5 us for the noise VJP at config 2, same box)
   // (at least n: the cosine transform's [2][half] partial sums reuse npart, and NSEG * bs < n when n > bs)
   const int npart_len = max(NSEG * (quads ? n + 4 : qmax), n);
-  float* xl = smem + ((hfl + 3) & ~3);                              // [bs] noise
-  float* ct = xl + bs;                                               // [n] cos(2 pi q / n)
-  float* e = ct + n;                                                 // [n] windowed tap gradients
-  float* npart = e + n;                                              // [npart_len]
-  float* gl = smem + (((xl - smem) + bs + 2 * n + npart_len + 3) & ~3);  // [bs + 8] g, zero-padded
-  const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, NT = blockDim.x;
-  const int64_t frame = (int64_t)b * F + f;
+  float* xl = smem;                                           // [bs] noise
+  float* ct = xl + bs;                                        // [n] cos(2 pi q / n)
+  float* e = ct + n;                                          // [n] windowed tap gradients
+  float* npart = e + n;                                       // [npart_len]
+  float* gl = smem + ((bs + 2 * n + npart_len + 3) & ~3);     // [bs + 8] g, zero-padded
+  const int tid = threadIdx.x, NT = blockDim.x;
+  const int64_t frame = (int64_t)blockIdx.y * F + blockIdx.x;
   const float* gf = grad + frame * bs;
 
-  // ---- phase 1: loads ----
-  double part_s = 0.0, part_d = 0.0;
-  float pitch0 = 0.0f;
-  const float half_sr = sr * 0.5f;
-  const float* prow = PARAMS ? param + frame * (H + 1) : nullptr;
-  if (HARM) {
-    const float* f0b = f0 + (int64_t)b * F;
-    pitch0 = f0b[f];
-    for (int q = tid; q < f; q += NT) part_s += (double)bs * (double)phase_inc(f0b[q], sr);
-    for (int k = tid; k < H; k += NT) {
-      if (PARAMS) {
-        const float v = controls_value(prow[1 + k], pitch0, k, half_sr);
-        uk[k] = v;
-        part_d += (double)v;
-      } else {
-        uk[k] = dist[frame * H + k];
-      }
-    }
-    for (int j = tid; j < WGN; j += NT) wg[j].y = j < bs ? gf[j] : 0.0f;
-  }
-  if (NOISE) {
-    for (int j = tid; j < bs + 8; j += NT) gl[j] = j < bs ? gf[j] : 0.0f;
-    if (NOISE == 2) {
-      const int fquads = (bs + 3) >> 2;
-      for (int t = tid; t < fquads; t += NT) {
-        const uint64_t qc = (uint64_t)frame * (uint64_t)fquads + (uint64_t)t;
-        const Philox4 r = philox4x32_10((uint32_t)qc, (uint32_t)(qc >> 32), off0, off1, k0, k1);
+  // ---- loads ----
+  for (int j = tid; j < bs + 8; j += NT) gl[j] = j < bs ? gf[j] : 0.0f;
+  if (NOISE == 2) {
+    const int fquads = (bs + 3) >> 2;
+    for (int t = tid; t < fquads; t += NT) {
+      const uint64_t qc = (uint64_t)frame * (uint64_t)fquads + (uint64_t)t;
+      const Philox4 r = philox4x32_10((uint32_t)qc, (uint32_t)(qc >> 32), off0, off1, k0, k1);
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (4 * t + c < bs) xl[4 * t + c] = uniform_pm1(r.v[c]);
-      }
-    } else {
-      const float* xf = noise + frame * bs;
-      for (int j = tid; j < bs; j += NT) xl[j] = xf[j];
+      for (int c = 0; c < 4; ++c)
+        if (4 * t + c < bs) xl[4 * t + c] = uniform_pm1(r.v[c]);
     }
-    fill_cos_table(ct, n);
+  } else {
+    const float* xf = noise + frame * bs;
+    for (int j = tid; j < bs; j += NT) xl[j] = xf[j];
   }
-  if (HARM) block_sum_double2(part_s, part_d, red);  // (the noise part needs only the barrier below)
+  fill_cos_table(ct, n);
+  __syncthreads();
 
-  // ---- phase 2: phases, normalised distribution ----
-  const double S0 = part_s;
-  const float norm = (float)part_d;
-  float a = 0.0f;
-  if (HARM) {
-    const double dinc = (double)phase_inc(pitch0, sr);
-    for (int j = tid; j < WGN; j += NT) wg[j].x = j < bs ? (float)(S0 + (double)(j + 1) * dinc) : 0.0f;
-    a = PARAMS ? scale_fn(prow[0]) : amp[frame];
-    if (PARAMS)
-      for (int k = tid; k < H; k += NT) uk[k] = uk[k] / norm;
-    if (tid == 0) {
-      const float w0 = (float)(S0 + dinc), w1 = (float)(S0 + (double)bs * dinc);
-      // The hardware sine's error is absolute (3.2e-7: reduce_rev's revolutions carry 3e-8 at |y| ~ 0.5, the odd
-      // multiples of pi), harmless against a gradient of the size of g.  When the frame's arguments k omega_t
-      // spread over few periods, its sines are a smooth function of (t, k) with only about H bs inc / pi
-      // independent directions, and the frame's whole gradient can cancel to a few percent of its terms:
-      // omega_t near a multiple of pi puts every k omega_t near one, or g is nearly orthogonal to the one or two
-      // directions.  That happened twice in 600 frames at bs = 4, H = 8, and the sine's error was 1.1e-5 of those
-      // frames' gradients (tests/test_gpu_vjp_shapes.py, case 8).  Frames whose arguments spread over less than
-      // 16 rad take the general loop below: its polynomial sine on the pi-reduced argument keeps its relative
-      // accuracy at the zero crossings.  (At bs = 512, H = 100 these are pitches below 2.4 Hz.)
-      const bool wide = (float)H * (float)bs * fabsf((float)dinc) >= 16.0f;
-      fast_s = wide && fmaxf(fabsf(w0), fabsf(w1)) * (float)H < kFastArgLimit;
+  // ---- dh[j(q)] = sum_d g[j+d] x[d] ----
+  if (quads) {
+    const int nqh = n >> 3;  // quads per half: long (q >= n/2, taps j < n/2) and short
+    const int seglen = ((bs + NSEG - 1) / NSEG + 3) & ~3;
+    for (int item = tid; item < nqh * NSEG + nqh; item += NT) {
+      int q0, j0, d0, d1, seg;
+      if (item < nqh * NSEG) {  // long taps: lag range [0, bs - j0) in NSEG segments
+        seg = item / nqh;
+        q0 = half + 4 * (item - seg * nqh);
+        j0 = q0 - half;
+        d0 = seg * seglen;
+        d1 = min(d0 + seglen, bs - j0);
+      } else {  // short (wrapped) taps j0 >= bs - n/2: one segment
+        seg = 0;
+        q0 = 4 * (item - nqh * NSEG);
+        j0 = q0 - half + bs;
+        d0 = 0;
+        d1 = bs - j0;
+      }
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (d0 < d1) {
+        float4 gc = *reinterpret_cast<const float4*>(gl + j0 + d0);
+        int d = d0;
+        // 8 lags per iteration with the g window ping-ponged between two registers sets (no window
+        // moves) and a second accumulator set (8 independent FMA chains), summed at the end
+        float4 acc2 = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (; d + 8 <= d1; d += 8) {
+          const float4 xv = *reinterpret_cast<const float4*>(xl + d);
+          const float4 xw = *reinterpret_cast<const float4*>(xl + d + 4);
+          const float4 gn = *reinterpret_cast<const float4*>(gl + j0 + d + 4);
+          const float4 gm = *reinterpret_cast<const float4*>(gl + j0 + d + 8);
+          acc.x = fmaf(gc.x, xv.x, fmaf(gc.y, xv.y, fmaf(gc.z, xv.z, fmaf(gc.w, xv.w, acc.x))));
+          acc.y = fmaf(gc.y, xv.x, fmaf(gc.z, xv.y, fmaf(gc.w, xv.z, fmaf(gn.x, xv.w, acc.y))));
+          acc.z = fmaf(gc.z, xv.x, fmaf(gc.w, xv.y, fmaf(gn.x, xv.z, fmaf(gn.y, xv.w, acc.z))));
+          acc.w = fmaf(gc.w, xv.x, fmaf(gn.x, xv.y, fmaf(gn.y, xv.z, fmaf(gn.z, xv.w, acc.w))));
+          acc2.x = fmaf(gn.x, xw.x, fmaf(gn.y, xw.y, fmaf(gn.z, xw.z, fmaf(gn.w, xw.w, acc2.x))));
+          acc2.y = fmaf(gn.y, xw.x, fmaf(gn.z, xw.y, fmaf(gn.w, xw.z, fmaf(gm.x, xw.w, acc2.y))));
+          acc2.z = fmaf(gn.z, xw.x, fmaf(gn.w, xw.y, fmaf(gm.x, xw.z, fmaf(gm.y, xw.w, acc2.z))));
+          acc2.w = fmaf(gn.w, xw.x, fmaf(gm.x, xw.y, fmaf(gm.y, xw.z, fmaf(gm.z, xw.w, acc2.w))));
+          gc = gm;
+        }
+        for (; d + 4 <= d1; d += 4) {
+          const float4 xv = *reinterpret_cast<const float4*>(xl + d);
+          const float4 gn = *reinterpret_cast<const float4*>(gl + j0 + d + 4);
+          acc.x = fmaf(gc.x, xv.x, fmaf(gc.y, xv.y, fmaf(gc.z, xv.z, fmaf(gc.w, xv.w, acc.x))));
+          acc.y = fmaf(gc.y, xv.x, fmaf(gc.z, xv.y, fmaf(gc.w, xv.z, fmaf(gn.x, xv.w, acc.y))));
+          acc.z = fmaf(gc.z, xv.x, fmaf(gc.w, xv.y, fmaf(gn.x, xv.z, fmaf(gn.y, xv.w, acc.z))));
+          acc.w = fmaf(gc.w, xv.x, fmaf(gn.x, xv.y, fmaf(gn.y, xv.z, fmaf(gn.z, xv.w, acc.w))));
+          gc = gn;
+        }
+        acc.x += acc2.x;
+        acc.y += acc2.y;
+        acc.z += acc2.z;
+        acc.w += acc2.w;
+        for (; d < d1; ++d) {  // g is zero past bs, so taps c > 0 need no separate bound
+          const float xv = xl[d];
+          acc.x = fmaf(gl[j0 + d], xv, acc.x);
+          acc.y = fmaf(gl[j0 + d + 1], xv, acc.y);
+          acc.z = fmaf(gl[j0 + d + 2], xv, acc.z);
+          acc.w = fmaf(gl[j0 + d + 3], xv, acc.w);
+        }
+      }
+      float* dst = npart + seg * (n + 4) + q0;
+      dst[0] = acc.x;
+      dst[1] = acc.y;
+      dst[2] = acc.z;
+      dst[3] = acc.w;
+    }
+  } else {
+    for (int item = tid; item < qmax * NSEG; item += NT) {
+      const int seg = item / qmax, q = item - seg * qmax;
+      int j = (q - half) % bs;
+      if (j < 0) j += bs;
+      const int d0 = (int)((int64_t)seg * bs / NSEG);
+      const int d1 = min((int)((int64_t)(seg + 1) * bs / NSEG), bs - j);
+      float c0 = 0.0f, c1 = 0.0f;
+      int d = d0;
+      for (; d + 1 < d1; d += 2) {
+        c0 = fmaf(gl[j + d], xl[d], c0);
+        c1 = fmaf(gl[j + d + 1], xl[d + 1], c1);
+      }
+      if (d < d1) c0 = fmaf(gl[j + d], xl[d], c0);
+      npart[seg * qmax + q] = c0 + c1;
     }
   }
   __syncthreads();
-
-  // Roles: with both parts the last wave does the noise VJP while the others run the sine
-  // loops (wave specialisation: the noise wave's LDS latency hides under the sine waves' VALU
-  // work); otherwise every thread works on the one part.
-  constexpr bool SPEC = HARM && NOISE != 0;
-  const int NTH = SPEC ? NT - 64 : NT;  // harmonic threads
-  const bool hthread = !SPEC || tid < NTH;
-  const int ntid = SPEC ? tid - NTH : tid, NTN = SPEC ? 64 : NT;  // noise thread id / count
-  const bool nthread = NOISE && (!SPEC || tid >= NTH);
-
-  // ---- phase 3a: harmonic dA_k = sum_t g_t sin(w_t (k+1)) ----
-  if (HARM && hthread) {
-    const int KQ = (H + kKPT - 1) / kKPT;
-    for (int item = tid; item < KQ * NS; item += NTH) {
-      const int s = item / KQ, kq = item - s * KQ;
-      const int j0 = s * SL, j1 = min(j0 + SL, bs);
-      float kf[kKPT], acc[kKPT];
-#pragma unroll
-      for (int c = 0; c < kKPT; ++c) {
-        kf[c] = (float)(kKPT * kq + c + 1);
-        acc[c] = 0.0f;
-      }
-      if (fast_s) {
-        float acc2[kKPT];
-#pragma unroll
-        for (int c = 0; c < kKPT; ++c) acc2[c] = 0.0f;
-        // loop placement (tools/loop_align.py, pinned by tests/test_loop_align.py): the
-        // 8-byte instructions at odd dword addresses; the alignment point makes the placement
-        // independent of the code laid out before the loop, the s_nop flips it per instantiation
-        if constexpr (kBwdLoopPad<HMODE, NOISE>) asm volatile(".p2align 3\n s_nop 0");
-        else asm volatile(".p2align 3");
-        const float2* wq = wg + j0;
-        for (int i = 0; i < SL; i += 2) {  // two samples per iteration: 8 independent sine chains
-          const float2 p = wq[i], p1 = wq[i + 1];
-          // the 8 chains written stage by stage so the scheduler keeps them interleaved (ILP 8)
-          float y[2 * kKPT];
-#pragma unroll
-          for (int c = 0; c < kKPT; ++c) {
-            y[c] = reduce_rev(p.x * kf[c]);
-            y[kKPT + c] = reduce_rev(p1.x * kf[c]);
-          }
-#pragma unroll
-          for (int c = 0; c < kKPT; ++c) {
-            acc[c] = fmaf(p.y, sin_rev(y[c]), acc[c]);
-            acc2[c] = fmaf(p1.y, sin_rev(y[kKPT + c]), acc2[c]);
-          }
-        }
-#pragma unroll
-        for (int c = 0; c < kKPT; ++c) acc[c] += acc2[c];
+  // ---- e[q] = dh[j(q)] hann[q]; the alternating sum for the Nyquist band ----
+  double alt_part = 0.0;
+  for (int q = tid; q < n; q += NT) {
+    float v = 0.0f;
+    if (q < qmax) {
+      if (quads) {
+        const int ns_q = q >= half ? NSEG : 1;
+        for (int s = 0; s < ns_q; ++s) v += npart[s * (n + 4) + q];
       } else {
-        for (int j = j0; j < j1; ++j) {
-          const float2 p = wg[j];
-#pragma unroll
-          for (int c = 0; c < kKPT; ++c) {
-            const float x = p.x * kf[c];
-            acc[c] = fmaf(p.y, fabsf(x) < kFastArgLimit ? sin_poly(x) : sin_slow(x), acc[c]);
-          }
-        }
+        for (int s = 0; s < NSEG; ++s) v += npart[s * qmax + q];
       }
-#pragma unroll
-      for (int c = 0; c < kKPT; ++c)
-        if (kKPT * kq + c < H) part[s * H + kKPT * kq + c] = acc[c];
+      v *= 0.5f - 0.5f * ct[q];  // periodic Hann(n) at q
     }
+    e[q] = v;
+    alt_part += (q & 1) ? -(double)v : (double)v;
   }
-
-  // ---- phase 3b: the noise VJP (all of it on the noise threads) ----
-  float alt = 0.0f;  // sum_q (-1)^q e[q]  (the Nyquist band)
-  if (nthread) {
-    // local barrier of the noise threads: one wave (LDS is in order per wave) or the workgroup
-    auto nsync = [&]() {
-      if (SPEC) {
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-      } else {
-        __syncthreads();
+  // sum_q (-1)^q e[q]; its barriers publish e[] and end the reads of npart
+  const float alt = (float)block_sum_double(alt_part, red);
+  // ---- dA_k = (c_k/n)(-1)^k [e0 + (-1)^k e_half + sum_{q=1}^{half-1} (e_q + e_{n-q}) cos(2 pi q k/n)],
+  // k < half on two threads (q halves) each; k = half from the alternating sum ----
+  float* dAp = npart;  // [2][half] (npart is consumed)
+  const int mid = (half + 1) >> 1;
+  const bool pow2 = (n & (n - 1)) == 0;
+  for (int item = tid; item < 2 * half; item += NT) {
+    const int pr = item / half, k = item - pr * half;
+    const int q0 = pr ? mid : 1, q1 = pr ? half : mid;
+    float s0 = 0.0f, s1 = 0.0f;
+    if (pow2) {
+      const int mask = n - 1;
+      int q = q0;
+      for (; q + 1 < q1; q += 2) {
+        s0 = fmaf(e[q] + e[n - q], ct[(q * k) & mask], s0);
+        s1 = fmaf(e[q + 1] + e[n - q - 1], ct[((q + 1) * k) & mask], s1);
       }
-    };
-    // dh[j(q)] = sum_d g[j+d] x[d]
-    if (quads) {
-      const int nqh = n >> 3;  // quads per half: long (q >= n/2, taps j < n/2) and short
-      const int seglen = ((bs + NSEG - 1) / NSEG + 3) & ~3;
-      for (int item = ntid; item < nqh * NSEG + nqh; item += NTN) {
-        int q0, j0, d0, d1, seg;
-        if (item < nqh * NSEG) {  // long taps: lag range [0, bs - j0) in NSEG segments
-          seg = item / nqh;
-          q0 = half + 4 * (item - seg * nqh);
-          j0 = q0 - half;
-          d0 = seg * seglen;
-          d1 = min(d0 + seglen, bs - j0);
-        } else {  // short (wrapped) taps j0 >= bs - n/2: one segment
-          seg = 0;
-          q0 = 4 * (item - nqh * NSEG);
-          j0 = q0 - half + bs;
-          d0 = 0;
-          d1 = bs - j0;
-        }
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (d0 < d1) {
-          float4 gc = *reinterpret_cast<const float4*>(gl + j0 + d0);
-          int d = d0;
-          // 8 lags per iteration with the g window ping-ponged between two registers sets (no window
-          // moves) and a second accumulator set (8 independent FMA chains), summed at the end
-          float4 acc2 = make_float4(0.f, 0.f, 0.f, 0.f);
-          for (; d + 8 <= d1; d += 8) {
-            const float4 xv = *reinterpret_cast<const float4*>(xl + d);
-            const float4 xw = *reinterpret_cast<const float4*>(xl + d + 4);
-            const float4 gn = *reinterpret_cast<const float4*>(gl + j0 + d + 4);
-            const float4 gm = *reinterpret_cast<const float4*>(gl + j0 + d + 8);
-            acc.x = fmaf(gc.x, xv.x, fmaf(gc.y, xv.y, fmaf(gc.z, xv.z, fmaf(gc.w, xv.w, acc.x))));
-            acc.y = fmaf(gc.y, xv.x, fmaf(gc.z, xv.y, fmaf(gc.w, xv.z, fmaf(gn.x, xv.w, acc.y))));
-            acc.z = fmaf(gc.z, xv.x, fmaf(gc.w, xv.y, fmaf(gn.x, xv.z, fmaf(gn.y, xv.w, acc.z))));
-            acc.w = fmaf(gc.w, xv.x, fmaf(gn.x, xv.y, fmaf(gn.y, xv.z, fmaf(gn.z, xv.w, acc.w))));
-            acc2.x = fmaf(gn.x, xw.x, fmaf(gn.y, xw.y, fmaf(gn.z, xw.z, fmaf(gn.w, xw.w, acc2.x))));
-            acc2.y = fmaf(gn.y, xw.x, fmaf(gn.z, xw.y, fmaf(gn.w, xw.z, fmaf(gm.x, xw.w, acc2.y))));
-            acc2.z = fmaf(gn.z, xw.x, fmaf(gn.w, xw.y, fmaf(gm.x, xw.z, fmaf(gm.y, xw.w, acc2.z))));
-            acc2.w = fmaf(gn.w, xw.x, fmaf(gm.x, xw.y, fmaf(gm.y, xw.z, fmaf(gm.z, xw.w, acc2.w))));
-            gc = gm;
-          }
-          for (; d + 4 <= d1; d += 4) {
-            const float4 xv = *reinterpret_cast<const float4*>(xl + d);
-            const float4 gn = *reinterpret_cast<const float4*>(gl + j0 + d + 4);
-            acc.x = fmaf(gc.x, xv.x, fmaf(gc.y, xv.y, fmaf(gc.z, xv.z, fmaf(gc.w, xv.w, acc.x))));
-            acc.y = fmaf(gc.y, xv.x, fmaf(gc.z, xv.y, fmaf(gc.w, xv.z, fmaf(gn.x, xv.w, acc.y))));
-            acc.z = fmaf(gc.z, xv.x, fmaf(gc.w, xv.y, fmaf(gn.x, xv.z, fmaf(gn.y, xv.w, acc.z))));
-            acc.w = fmaf(gc.w, xv.x, fmaf(gn.x, xv.y, fmaf(gn.y, xv.z, fmaf(gn.z, xv.w, acc.w))));
-            gc = gn;
-          }
-          acc.x += acc2.x;
-          acc.y += acc2.y;
-          acc.z += acc2.z;
-          acc.w += acc2.w;
-          for (; d < d1; ++d) {  // g is zero past bs, so taps c > 0 need no separate bound
-            const float xv = xl[d];
-            acc.x = fmaf(gl[j0 + d], xv, acc.x);
-            acc.y = fmaf(gl[j0 + d + 1], xv, acc.y);
-            acc.z = fmaf(gl[j0 + d + 2], xv, acc.z);
-            acc.w = fmaf(gl[j0 + d + 3], xv, acc.w);
-          }
-        }
-        float* dst = npart + seg * (n + 4) + q0;
-        dst[0] = acc.x;
-        dst[1] = acc.y;
-        dst[2] = acc.z;
-        dst[3] = acc.w;
-      }
+      if (q < q1) s0 = fmaf(e[q] + e[n - q], ct[(q * k) & mask], s0);
     } else {
-      for (int item = ntid; item < qmax * NSEG; item += NTN) {
-        const int seg = item / qmax, q = item - seg * qmax;
-        int j = (q - half) % bs;
-        if (j < 0) j += bs;
-        const int d0 = (int)((int64_t)seg * bs / NSEG);
-        const int d1 = min((int)((int64_t)(seg + 1) * bs / NSEG), bs - j);
-        float c0 = 0.0f, c1 = 0.0f;
-        int d = d0;
-        for (; d + 1 < d1; d += 2) {
-          c0 = fmaf(gl[j + d], xl[d], c0);
-          c1 = fmaf(gl[j + d + 1], xl[d + 1], c1);
-        }
-        if (d < d1) c0 = fmaf(gl[j + d], xl[d], c0);
-        npart[seg * qmax + q] = c0 + c1;
+      int qk = (int)(((int64_t)q0 * k) % n);
+      for (int q = q0; q < q1; ++q) {
+        s0 = fmaf(e[q] + e[n - q], ct[qk], s0);
+        qk += k;
+        if (qk >= n) qk -= n;
       }
     }
-    nsync();
-    // e[q] = dh[j(q)] hann[q]; the alternating sum for the Nyquist band
-    double alt_part = 0.0;
-    for (int q = ntid; q < n; q += NTN) {
-      float v = 0.0f;
-      if (q < qmax) {
-        if (quads) {
-          const int ns_q = q >= half ? NSEG : 1;
-          for (int s = 0; s < ns_q; ++s) v += npart[s * (n + 4) + q];
-        } else {
-          for (int s = 0; s < NSEG; ++s) v += npart[s * qmax + q];
-        }
-        v *= 0.5f - 0.5f * ct[q];  // periodic Hann(n) at q
-      }
-      e[q] = v;
-      alt_part += (q & 1) ? -(double)v : (double)v;
-    }
-    if (SPEC) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) alt_part += __shfl_xor(alt_part, o, 64);
-    } else {
-      alt_part = block_sum_double(alt_part, red2);  // includes the barrier publishing e[]
-    }
-    alt = (float)alt_part;
-    nsync();
-    // dA_k = (c_k/n)(-1)^k [e0 + (-1)^k e_half + sum_{q=1}^{half-1} (e_q + e_{n-q}) cos(2 pi q k/n)],
-    // k < half on two threads (q halves) each; k = half from the alternating sum.
-    float* dAp = npart;  // [2][half] (npart is consumed)
-    const int mid = (half + 1) >> 1;
-    const bool pow2 = (n & (n - 1)) == 0;
-    for (int item = ntid; item < 2 * half; item += NTN) {
-      const int pr = item / half, k = item - pr * half;
-      const int q0 = pr ? mid : 1, q1 = pr ? half : mid;
-      float s0 = 0.0f, s1 = 0.0f;
-      if (pow2) {
-        const int mask = n - 1;
-        int q = q0;
-        for (; q + 1 < q1; q += 2) {
-          s0 = fmaf(e[q] + e[n - q], ct[(q * k) & mask], s0);
-          s1 = fmaf(e[q + 1] + e[n - q - 1], ct[((q + 1) * k) & mask], s1);
-        }
-        if (q < q1) s0 = fmaf(e[q] + e[n - q], ct[(q * k) & mask], s0);
-      } else {
-        int qk = (int)(((int64_t)q0 * k) % n);
-        for (int q = q0; q < q1; ++q) {
-          s0 = fmaf(e[q] + e[n - q], ct[qk], s0);
-          qk += k;
-          if (qk >= n) qk -= n;
-        }
-      }
-      float v = s0 + s1;
-      if (pr == 0) v += e[0] + ((k & 1) ? -e[half] : e[half]);
-      dAp[pr * half + k] = v;
-    }
-    nsync();
-    const float inv_n = 1.0f / (float)n;
-    for (int k = ntid; k < NB; k += NTN) {
-      float dA = k < half ? (dAp[k] + dAp[half + k]) * (k == 0 ? 1.0f : 2.0f) * inv_n : alt * inv_n;
-      if (k & 1) dA = -dA;
-      d_mags[frame * NB + k] = RAW ? dA * scale_fn_grad(mags[frame * NB + k] + bias) : dA;
-    }
+    float v = s0 + s1;
+    if (pr == 0) v += e[0] + ((k & 1) ? -e[half] : e[half]);
+    dAp[pr * half + k] = v;
   }
-
-  if (HARM) {
-    // ---- phase 4: harmonic reductions and outputs ----
-    __syncthreads();
-    double da_part = 0.0;
-    for (int k = tid; k < H; k += NT) {
-      float dA = part[k];
-      for (int s = 1; s < NS; ++s) dA += part[s * H + k];
-      part[k] = dA;
-      da_part += (double)dA * (double)uk[k];
-    }
-    const float da = (float)block_sum_double(da_part, red2);  // barrier: part[0..H) complete
-    if (PARAMS) {
-      float* dp = d_param + frame * (H + 1);
-      for (int k = tid; k < H; k += NT) {
-        const float mask = (pitch0 * (float)(k + 1)) < half_sr ? kOnePlusEps : kEps;
-        const float dv = a * (part[k] - da) / norm;
-        dp[1 + k] = dv * mask * scale_fn_grad(prow[1 + k]);
-      }
-      if (tid == 0) dp[0] = da * scale_fn_grad(prow[0]);
-    } else {
-      for (int k = tid; k < H; k += NT) d_dist[frame * H + k] = part[k] * a;
-      if (tid == 0) d_amp[frame] = da;
-    }
+  __syncthreads();
+  const float inv_n = 1.0f / (float)n;
+  for (int k = tid; k < NB; k += NT) {
+    float dA = k < half ? (dAp[k] + dAp[half + k]) * (k == 0 ? 1.0f : 2.0f) * inv_n : alt * inv_n;
+    if (k & 1) dA = -dA;
+    d_mags[frame * NB + k] = RAW ? dA * scale_fn_grad(mags[frame * NB + k] + bias) : dA;
   }
 }
 
@@ -488,7 +426,7 @@ __global__ void __launch_bounds__(512) frame_backward_kernel(
 //   e[q] = dh[j(q)] hann[q] (q >= 64: j = q - 64; q < 64: j = q - 64 + bs), then
 //   dA_k = (c_k / n)(-1)^k [e_0 + (-1)^k e_64 + sum_{q=1}^{63} s_q cos(2 pi q k / n)] for k < 64 with the
 //   folded sums s_q = e_q + e_{n-q}, and the Nyquist band k = 64 from the alternating sum (as
-//   frame_backward_kernel).
+//   noise_vjp_kernel).
 constexpr int kNvjpWaves = 4;  // frames per workgroup
 __host__ __device__ constexpr int nvjp_gstride(int L) { return L + 76; }
 __host__ __device__ constexpr int nvjp_xstride(int L) { return L + 4; }
@@ -701,17 +639,13 @@ __global__ void __launch_bounds__(64 * kNvjpWaves) noise_vjp_wave_kernel(
   }
 }
 
-// LDS floats of frame_backward_kernel (its layout, written out on the host)
-size_t frame_backward_lds_floats(bool harm, bool noise, int H, int bs, int NS, int NB, int NSEG) {
-  const size_t SL = (size_t)(((bs + NS - 1) / NS + 1) & ~1);
-  const size_t hfl = harm ? (size_t)2 * NS * SL + (size_t)NS * H + H : 0;
-  if (!noise) return hfl;
+// LDS floats of noise_vjp_kernel (its layout, written out on the host)
+size_t noise_vjp_lds_floats(int bs, int NB, int NSEG) {
   const int n = 2 * (NB - 1);
   const int qmax = std::min(n, bs);
   const bool quads = ((n / 2) % 4 == 0) && n <= bs && bs % 4 == 0;
   const size_t npart_len = std::max((size_t)NSEG * (quads ? n + 4 : qmax), (size_t)n);
-  const size_t off_xl = (hfl + 3) & ~(size_t)3;
-  const size_t off_gl = (off_xl + (size_t)bs + 2 * (size_t)n + npart_len + 3) & ~(size_t)3;
+  const size_t off_gl = ((size_t)bs + 2 * (size_t)n + npart_len + 3) & ~(size_t)3;
   return off_gl + (size_t)bs + 8;
 }
 
@@ -796,16 +730,65 @@ unsigned grid1d(int64_t n, int per_block) {
   return (unsigned)std::min<int64_t>(std::max<int64_t>((n + per_block - 1) / per_block, 1), 1 << 20);
 }
 
-// Harmonic backward geometry: NS sample segments so that ceil(H/4) x NS fills about
-// kBwdThreads threads (small workgroups: several per CU hide each one's latency-bound phases).
-constexpr int kBwdThreads = 128;  // measured best at config 2 (64..512 swept)
-int bwd_threads() { return kBwdThreads; }
+constexpr size_t kMaxLdsBytes = 150 * 1024;
 
-void harmonic_backward_shape(int H, int bs, int& nt, int& ns) {
-  const int kq = (H + kKPT - 1) / kKPT;
-  const int target = bwd_threads();
-  ns = std::max(1, std::min(std::min(target / kq, bs), 64));
-  nt = std::min(512, ((kq * ns + 63) / 64) * 64);
+// harmonic_vjp_kernel: param != nullptr is the raw-projection form (-> d_param), else the frame-control form
+// (amp, dist -> d_amp, d_dist)
+int harmonic_vjp_launch(const float* f0, const float* grad, const float* param, const float* amp, const float* dist,
+                        float* d_param, float* d_amp, float* d_dist, int64_t batch, int64_t frames, int64_t H,
+                        int64_t bs, float sr, void* stream) {
+  if (batch < 0 || frames < 0 || bs < 1 || H < 1 || !(sr > 0)) return DDSP_HIP_EINVAL;
+  if (batch == 0 || frames == 0) return DDSP_HIP_OK;
+  if (batch > 65535 || frames > INT32_MAX || H > 4096 || bs > 8192) return DDSP_HIP_ERANGE;
+  int nt, ns;
+  harmonic_backward_shape((int)H, (int)bs, nt, ns);
+  const size_t shm = sizeof(float) * harmonic_frame_lds_floats((int)H, (int)bs, ns, (size_t)ns * H);
+  if (shm > kMaxLdsBytes) return DDSP_HIP_ERANGE;
+  const dim3 grid((unsigned)frames, (unsigned)batch);
+  if (param)
+    hipLaunchKernelGGL((harmonic_vjp_kernel<true>), grid, dim3(nt), shm, S(stream), f0, grad, param, amp, dist,
+                       d_param, d_amp, d_dist, (int)frames, (int)H, (int)bs, sr, ns);
+  else
+    hipLaunchKernelGGL((harmonic_vjp_kernel<false>), grid, dim3(nt), shm, S(stream), f0, grad, param, amp, dist,
+                       d_param, d_amp, d_dist, (int)frames, (int)H, (int)bs, sr, ns);
+  return launch_status();
+}
+
+// The noise VJP of batch * frames > 0 frames (sizes non-negative, NB >= 2, bs >= 1: the entry point's checks):
+// the wave kernel at the reference's shape, else noise_vjp_kernel.  noise != nullptr: injected, else Philox.
+int noise_vjp_launch(const float* mags, const float* noise, uint64_t seed, uint64_t offset, bool raw, float bias,
+                     const float* grad, float* d_mags, int64_t batch, int64_t frames, int64_t NB, int64_t bs,
+                     void* stream) {
+  if (batch > 65535 || frames > INT32_MAX || bs > 8192 || NB > 4097) return DDSP_HIP_ERANGE;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  const uint32_t o0 = (uint32_t)offset, o1 = (uint32_t)(offset >> 32);
+  // K_<NOISE, RAW> of the four instantiations
+#define DDSP_NOISE_LAUNCH(K_, GRID_, NT_, SHM_, ...)                                                             \
+  do {                                                                                                            \
+    if (noise && raw) hipLaunchKernelGGL((K_<1, true>), GRID_, dim3(NT_), SHM_, S(stream), __VA_ARGS__);         \
+    else if (noise) hipLaunchKernelGGL((K_<1, false>), GRID_, dim3(NT_), SHM_, S(stream), __VA_ARGS__);          \
+    else if (raw) hipLaunchKernelGGL((K_<2, true>), GRID_, dim3(NT_), SHM_, S(stream), __VA_ARGS__);             \
+    else hipLaunchKernelGGL((K_<2, false>), GRID_, dim3(NT_), SHM_, S(stream), __VA_ARGS__);                     \
+  } while (0)
+  // the reference's 65 bands: one wave per frame (noise_vjp_wave_kernel)
+  if (NB == 65 && bs % 128 == 0 && bs >= 512 && bs <= 1024 && ((uintptr_t)grad & 15) == 0 &&
+      (!noise || ((uintptr_t)noise & 15) == 0)) {
+    const int64_t rows = batch * frames;
+    const dim3 grid((unsigned)((rows + kNvjpWaves - 1) / kNvjpWaves));
+    const size_t shm = sizeof(float) * (128 + (size_t)kNvjpWaves * nvjp_wave_floats((int)bs));  // 29.7 KB at bs 512
+    DDSP_NOISE_LAUNCH(noise_vjp_wave_kernel, grid, 64 * kNvjpWaves, shm, grad, mags, noise, k0, k1, o0, o1, bias,
+                      d_mags, rows, (int)bs);
+    return launch_status();
+  }
+  // 128 threads per frame (config 2: 53.8 us; 64 threads 60.5, 256 threads 70.0)
+  const int nt = 128, nseg = noise_nseg(nt, (int)NB, (int)bs);
+  const size_t shm = sizeof(float) * noise_vjp_lds_floats((int)bs, (int)NB, nseg);
+  if (shm > kMaxLdsBytes) return DDSP_HIP_ERANGE;
+  const dim3 grid((unsigned)frames, (unsigned)batch);
+  DDSP_NOISE_LAUNCH(noise_vjp_kernel, grid, nt, shm, grad, mags, noise, k0, k1, o0, o1, bias, d_mags, (int)frames,
+                    (int)bs, (int)NB, nseg);
+#undef DDSP_NOISE_LAUNCH
+  return launch_status();
 }
 
 }  // namespace
@@ -853,69 +836,6 @@ int ddsp_hip_harmonic_controls_backward(const float* amplitudes_raw, int64_t amp
   return launch_status();
 }
 
-// hmode: 0 no harmonic part, 1 frame controls, 2 raw params; noise_mode: 0 none, 1 injected, 2 Philox
-static int frame_backward_launch(int hmode, int noise_mode, bool raw, const float* f0, const float* grad,
-                                 const float* param, const float* amp, const float* dist, float* d_param,
-                                 float* d_amp, float* d_dist, int64_t batch, int64_t frames, int64_t H,
-                                 int64_t bs, float sr, const float* mags, const float* noise, uint64_t seed,
-                                 uint64_t offset, float bias, float* d_mags, int64_t NB, void* stream) {
-  if (batch < 0 || frames < 0 || bs < 1 || (hmode && (H < 1 || !(sr > 0)))) return DDSP_HIP_EINVAL;
-  if (noise_mode && NB < 2) return DDSP_HIP_EINVAL;
-  if (batch == 0 || frames == 0) return DDSP_HIP_OK;
-  if (batch > 65535 || frames > INT32_MAX || H > 4096 || bs > 8192 || NB > 4097) return DDSP_HIP_ERANGE;
-  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  const uint32_t o0 = (uint32_t)offset, o1 = (uint32_t)(offset >> 32);
-  // noise alone at the reference's 65 bands: one wave per frame (noise_vjp_wave_kernel)
-  if (hmode == 0 && NB == 65 && bs % 128 == 0 && bs >= 512 && bs <= 1024 && ((uintptr_t)grad & 15) == 0 &&
-      (noise_mode == 2 || ((uintptr_t)noise & 15) == 0)) {
-    const int64_t rows = batch * frames;
-    const dim3 grid((unsigned)((rows + kNvjpWaves - 1) / kNvjpWaves));
-    const size_t shm = sizeof(float) * (128 + (size_t)kNvjpWaves * nvjp_wave_floats((int)bs));  // 29.7 KB at bs 512
-#define DDSP_NVJP_LAUNCH(N_, R_)                                                                                \
-  hipLaunchKernelGGL((noise_vjp_wave_kernel<N_, R_>), grid, dim3(64 * kNvjpWaves), shm, S(stream), grad, mags, \
-                     noise, k0, k1, o0, o1, bias, d_mags, rows, (int)bs)
-    if (noise_mode == 1) {
-      if (raw) DDSP_NVJP_LAUNCH(1, true); else DDSP_NVJP_LAUNCH(1, false);
-    } else {
-      if (raw) DDSP_NVJP_LAUNCH(2, true); else DDSP_NVJP_LAUNCH(2, false);
-    }
-#undef DDSP_NVJP_LAUNCH
-    return launch_status();
-  }
-  // noise alone: 128 threads per frame (config 2: 53.8 us; 64 threads 60.5, 256 threads 70.0)
-  int nt = 128, ns = 1;
-  if (hmode) harmonic_backward_shape((int)H, (int)bs, nt, ns);
-  // both parts: one extra wave runs the noise VJP beside the sine waves
-  const bool spec = hmode && noise_mode;
-  const int nseg = noise_mode ? noise_nseg(spec ? 64 : nt, (int)NB, (int)bs) : 0;
-  if (spec) nt += 64;
-  const size_t shm = sizeof(float) * frame_backward_lds_floats(hmode != 0, noise_mode != 0, (int)H, (int)bs, ns,
-                                                               (int)NB, nseg);
-  if (shm > 150 * 1024) return DDSP_HIP_ERANGE;
-  const dim3 grid((unsigned)frames, (unsigned)batch);
-#define DDSP_FB_LAUNCH(HM_, N_, R_)                                                                         \
-  hipLaunchKernelGGL((frame_backward_kernel<HM_, N_, R_>), grid, dim3(nt), shm, S(stream), f0, grad, param, amp, \
-                     dist, d_param, d_amp, d_dist, (int)frames, (int)H, (int)bs, sr, ns, mags, noise, k0, k1,  \
-                     o0, o1, bias, d_mags, (int)NB, nseg)
-  if (hmode == 1 && noise_mode == 0) {
-    DDSP_FB_LAUNCH(1, 0, false);
-  } else if (hmode == 2 && noise_mode == 0) {
-    DDSP_FB_LAUNCH(2, 0, false);
-  } else if (hmode == 2 && noise_mode == 1 && raw) {
-    DDSP_FB_LAUNCH(2, 1, true);
-  } else if (hmode == 2 && noise_mode == 2 && raw) {
-    DDSP_FB_LAUNCH(2, 2, true);
-  } else if (hmode == 0 && noise_mode == 1) {
-    if (raw) DDSP_FB_LAUNCH(0, 1, true); else DDSP_FB_LAUNCH(0, 1, false);
-  } else if (hmode == 0 && noise_mode == 2) {
-    if (raw) DDSP_FB_LAUNCH(0, 2, true); else DDSP_FB_LAUNCH(0, 2, false);
-  } else {
-    return DDSP_HIP_EINVAL;
-  }
-#undef DDSP_FB_LAUNCH
-  return launch_status();
-}
-
 int ddsp_hip_harmonic_synth_frames_backward(const float* f0, const float* amplitudes, const float* distribution,
                                             const float* grad, float* grad_amplitudes,
                                             float* grad_distribution, int64_t batch, int64_t frames,
@@ -923,9 +843,8 @@ int ddsp_hip_harmonic_synth_frames_backward(const float* f0, const float* amplit
                                             void* stream) {
   if (!f0 || !amplitudes || !distribution || !grad || !grad_amplitudes || !grad_distribution)
     return batch == 0 || frames == 0 ? DDSP_HIP_OK : DDSP_HIP_EINVAL;
-  return frame_backward_launch(1, 0, false, f0, grad, nullptr, amplitudes, distribution, nullptr, grad_amplitudes,
-                               grad_distribution, batch, frames, n_harmonic, block_size, sample_rate, nullptr,
-                               nullptr, 0, 0, 0.0f, nullptr, 0, stream);
+  return harmonic_vjp_launch(f0, grad, nullptr, amplitudes, distribution, nullptr, grad_amplitudes, grad_distribution,
+                             batch, frames, n_harmonic, block_size, sample_rate, stream);
 }
 
 int ddsp_hip_harmonic_synth_params_backward(const float* f0, const float* param, const float* grad,
@@ -933,9 +852,8 @@ int ddsp_hip_harmonic_synth_params_backward(const float* f0, const float* param,
                                             int64_t n_harmonic, int64_t block_size, float sample_rate,
                                             void* stream) {
   if (!f0 || !param || !grad || !grad_param) return batch == 0 || frames == 0 ? DDSP_HIP_OK : DDSP_HIP_EINVAL;
-  return frame_backward_launch(2, 0, false, f0, grad, param, nullptr, nullptr, grad_param, nullptr, nullptr, batch,
-                               frames, n_harmonic, block_size, sample_rate, nullptr, nullptr, 0, 0, 0.0f, nullptr, 0,
-                               stream);
+  return harmonic_vjp_launch(f0, grad, param, nullptr, nullptr, grad_param, nullptr, nullptr, batch, frames,
+                             n_harmonic, block_size, sample_rate, stream);
 }
 
 int ddsp_hip_synth_frames_backward(const float* f0, const float* param, const float* raw_magnitudes, float bias,
@@ -946,12 +864,11 @@ int ddsp_hip_synth_frames_backward(const float* f0, const float* param, const fl
   if (batch == 0 || frames == 0) return batch < 0 || frames < 0 ? DDSP_HIP_EINVAL : DDSP_HIP_OK;
   if (!f0 || !param || !raw_magnitudes || !grad_harmonic || !grad_param || !grad_magnitudes)
     return DDSP_HIP_EINVAL;
-  // The two halves as two launches on the stream: measured faster than the one-launch form whose
-  // extra wave ran the noise VJP beside the sine waves (config 2, tools/exp_bwd_split.py: 176.7 vs
-  // 187.6-190.3 us; the halves alone 130.4 and 47.9 us, on two streams 223 us).
-  int st = frame_backward_launch(2, 0, false, f0, grad_harmonic, param, nullptr, nullptr, grad_param, nullptr,
-                                 nullptr, batch, frames, n_harmonic, block_size, sample_rate, nullptr, nullptr, 0,
-                                 0, 0.0f, nullptr, 0, stream);
+  // The two halves as two launches on the stream: measured faster than a one-launch kernel whose
+  // extra wave ran the noise VJP beside the sine waves (config 2: 176.7 vs 187.6-190.3 us; the halves
+  // alone 130.4 and 47.9 us, on two streams 223 us).  That kernel was removed; it is in the git history.
+  int st = harmonic_vjp_launch(f0, grad_harmonic, param, nullptr, nullptr, grad_param, nullptr, nullptr, batch,
+                               frames, n_harmonic, block_size, sample_rate, stream);
   if (st) return st;
   return ddsp_hip_filtered_noise_backward(raw_magnitudes, noise, seed, offset, 1, bias,
                                           grad_noise ? grad_noise : grad_harmonic, grad_magnitudes, batch, frames,
@@ -965,9 +882,8 @@ int ddsp_hip_filtered_noise_backward(const float* magnitudes, const float* noise
   if (batch < 0 || frames < 0 || n_bands < 2 || block_size < 1) return DDSP_HIP_EINVAL;
   if (batch == 0 || frames == 0) return DDSP_HIP_OK;
   if (!grad || !grad_magnitudes || (raw && !magnitudes)) return DDSP_HIP_EINVAL;
-  return frame_backward_launch(0, noise ? 1 : 2, raw != 0, nullptr, grad, nullptr, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, batch, frames, 0, block_size, 0.0f, magnitudes, noise, seed, offset, bias,
-                               grad_magnitudes, n_bands, stream);
+  return noise_vjp_launch(magnitudes, noise, seed, offset, raw != 0, bias, grad, grad_magnitudes, batch, frames,
+                          n_bands, block_size, stream);
 }
 
 int ddsp_hip_amp_to_impulse_response_backward(const float* grad_impulse, float* grad_amp, int64_t rows,

@@ -8,8 +8,9 @@
 //   Q_f = sum_j q_{f,j},   R_f = sum_j (j+1) q_{f,j}
 //   dL/d f0_f = c (R_f + bs sum_{f'>f} Q_{f'})
 // The sums over (j, k) are swapped, C_k = sum_j g_j cos(.), C'_k = sum_j (j+1) g_j cos(.), so that
-// Q = sum_k k A_k C_k and R = sum_k k A_k C'_k: the loop shape of frame_backward_kernel's sine VJP (backward.hip),
-// one (omega, g) pair from LDS feeding several harmonic chains.
+// Q = sum_k k A_k C_k and R = sum_k k A_k C'_k: the loop shape of harmonic_vjp_kernel's sines (backward.hip), one
+// (omega, g) pair from LDS feeding several harmonic chains.  The frame's set-up (phase convention, table, segment
+// shape, controls) is the one of that kernel: harmonic_frame.h.
 //
 // Two launches: frame_pitch_grad_kernel writes (Q_f, R_f) as two doubles per frame, pitch_grad_scan_kernel makes
 // the exclusive reverse scan of Q over each item's frames and writes the gradient.  Past kPrefixMinFrames frames
@@ -23,14 +24,12 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "harmonic_frame.h"
 
 namespace ddsp {
 namespace {
 
-constexpr int kKPT = 4;               // harmonics per thread (as backward.hip)
-constexpr int kPgThreads = 128;       // ceil(H/4) x NS fills about this many threads (as backward.hip)
-constexpr int kScanChunk = 256;       // frames per step of the reverse scan (= its workgroup's threads)
-constexpr int kPrefixMinFrames = 512;  // core.FRAME_PREFIX_MIN_FRAMES: past it S0 is read, not summed
+constexpr int kScanChunk = 256;  // frames per step of the reverse scan (= its workgroup's threads)
 
 // cos(2 pi y) on the hardware cosine (v_cos_f32 takes revolutions, as v_sin_f32)
 __device__ __forceinline__ float cos_rev(float y) { return __builtin_amdgcn_cosf(y); }
@@ -38,11 +37,10 @@ __device__ __forceinline__ float cos_rev(float y) { return __builtin_amdgcn_cosf
 // arguments beyond kFastArgLimit: the fp64 cosine of the exact fp32 value, rounded (mirrors sin_slow)
 __device__ __noinline__ float cos_slow(float x) { return (float)cos((double)x); }
 
-// One workgroup per (item, frame): item (kq, s) of the ceil(H/4) x NS grid sums g_t cos(w_t k) and
-// (t+1) g_t cos(w_t k) for the 4 harmonics k = 4kq+1..4kq+4 over segment s of the frame's samples.  The NS
-// segments are SL samples each (even, NS * SL >= bs; (omega, g) = 0 past bs adds exact zeros).
-// PARAMS: A_k from the raw projection param[B,F,H+1] (controls_value, scale_fn, the norm), else from the frame
-// controls amp[B,F], normalised dist[B,F,H].  prefix (nullable): S0 per frame.
+// One workgroup per (item, frame), on harmonic_frame.h's set-up (phases 1 and 2): item (kq, s) of the ceil(H/4) x
+// NS grid sums g_t cos(w_t k) and (t+1) g_t cos(w_t k) for the 4 harmonics k = 4kq+1..4kq+4 over segment s of the
+// frame's samples.  PARAMS: A_k from the raw projection param[B,F,H+1], else from the frame controls amp[B,F],
+// normalised dist[B,F,H].  prefix (nullable): S0 per frame.
 template <bool PARAMS>
 __global__ void __launch_bounds__(512) frame_pitch_grad_kernel(
     const float* __restrict__ f0, const float* __restrict__ grad, const float* __restrict__ param,
@@ -51,44 +49,16 @@ __global__ void __launch_bounds__(512) frame_pitch_grad_kernel(
   extern __shared__ float smem[];
   __shared__ double red[32];
   __shared__ int fast_s;
-  // LDS layout (mirrored by pitch_grad_lds_floats)
-  const int SL = ((bs + NS - 1) / NS + 1) & ~1, WGN = NS * SL;
-  float2* wg = reinterpret_cast<float2*>(smem);  // [WGN] (omega_t, g_t)
-  float* partc = smem + 2 * WGN;                 // [NS * H] C_k per segment
-  float* partd = partc + NS * H;                 // [NS * H] C'_k per segment
-  float* uk = partd + NS * H;                    // [H] u_k (PARAMS: v_k first)
-  const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, NT = blockDim.x;
-  const int64_t frame = (int64_t)b * F + f;
-  const float* gf = grad + frame * bs;
-
-  // ---- phase 1: loads ----
-  double part_s = 0.0, part_d = 0.0;
-  const float half_sr = sr * 0.5f;
-  const float* prow = PARAMS ? param + frame * (H + 1) : nullptr;
-  const float* f0b = f0 + (int64_t)b * F;
-  const float pitch0 = f0b[f];
-  if (!prefix)
-    for (int q = tid; q < f; q += NT) part_s += (double)bs * (double)phase_inc(f0b[q], sr);
-  for (int k = tid; k < H; k += NT) {
-    if (PARAMS) {
-      const float v = controls_value(prow[1 + k], pitch0, k, half_sr);
-      uk[k] = v;
-      part_d += (double)v;
-    } else {
-      uk[k] = dist[frame * H + k];
-    }
-  }
-  for (int j = tid; j < WGN; j += NT) wg[j].y = j < bs ? gf[j] : 0.0f;
-  block_sum_double2(part_s, part_d, red);
-
-  // ---- phase 2: phases ----
-  const double S0 = prefix ? prefix[frame] : part_s;
-  const float norm = (float)part_d;
-  const double dinc = (double)phase_inc(pitch0, sr);
-  for (int j = tid; j < WGN; j += NT) wg[j].x = j < bs ? (float)(S0 + (double)(j + 1) * dinc) : 0.0f;
-  const float a = PARAMS ? scale_fn(prow[0]) : amp[frame];
+  const int tid = threadIdx.x, NT = blockDim.x;
+  const HarmonicFrame fr =
+      harmonic_frame_setup<PARAMS>(smem, red, 2 * NS * H, f0, grad, param, amp, dist, prefix, F, H, bs, sr, NS);
+  const float2* wg = fr.wg;
+  float* partc = fr.own;          // [NS * H] C_k per segment
+  float* partd = partc + NS * H;  // [NS * H] C'_k per segment
+  const float* uk = fr.uk;
+  const int SL = fr.SL;
   if (tid == 0) {
-    const float w0 = (float)(S0 + dinc), w1 = (float)(S0 + (double)bs * dinc);
+    const float w0 = (float)(fr.S0 + fr.dinc), w1 = (float)(fr.S0 + (double)bs * fr.dinc);
     fast_s = fmaxf(fabsf(w0), fabsf(w1)) * (float)H < kFastArgLimit;
   }
   __syncthreads();
@@ -168,15 +138,14 @@ __global__ void __launch_bounds__(512) frame_pitch_grad_kernel(
       ck += (double)partc[s * H + k];
       dk += (double)partd[s * H + k];
     }
-    const float u = PARAMS ? uk[k] / norm : uk[k];
-    const double w = (double)(k + 1) * ((double)a * (double)u);
+    const double w = (double)(k + 1) * ((double)fr.a * (double)uk[k]);
     q += w * ck;
     r += w * dk;
   }
   block_sum_double2(q, r, red);
   if (tid == 0) {
-    qr[2 * frame] = q;
-    qr[2 * frame + 1] = r;
+    qr[2 * fr.frame] = q;
+    qr[2 * fr.frame + 1] = r;
   }
 }
 
@@ -210,17 +179,6 @@ __global__ void __launch_bounds__(kScanChunk) pitch_grad_scan_kernel(const doubl
   }
 }
 
-size_t pitch_grad_lds_floats(int H, int bs, int NS) {
-  const size_t SL = (size_t)(((bs + NS - 1) / NS + 1) & ~1);
-  return (size_t)2 * NS * SL + (size_t)2 * NS * H + H;
-}
-
-void pitch_grad_shape(int H, int bs, int& nt, int& ns) {
-  const int kq = (H + kKPT - 1) / kKPT;
-  ns = std::max(1, std::min(std::min(kPgThreads / kq, bs), 64));
-  nt = std::min(512, ((kq * ns + 63) / 64) * 64);
-}
-
 size_t pitch_grad_ws_bytes(int64_t batch, int64_t frames) {
   if (batch <= 0 || frames <= 0) return 0;
   const size_t rows = (size_t)batch * (size_t)frames;
@@ -238,8 +196,8 @@ int pitch_grad_launch(const float* f0, const float* param, const float* amp, con
   if (!workspace || ((uintptr_t)workspace & 7)) return DDSP_HIP_EINVAL;
   if (workspace_bytes < pitch_grad_ws_bytes(batch, frames)) return DDSP_HIP_EWORKSPACE;
   int nt, ns;
-  pitch_grad_shape((int)H, (int)bs, nt, ns);
-  const size_t shm = sizeof(float) * pitch_grad_lds_floats((int)H, (int)bs, ns);
+  harmonic_backward_shape((int)H, (int)bs, nt, ns);
+  const size_t shm = sizeof(float) * harmonic_frame_lds_floats((int)H, (int)bs, ns, (size_t)2 * ns * H);
   if (shm > 150 * 1024) return DDSP_HIP_ERANGE;
   double* qr = static_cast<double*>(workspace);
   double* prefix = nullptr;

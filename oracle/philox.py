@@ -13,7 +13,7 @@ counter-based generator so that no host RNG or H2D copy sits in the synthesis st
   SC'11), multipliers 0xD2511F53 / 0xCD9E8D57, Weyl key increments 0x9E3779B9 / 0xBB67AE85,
   ten rounds — the published algorithm (known-answer vectors in tests/test_philox.py);
 * counter layout (ddsp_pytorch_amd/csrc/synth_frame.hip:71-76, noise.hip:96-103,
-  backward.hip:173-180): for frame index ``fr = b * F + f`` and sample quad ``t`` (samples
+  backward.hip:255-262): for frame index ``fr = b * F + f`` and sample quad ``t`` (samples
   4t..4t+3 of the frame, ``quads = ceil(bs / 4)``), the 128-bit counter is
   ``(lo32(q), hi32(q), lo32(offset), hi32(offset))`` with ``q = fr * quads + t``, and the key is
   ``(lo32(seed), hi32(seed))``;

@@ -1,5 +1,5 @@
-"""The synthesis VJP kernels (csrc/backward.hip: frame_backward_kernel, noise_vjp_wave_kernel) at every branch
-their shape arithmetic takes, against the high-precision references of tests/vjp_ref.py, checked PER FRAME:
+"""The synthesis VJP kernels (csrc/backward.hip: harmonic_vjp_kernel, noise_vjp_kernel, noise_vjp_wave_kernel) at every
+branch their shape arithmetic takes, against the high-precision references of tests/vjp_ref.py, checked PER FRAME:
 max over (b, f) of ||got - ref||_2 / ||ref||_2 <= GRAD_REL (1e-5, the project's gradient tolerance), and the
 whole-tensor relative L2 as well.  One wrong frame among hundreds, or one wrong band of one frame (a partly empty
 last workgroup, the Nyquist band, the DC band's factor, the last lag segment), passes a whole-tensor check; it does
@@ -11,7 +11,8 @@ The kernels are called directly (grad.params_backward, grad.noise_backward, ddsp
 as SynthFramesHarmonicFn.backward calls it), so the forward kernels' envelopes do not limit the shapes; cases 2, a
 and c run through the public autograd route too.  Sample rate 48000, f0 = 50 * 20**U per frame, upstream randn.
 
-Harmonic part, (B, F, H, bs), HMODE 2 (raw param) and HMODE 1 (frame controls).  harmonic_backward_shape works
+Harmonic part, (B, F, H, bs), harmonic_vjp_kernel<true> (raw param, "HMODE 2" below) and <false> (frame controls,
+"HMODE 1").  harmonic_backward_shape (csrc/harmonic_frame.h) works
 from kq = ceil(H/4), ns = clamp(min(128/kq, bs), 1, 64), nt = min(512, roundup64(kq ns)), SL = ((bs+ns-1)/ns+1)&~1.
 Per frame the kernel takes its padded hardware-sine loop when H bs inc >= 16 rad and max |omega| H < 8e6 (`fast_s`),
 else the general loop (polynomial sine, sin_slow past 8e6): "fast" / "general" below says which one the case's
@@ -49,10 +50,6 @@ Noise part, (B, F, bs, NB), n = 2 (NB - 1) taps, raw_bias = -5.0 (RAW) and None,
    l  (2, 3, 441, 18), (1, 3, 30, 33)     generic kernel, Philox noise at bs % 4 != 0, same seed and offset
    m  (1, 2, 8, 65)      n = 128 > 9 bs + 8: the cosine transform's n partial sums need more than the NSEG * bs = 64
                          floats of the correlation's partials (they used to run past the workgroup's LDS)
-
-Not reachable, so not tested: the one-launch harmonic + noise instantiations of frame_backward_kernel (SPEC: the
-extra noise wave beside the sine waves).  ddsp_hip_synth_frames_backward issues two launches, and no caller passes
-hmode = 2 together with a noise mode.
 
 Largest per-frame error measured on an MI355X (a record; the assertion is GRAD_REL), beside the fp32 oracle's on the
 CPU (tests/test_vjp_ref.py):

@@ -1,7 +1,7 @@
 """Guard of the oscillator loops' code placement: the fused synthesis kernel ran
 ~10 % faster on MI355X (135-137 vs 148-149 us at config 2) when the 8-byte instructions of its
 sine loop sit at odd dword addresses (address % 8 == 4).  Any edit to synth_frame.hip, common.h,
-noise_dsp.h or backward.hip, or a compiler update, can move the loop; this test reads the built
+noise_dsp.h, harmonic_frame.h or backward.hip, or a compiler update, can move the loop; this test reads the built
 library's ISA (llvm-objdump, no GPU) and fails when a throughput kernel lost the fast placement.
 """
 import os
@@ -20,7 +20,7 @@ LIB = os.path.join(ROOT, "ddsp_pytorch_amd", "lib", "libddsp_hip.so")
 # which are latency-bound: reported, not pinned.
 PINNED = ("synth_frame_kernelILb1ELb0ELb0ELb0EE", "synth_frame_kernelILb0ELb0ELb0ELb0EE",
           "synth_frame_kernelILb1ELb0ELb1ELb0EE", "synth_frame_kernelILb0ELb0ELb1ELb0EE",
-          "frame_backward_kernelILi2ELi0ELb0EE", "frame_backward_kernelILi1ELi0ELb0EE")
+          "harmonic_vjp_kernelILb1EE", "harmonic_vjp_kernelILb0EE")
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libddsp_hip.so not built (make)")

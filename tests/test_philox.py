@@ -1,6 +1,6 @@
 """The host restatement of the on-device noise generator (oracle/philox.py), pinned to the
 published Philox4x32-10 known-answer vectors (Random123, Salmon et al. SC'11) and to the counter
-layout the kernels use (synth_frame.hip:71-76, noise.hip:96-103, backward.hip:173-180)."""
+layout the kernels use (synth_frame.hip:71-76, noise.hip:96-103, backward.hip:255-262)."""
 import numpy as np
 import pytest
 

@@ -1,4 +1,4 @@
-"""The yardstick of the synthesis VJP kernels (``csrc/backward.hip``: frame_backward_kernel and
+"""The yardstick of the synthesis VJP kernels (``csrc/backward.hip``: harmonic_vjp_kernel, noise_vjp_kernel and
 noise_vjp_wave_kernel): high-precision references of the gradients, the shape cases that reach the kernels'
 branches, and the per-frame error metric.  Test infrastructure only (torch on the CPU, no device code); shared by
 tests/test_vjp_ref.py (which ties it to the fp32 oracle's autograd) and tests/test_gpu_vjp_shapes.py.

@@ -13,7 +13,7 @@ for f in $(git ls-tree --name-only $COMMIT ddsp_pytorch_amd/csrc/); do
 done
 git show $COMMIT:include/ddsp_hip.h > $SRC/include/ddsp_hip.h
 HIPFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I$SRC/include -Ibuild -Wno-unused-result"
-case $STEM in synth|synth_frame|backward) HIPFLAGS="$HIPFLAGS -fno-slp-vectorize";; esac
+case $STEM in synth|synth_frame|backward|pitch_grad) HIPFLAGS="$HIPFLAGS -fno-slp-vectorize";; esac
 /opt/rocm/bin/hipcc $HIPFLAGS "$@" -c $SRC/csrc/$STEM.hip -o build/ab_${NAME}_$STEM.o
 OBJS=$(ls build/*.o | grep -v "/ab_" | grep -v "/$STEM.o")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o build/ab_$NAME.so $OBJS build/ab_${NAME}_$STEM.o

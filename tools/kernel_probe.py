@@ -25,7 +25,7 @@ def main():
         F = int(sys.argv[3])
     inp = make_inputs(B, F, H, NB, bs, seed=0, device=dev, with_noise=False)
     syn = SynthPath(bs, sr, reverb_length=48000).to(dev)
-    if which == "bwd":  # the fused synthesis backward (frame_backward_kernel<2, 2, true>)
+    if which == "bwd":  # the fused synthesis backward's two launches (harmonic_vjp_kernel<true>, noise_vjp_wave_kernel<2, true>)
         param = inp["param"].clone().requires_grad_(True)
         mags = inp["mags"].clone().requires_grad_(True)
         out = core.synth_frames(inp["f0"], param, mags, bs, sr)
@@ -34,7 +34,7 @@ def main():
             out.backward(g, retain_graph=True)
         torch.cuda.synchronize()
         return
-    if which == "pitch_grad":  # the harmonic VJP (frame_backward_kernel<2, 0, false>) and, beside it in the same
+    if which == "pitch_grad":  # the harmonic VJP (harmonic_vjp_kernel<true>) and, beside it in the same
         # backward, the pitch gradient's two launches (frame_pitch_grad_kernel<true>, pitch_grad_scan_kernel)
         param = inp["param"].clone().requires_grad_(True)
         f0 = inp["f0"].clone().requires_grad_(True)

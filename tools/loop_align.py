@@ -113,13 +113,13 @@ def analyze_all(so, kern="synth_frame_kernelILb1ELb0ELb0ELb0EE"):
 
 # every shipped instantiation with a hardware-sine loop: fused forward (device noise / injected
 # noise; the fixed-shape form of 65 bands at block 512, one sample per thread for few-frame launches,
-# the any-shape form <RNG, CTRL, PREFIX> of every other shape), the harmonic-only fused backward
+# the any-shape form <RNG, CTRL, PREFIX> of every other shape), the harmonic VJP (raw params / frame controls)
 SHIPPED = ("synth_frame_kernelILb1ELb0ELb0ELb0EE", "synth_frame_kernelILb0ELb0ELb0ELb0EE",
            "synth_frame_kernelILb1ELb1ELb0ELb0EE", "synth_frame_kernelILb0ELb1ELb0ELb0EE",
            "synth_frame_kernelILb1ELb0ELb1ELb0EE", "synth_frame_kernelILb0ELb0ELb1ELb0EE",
            "synth_frame_any_kernelILb1ELb0ELb0EE", "synth_frame_any_kernelILb0ELb0ELb0EE",
            "synth_frame_any_kernelILb1ELb1ELb0EE", "synth_frame_any_kernelILb0ELb1ELb0EE",
-           "frame_backward_kernelILi2ELi2ELb1EE")
+           "harmonic_vjp_kernelILb1EE", "harmonic_vjp_kernelILb0EE")
 
 
 def report(so, kern):
